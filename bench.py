@@ -10,8 +10,23 @@ call, relays the child's JSON line and exits with its code (the reference's coun
 A step = one pass of the hot path over one batch that is already resident in HBM:
 fused gather -> expert/gate/tower MLPs (fp32 MFMA) -> heads + summed BCE -> backward (dgrad/wgrad GEMMs, gate/head
 backward, sparse row-scatter) -> optimizer (reference-exact dense Adam over every table row + MLP parameters).
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, HIP-event timed in a
-second, instrumented pass over the same batches) and `cpu_baseline` (the oracle timed on the host, N=1 only).
+Prints ONE JSON line on rank 0: `metric`, `value` (samples/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` and
+the run's configuration.  A plain run does only that: set-up, the warm-up steps, the K timed steps, the line.
+
+--full adds everything else the benchmark measures or checks: `roofline` / `kernels_ms_per_step` / `whole_step` (a
+second, HIP-event instrumented pass over the same batches), the `alt` batch, `inference`, `lazy_exact`, the `configs`
+block (BASELINE.json's other configurations), `cpu_baseline` (the oracle timed on the host, N=1 only), the loss check
+against tests/golden/bench_losses_*.json and, for N > 1, the collectives preflight and check.  The --no-* options and
+--alt-batch / --cpu-* / --lazy-epoch-steps shape those parts.
+
+--dump-outputs DIR writes what the last timed step computed -- the step's predictions and loss, the MLP parameters
+and a fixed, seeded sample of every table's rows after the update -- as DIR/<name>.npy (float32), on rank 0.
+
+One GPU times the step with the deterministic table-gradient scatter (integer fixed-point row totals): the inputs are
+seeded, so two runs with the same arguments compute the same bits.  With float atomics (--scatter-mode atomic, ~4 %
+faster) the summation order changes from run to run, and the free-running trajectory on four rotated batches turns
+that into differences far beyond rounding within a few dozen steps.  Sharded tables (N > 1) take the atomic scatter:
+the deterministic form has no sharded variant.
 """
 import argparse
 import gc
@@ -61,11 +76,18 @@ def parse():
     ap.add_argument("--cpu-batch", type=int, default=4096)
     ap.add_argument("--cpu-steps", type=int, default=10)
     ap.add_argument("--cpu-big-steps", type=int, default=3, help="cpu_baseline: steps at the headline batch (0 = skip)")
-    ap.add_argument("--scatter-mode", default="atomic", choices=["atomic", "deterministic"],
-                    help="deterministic: table gradients as order-independent integer fixed-point sums (bitwise repeatable)")
+    ap.add_argument("--scatter-mode", default=None, choices=["atomic", "deterministic"],
+                    help="deterministic (the default on one GPU): table gradients as order-independent integer "
+                         "fixed-point sums, bitwise repeatable runs; atomic: float atomics (the default for N > 1)")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the `configs` block (BASELINE.json's other configurations, a few steps each)")
     ap.add_argument("--no-loss-check", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary measurements and checks (roofline / per-kernel pass, alt batch, inference, "
+                         "lazy_exact, configs, cpu_baseline, loss check, collectives check); off: the headline line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (predictions, loss, parameters; tables as a seeded row "
+                         "sample) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -232,6 +254,46 @@ def timed_steps(runner, batches, steps, warmup, dist, flush=None, warm_losses=No
     if flush is not None:
         return dt, t_flush
     return dt
+
+
+DUMP_HEAD_ROWS = 2048     # the Zipf head of every table: rows every batch touches
+DUMP_SAMPLE_ROWS = 2048   # plus this many rows drawn uniformly (seeded) over the whole table
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(runner, model, out_dir, write=True):
+    """What a caller of the timed step receives after its last call: the predictions [B, T] and the summed BCE loss
+    (plan.prob / plan.loss) and the updated parameters (model.state_dict()).  Tensors with more than
+    DUMP_HEAD_ROWS + DUMP_SAMPLE_ROWS rows (the embedding tables) are written as the rows
+    0 .. DUMP_HEAD_ROWS-1 plus a seeded uniform sample, the same rows in every run with the same arguments.  Everything
+    as float32 (integer buffers as float64), DIR/<name>.npy, at most DUMP_LIMIT_BYTES in all.
+    Every rank calls this: state_dict() first brings sharded tables up to date with collectives; only the rank with
+    `write` (rank 0: its own batch's predictions and loss, the full tables) writes the files."""
+    import numpy as np
+    torch.cuda.synchronize()
+    state = model.state_dict()
+    if not write:
+        return 0
+    arrays = {"prob": runner.plan.prob.detach().float().cpu().numpy(),
+              "loss": runner.plan.loss.detach().float().cpu().numpy()}
+    for k, v in state.items():
+        v = v.detach()
+        if v.dim() >= 1 and v.shape[0] > DUMP_HEAD_ROWS + DUMP_SAMPLE_ROWS:
+            n = v.shape[0]
+            g = torch.Generator().manual_seed(12345)
+            rows = torch.cat([torch.arange(DUMP_HEAD_ROWS),
+                              torch.randint(DUMP_HEAD_ROWS, n, (DUMP_SAMPLE_ROWS,), generator=g)]).unique()
+            v = v.index_select(0, rows.to(v.device))
+        a = v.cpu()
+        a = a.double().numpy() if not a.is_floating_point() else a.float().numpy()
+        arrays["param." + k] = a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def kernel_breakdown(runner, batches, steps):
@@ -592,183 +654,15 @@ def describe_workload(name, cfg, vocab, dense):
             f"{', '.join(parts)}, {cfg['optim_config']['optimizer']} lr {cfg['optim_config']['lr']}")
 
 
-def main():
-    args = parse()
-    forced = os.environ.get("MMLREC_BENCH_FORCE_SHARD") == "1"
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not forced:
-        sys.exit(spawn_ranks(args))
-    world_env = int(os.environ.get("WORLD_SIZE", "1"))
-    if world_env != args.gpus and not forced:  # a silent 1-GPU measurement labelled otherwise helps nobody
-        print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world_env}", file=sys.stderr)
-        sys.exit(2)
-    rank, local, world, dist = dist_setup(args.gpus)
-    dev = torch.device("cuda", local)
-    import mmlrec_amd  # noqa: F401
-    from mmlrec_amd import workloads as W
-    if args.profile:
-        from mmlrec_amd import profiling
-        profiling.enable()
-
-    model, cfg, vocab, dense = W.build_model(args.workload, dev, table_update=args.table_update,
-                                             use_hip_graph=not args.no_graph, scatter_mode=args.scatter_mode)
-    model.compile(cfg["optim_config"]["optimizer"], cfg["optim_config"]["loss"], cfg["optim_config"]["metrics"])
-    model.train()
-    T = W.num_tasks(cfg)
-
-    allreduce = None
-    # MMLREC_BENCH_FORCE_SHARD=1 with --gpus 2 and WORLD_SIZE=1 walks the table-sharded code path (exchange, no HIP
-    # graph, per-call timing of the collectives) on a single GPU: a smoke test of the N > 1 bench, not a measurement
-    if world > 1 or (dist is not None and forced):
-        from mmlrec_amd import parallel
-        parallel.shard_model(model, dist, args.batch, mode=args.parallel_mode)
-
-    def make_batches(B):
-        out = []
-        for i in range(4):
-            X, y = W.synth_batch(vocab, len(dense), B, T, seed=1 + i + 1000 * rank, dist=args.dist)
-            out.append((X.to(dev), y.to(dev)))
-        return out
-
-    results = {}
-    for B in [args.batch] + ([args.alt_batch] if args.alt_batch and args.alt_batch != args.batch else []):
-        batches = make_batches(B)
-        runner = model.train_step_runner(B, use_graph=not args.no_graph, allreduce=allreduce, overlap=(args.streams == 2 and not args.serial),
-                                         split_dense="force" if args.split_dense else False)
-        if B == args.batch and getattr(model, "_parallel", None) is not None:
-            # PREFLIGHT (before anything is timed; every rank computes it, rank 0 prints it): what DESIGN section 5's model
-            # says one step of THIS run exchanges per rank -- the JSON line repeats it next to what was counted inside the
-            # timed region and says whether the two agree (collectives_per_step.check)
-            Xi = batches[0][0][:, :len(vocab)].long()
-            pre = dict(distinct_rows=int(sum(torch.unique(Xi[:, f]).numel() for f in range(len(vocab)))),
-                       emb=int(cfg["model_config"]["emb"]), arena_bytes=int(runner.store.arena.numel() * 4))
-            exp = expected_collectives(args, world, pre)
-            if rank == 0:
-                print("bench.py preflight: world %d, mode %s, batch %d per rank -> expected per step and rank: %s"
-                      % (world, args.parallel_mode, B, json.dumps(exp)), file=sys.stderr, flush=True)
-        steps = args.steps if B == args.batch else max(args.steps, 50)
-        warm_losses = [] if (B == args.batch and world == 1 and getattr(model, "_parallel", None) is None) else None
-        dt = timed_steps(runner, batches, steps, args.warmup, dist, warm_losses=warm_losses)
-        results[B] = dict(dt=dt, steps=steps, value=world * B * steps / dt, ms=dt / steps * 1e3,
-                          loss=float(runner.plan.loss.item()) / B, warm_losses=warm_losses)
-        if B == args.batch:
-            runner0 = runner
-            if getattr(model, "_parallel", None) is not None:
-                Xi = batches[0][0][:, :len(vocab)].long()
-                results[B]["distinct_rows"] = int(sum(torch.unique(Xi[:, f]).numel() for f in range(len(vocab))))
-                results[B]["emb"] = int(cfg["model_config"]["emb"])
-                results[B]["arena_bytes"] = int(runner.store.arena.numel() * 4)
-        acc = kernel_breakdown(runner, batches, min(args.steps, 10))
-        results[B]["acc"] = acc
-        results[B]["bsteps"] = min(args.steps, 10)
-        # did the run stay a training run?  (the summed-BCE kernel clamps log p at -100 with fmaxf, which also swallows a
-        # NaN: a diverged model keeps reporting a finite loss.  snr_trans_ae30 on two alternating batches overfits to
-        # loss 0.004 by step 31 and has all-NaN input gradients by step 41 -- and a scatter that takes 4 ms for them)
-        gin = runner.plan.layer_outputs.get("dnn_input") if hasattr(runner.plan, "layer_outputs") else None
-        results[B]["finite"] = bool(gin is None or gin.grad is None or torch.isfinite(gin.grad).all().item())
-
-    # forward-only path (SURVEY 8(f) rank 2: predict / evaluate reuse the gather, GEMM, gate and head kernels):
-    # model.forward in eval mode under no_grad, as predict() calls it -- includes the input copy, the output clone
-    # and the embedding-status check (one host sync per call)
-    infer = None
-    if world == 1:
-        B = args.batch
-        batches = make_batches(B)
-        model.eval()
-        import gc
-        with torch.no_grad():
-            for i in range(3):
-                model(batches[i % 4][0])
-            torch.cuda.synchronize()
-            gc.collect()   # (as in timed_steps: a cyclic-GC pass that destroys the HIP graphs / events of the earlier
-            gc.disable()   # phases inside the timed loop costs tens of ms once)
-            n_inf = max(args.steps, 20)
-            t0 = time.perf_counter()
-            for i in range(n_inf):
-                model(batches[i % 4][0])
-            torch.cuda.synchronize()
-            dt = time.perf_counter() - t0
-            gc.enable()
-        model.train()
-        infer = {"value": round(B * n_inf / dt, 1), "unit": "samples/s", "batch": B, "ms_per_batch": round(dt / n_inf * 1e3, 4),
-                 "path": "model.forward(X) in eval mode under no_grad (what predict() runs per batch)"}
-
-    # secondary measurement: the lazy_exact table optimizer (dense-Adam trajectory at touched-row cost); its timed
-    # region ENDS with the flush that brings every one of the 12.49 M rows to the reference state
-    lazy = {}
-    if world == 1 and args.table_update != "lazy_exact" and not args.no_lazy:
-        del runner
-        model2, _, _, _ = W.build_model(args.workload, dev, table_update="lazy_exact", use_hip_graph=not args.no_graph)
-        model2.compile(cfg["optim_config"]["optimizer"], cfg["optim_config"]["loss"], cfg["optim_config"]["metrics"])
-        model2.train()
-        for B in [args.batch] + ([args.alt_batch] if args.alt_batch and args.alt_batch != args.batch else []):
-            batches = make_batches(B)
-            r2 = model2.train_step_runner(B, use_graph=not args.no_graph)
-            steps = args.steps if B == args.batch else max(args.steps, 50)
-            dt, tf = timed_steps(r2, batches, steps, args.warmup, dist, flush=model2.flush_tables)
-            lazy[B] = {"batch_per_gpu": B, "unit": "samples/s", "steps": steps,
-                       "value_incl_final_flush": round(B * steps / dt, 1),
-                       "value_steps_only": round(B * steps / (dt - tf), 1),
-                       "ms_per_step_steps_only": round((dt - tf) / steps * 1e3, 4), "final_flush_ms": round(tf * 1e3, 3)}
-            if B == args.batch and args.lazy_epoch_steps > 0:
-                # steady state (VERDICT r3): an "epoch" of lazy_epoch_steps steps, then the flush a fit() epoch ends with:
-                # rows no batch touched replay that many zero-gradient steps there
-                n_ep = args.lazy_epoch_steps
-                dt2, tf2 = timed_steps(r2, batches, n_ep, 0, dist, flush=model2.flush_tables)
-                lazy[B]["epoch"] = {"steps": n_ep, "ms_per_step_steps_only": round((dt2 - tf2) / n_ep * 1e3, 4),
-                                    "flush_ms": round(tf2 * 1e3, 3),
-                                    "value_incl_flush": round(B * n_ep / dt2, 1),
-                                    "note": "flush amortised over an epoch of this many steps (4 resident batches rotated: "
-                                            "the untouched rows skip every step of the epoch)"}
-        del model2
-
-    if dist is not None:
-        barrier(dist)
-        dist.destroy_process_group()
-    if rank != 0:
-        return
-    from mmlrec_amd import _lib
-    gmode = _lib.load().mml_gemm_get_mode()
-    gemm_dtype = {0: "f32", 4: "f32 (GEMMs: fp32-equivalent emulation on the 16-bit MFMA pipe with f32 accumulate -- two scaled fp16 planes "
-                                "per operand where the operand magnitudes travel with the tensors (batches >= 32 768), else three bf16 planes; "
-                                "max-norm error vs float64 3.3e-7 / 4.7e-7, fp32 MFMA 4.3e-7)",
-                  2: "f32 (GEMMs: as mode 4)",
-                  3: "f32 (GEMMs: fp32-equivalent 3-plane bf16 MFMA emulation, f32 accumulate)",
-                  1: "bf16 GEMM operands (rounded in registers), f32 accumulate, f32 everywhere else"}.get(
-        gmode, "f32 operands, GEMM products from 2 bf16 planes (~1e-5 rel), f32 accumulate")
+def full_fields(line, args, cfg, model, dev, world, forced, results, runner0, infer, lazy):
+    """--full: what the benchmark measures and checks beyond the headline figure, added to the result line."""
     main_r = results[args.batch]
     roof = roofline_of(main_r["acc"])
     roof["launches_per_step"] = main_r["acc"][roof["kernel"]]["launches"] / main_r["bsteps"]
-    per = W.algorithmic_per_sample(cfg, vocab, len(dense))
-    line = {
-        "metric": "train-step samples/sec, MMoE AliExpress-shape batch" if args.workload.startswith("mmoe_ae30")
-                  else f"train-step samples/sec, {args.workload}",
-        "value": round(main_r["value"], 1), "unit": "samples/s", "n_gpus": world, "steps": main_r["steps"],
-        "warmup": args.warmup, "ms_per_step": round(main_r["ms"], 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": gemm_dtype, "data": "synthetic",
-        "config": {"workload": describe_workload(args.workload, cfg, vocab, dense),
-                   "batch_per_gpu": args.batch, "global_batch": args.batch * world, "index_dist": args.dist,
-                   "table_update": model.optimizer().table_update,
-                   "dense_update_schedule": ("split: untouched rows beside the forward, touched rows after the scatter"
-                                             if getattr(runner0, "split_dense", False) else
-                                             ("one launch after the scatter, gradients read for marked rows only"
-                                              if getattr(runner0, "grad_marks", False) else "one launch after the scatter")),
-                   "hip_graph": not args.no_graph, "scatter_mode": args.scatter_mode,
-                   "hip_runtime": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG")},
-                   "streams": 1 if not getattr(runner0, "overlap", True) else (3 if getattr(runner0, "split_dense", False) else 2),
-                   "early_fork": int(getattr(runner0, "early_fork", 0) or 0),
-                   "tables": "single GPU" if getattr(model, "_parallel", None) is None else
-                             {"row_sharded": "row-wise sharded over ranks (owner = (row + field) mod N), one all-to-all "
-                                             "per direction: keys / rows / row gradients",
-                              "replicated": "replicated, all-gather of (index, row-gradient) pairs",
-                              "table_wise": "table-wise sharded over ranks, all-to-all index/row/grad exchange"}[
-                                 args.parallel_mode],
-                   "algorithmic_per_sample": per},
-        "roofline": roof,
-        "kernels_ms_per_step": {k: round(v["ms"] / main_r["bsteps"], 4) for k, v in
-                                sorted(main_r["acc"].items(), key=lambda kv: -kv[1]["ms"])},
-        "mean_loss_per_sample": round(main_r["loss"], 5),
-        "gradients_finite": main_r.get("finite", True),
-    }
+    line["roofline"] = roof
+    line["kernels_ms_per_step"] = {k: round(v["ms"] / main_r["bsteps"], 4) for k, v in
+                                   sorted(main_r["acc"].items(), key=lambda kv: -kv[1]["ms"])}
+    line["gradients_finite"] = main_r.get("finite", True)
     # the whole step against the HBM roofline (VERDICT r4 item 6): every launch's compulsory bytes -- each distinct
     # operand read once, each output written once; GEMM launches included (engine: `hbm_bytes`) -- over the MEASURED step
     kern = {k: v for k, v in main_r["acc"].items()
@@ -785,8 +679,6 @@ def main():
     if not line["gradients_finite"]:
         sys.stderr.write("bench: the input gradients of the last step are not finite -- the model diverged on this "
                          "synthetic stream; the timing is that of a diverged run\n")
-    if world > 1 or forced:
-        line["rccl_ranks"] = world if os.environ.get("MMLREC_BENCH_SHARE_GPU") != "1" else 0
     # parity of the measured run itself: the losses of the untimed warm-up steps and of the LAST timed step against the
     # oracle's losses for this exact step sequence (tests/golden/make_bench_losses.py; the GPU test
     # test_bench_sequence_losses_match_fixture checks every step).  A mismatch fails the run.
@@ -864,6 +756,191 @@ def main():
         except Exception as e:  # never lose the GPU line to a host-side problem
             line["cpu_baseline"] = {"value": None, "unit": "samples/s", "cores": os.cpu_count(), "kind": "port",
                                     "sample": f"failed: {e!r}"}
+
+
+def main():
+    args = parse()
+    forced = os.environ.get("MMLREC_BENCH_FORCE_SHARD") == "1"
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not forced:
+        sys.exit(spawn_ranks(args))
+    world_env = int(os.environ.get("WORLD_SIZE", "1"))
+    if world_env != args.gpus and not forced:  # a silent 1-GPU measurement labelled otherwise helps nobody
+        print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world_env}", file=sys.stderr)
+        sys.exit(2)
+    rank, local, world, dist = dist_setup(args.gpus)
+    dev = torch.device("cuda", local)
+    full = args.full
+    if args.scatter_mode is None:  # (the deterministic scatter has no form for sharded tables)
+        args.scatter_mode = "atomic" if (args.gpus > 1 or world > 1) else "deterministic"
+    import mmlrec_amd  # noqa: F401
+    from mmlrec_amd import workloads as W
+    if args.profile:
+        from mmlrec_amd import profiling
+        profiling.enable()
+
+    model, cfg, vocab, dense = W.build_model(args.workload, dev, table_update=args.table_update,
+                                             use_hip_graph=not args.no_graph, scatter_mode=args.scatter_mode)
+    model.compile(cfg["optim_config"]["optimizer"], cfg["optim_config"]["loss"], cfg["optim_config"]["metrics"])
+    model.train()
+    T = W.num_tasks(cfg)
+
+    allreduce = None
+    # MMLREC_BENCH_FORCE_SHARD=1 with --gpus 2 and WORLD_SIZE=1 walks the table-sharded code path (exchange, no HIP
+    # graph, per-call timing of the collectives) on a single GPU: a smoke test of the N > 1 bench, not a measurement
+    if world > 1 or (dist is not None and forced):
+        from mmlrec_amd import parallel
+        parallel.shard_model(model, dist, args.batch, mode=args.parallel_mode)
+
+    def make_batches(B):
+        out = []
+        for i in range(4):
+            X, y = W.synth_batch(vocab, len(dense), B, T, seed=1 + i + 1000 * rank, dist=args.dist)
+            out.append((X.to(dev), y.to(dev)))
+        return out
+
+    results = {}
+    for B in [args.batch] + ([args.alt_batch] if full and args.alt_batch and args.alt_batch != args.batch else []):
+        batches = make_batches(B)
+        runner = model.train_step_runner(B, use_graph=not args.no_graph, allreduce=allreduce, overlap=(args.streams == 2 and not args.serial),
+                                         split_dense="force" if args.split_dense else False)
+        if full and B == args.batch and getattr(model, "_parallel", None) is not None:
+            # PREFLIGHT (before anything is timed; every rank computes it, rank 0 prints it): what DESIGN section 5's model
+            # says one step of THIS run exchanges per rank -- the JSON line repeats it next to what was counted inside the
+            # timed region and says whether the two agree (collectives_per_step.check)
+            Xi = batches[0][0][:, :len(vocab)].long()
+            pre = dict(distinct_rows=int(sum(torch.unique(Xi[:, f]).numel() for f in range(len(vocab)))),
+                       emb=int(cfg["model_config"]["emb"]), arena_bytes=int(runner.store.arena.numel() * 4))
+            exp = expected_collectives(args, world, pre)
+            if rank == 0:
+                print("bench.py preflight: world %d, mode %s, batch %d per rank -> expected per step and rank: %s"
+                      % (world, args.parallel_mode, B, json.dumps(exp)), file=sys.stderr, flush=True)
+        steps = args.steps if B == args.batch else max(args.steps, 50)
+        warm_losses = [] if (full and B == args.batch and world == 1 and getattr(model, "_parallel", None) is None) else None
+        dt = timed_steps(runner, batches, steps, args.warmup, dist, warm_losses=warm_losses)
+        results[B] = dict(dt=dt, steps=steps, value=world * B * steps / dt, ms=dt / steps * 1e3,
+                          loss=float(runner.plan.loss.item()) / B, warm_losses=warm_losses)
+        if B == args.batch:
+            runner0 = runner
+            if args.dump_outputs:  # before anything else runs a step on this model; every rank (collectives), rank 0 writes
+                dump_outputs(runner, model, args.dump_outputs, write=(rank == 0))
+        if not full:
+            continue
+        if B == args.batch:
+            if getattr(model, "_parallel", None) is not None:
+                Xi = batches[0][0][:, :len(vocab)].long()
+                results[B]["distinct_rows"] = int(sum(torch.unique(Xi[:, f]).numel() for f in range(len(vocab))))
+                results[B]["emb"] = int(cfg["model_config"]["emb"])
+                results[B]["arena_bytes"] = int(runner.store.arena.numel() * 4)
+        acc = kernel_breakdown(runner, batches, min(args.steps, 10))
+        results[B]["acc"] = acc
+        results[B]["bsteps"] = min(args.steps, 10)
+        # did the run stay a training run?  (the summed-BCE kernel clamps log p at -100 with fmaxf, which also swallows a
+        # NaN: a diverged model keeps reporting a finite loss.  snr_trans_ae30 on two alternating batches overfits to
+        # loss 0.004 by step 31 and has all-NaN input gradients by step 41 -- and a scatter that takes 4 ms for them)
+        gin = runner.plan.layer_outputs.get("dnn_input") if hasattr(runner.plan, "layer_outputs") else None
+        results[B]["finite"] = bool(gin is None or gin.grad is None or torch.isfinite(gin.grad).all().item())
+
+    # forward-only path (SURVEY 8(f) rank 2: predict / evaluate reuse the gather, GEMM, gate and head kernels):
+    # model.forward in eval mode under no_grad, as predict() calls it -- includes the input copy, the output clone
+    # and the embedding-status check (one host sync per call)
+    infer = None
+    if full and world == 1:
+        B = args.batch
+        batches = make_batches(B)
+        model.eval()
+        import gc
+        with torch.no_grad():
+            for i in range(3):
+                model(batches[i % 4][0])
+            torch.cuda.synchronize()
+            gc.collect()   # (as in timed_steps: a cyclic-GC pass that destroys the HIP graphs / events of the earlier
+            gc.disable()   # phases inside the timed loop costs tens of ms once)
+            n_inf = max(args.steps, 20)
+            t0 = time.perf_counter()
+            for i in range(n_inf):
+                model(batches[i % 4][0])
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            gc.enable()
+        model.train()
+        infer = {"value": round(B * n_inf / dt, 1), "unit": "samples/s", "batch": B, "ms_per_batch": round(dt / n_inf * 1e3, 4),
+                 "path": "model.forward(X) in eval mode under no_grad (what predict() runs per batch)"}
+
+    # secondary measurement: the lazy_exact table optimizer (dense-Adam trajectory at touched-row cost); its timed
+    # region ENDS with the flush that brings every one of the 12.49 M rows to the reference state
+    lazy = {}
+    if full and world == 1 and args.table_update != "lazy_exact" and not args.no_lazy:
+        del runner
+        model2, _, _, _ = W.build_model(args.workload, dev, table_update="lazy_exact", use_hip_graph=not args.no_graph)
+        model2.compile(cfg["optim_config"]["optimizer"], cfg["optim_config"]["loss"], cfg["optim_config"]["metrics"])
+        model2.train()
+        for B in [args.batch] + ([args.alt_batch] if args.alt_batch and args.alt_batch != args.batch else []):
+            batches = make_batches(B)
+            r2 = model2.train_step_runner(B, use_graph=not args.no_graph)
+            steps = args.steps if B == args.batch else max(args.steps, 50)
+            dt, tf = timed_steps(r2, batches, steps, args.warmup, dist, flush=model2.flush_tables)
+            lazy[B] = {"batch_per_gpu": B, "unit": "samples/s", "steps": steps,
+                       "value_incl_final_flush": round(B * steps / dt, 1),
+                       "value_steps_only": round(B * steps / (dt - tf), 1),
+                       "ms_per_step_steps_only": round((dt - tf) / steps * 1e3, 4), "final_flush_ms": round(tf * 1e3, 3)}
+            if B == args.batch and args.lazy_epoch_steps > 0:
+                # steady state (VERDICT r3): an "epoch" of lazy_epoch_steps steps, then the flush a fit() epoch ends with:
+                # rows no batch touched replay that many zero-gradient steps there
+                n_ep = args.lazy_epoch_steps
+                dt2, tf2 = timed_steps(r2, batches, n_ep, 0, dist, flush=model2.flush_tables)
+                lazy[B]["epoch"] = {"steps": n_ep, "ms_per_step_steps_only": round((dt2 - tf2) / n_ep * 1e3, 4),
+                                    "flush_ms": round(tf2 * 1e3, 3),
+                                    "value_incl_flush": round(B * n_ep / dt2, 1),
+                                    "note": "flush amortised over an epoch of this many steps (4 resident batches rotated: "
+                                            "the untouched rows skip every step of the epoch)"}
+        del model2
+
+    if dist is not None:
+        barrier(dist)
+        dist.destroy_process_group()
+    if rank != 0:
+        return
+    from mmlrec_amd import _lib
+    gmode = _lib.load().mml_gemm_get_mode()
+    gemm_dtype = {0: "f32", 4: "f32 (GEMMs: fp32-equivalent emulation on the 16-bit MFMA pipe with f32 accumulate -- two scaled fp16 planes "
+                                "per operand where the operand magnitudes travel with the tensors (batches >= 32 768), else three bf16 planes; "
+                                "max-norm error vs float64 3.3e-7 / 4.7e-7, fp32 MFMA 4.3e-7)",
+                  2: "f32 (GEMMs: as mode 4)",
+                  3: "f32 (GEMMs: fp32-equivalent 3-plane bf16 MFMA emulation, f32 accumulate)",
+                  1: "bf16 GEMM operands (rounded in registers), f32 accumulate, f32 everywhere else"}.get(
+        gmode, "f32 operands, GEMM products from 2 bf16 planes (~1e-5 rel), f32 accumulate")
+    main_r = results[args.batch]
+    per = W.algorithmic_per_sample(cfg, vocab, len(dense))
+    line = {
+        "metric": "train-step samples/sec, MMoE AliExpress-shape batch" if args.workload.startswith("mmoe_ae30")
+                  else f"train-step samples/sec, {args.workload}",
+        "value": round(main_r["value"], 1), "unit": "samples/s", "n_gpus": world, "steps": main_r["steps"],
+        "warmup": args.warmup, "ms_per_step": round(main_r["ms"], 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": gemm_dtype, "data": "synthetic",
+        "config": {"workload": describe_workload(args.workload, cfg, vocab, dense),
+                   "batch_per_gpu": args.batch, "global_batch": args.batch * world, "index_dist": args.dist,
+                   "table_update": model.optimizer().table_update,
+                   "dense_update_schedule": ("split: untouched rows beside the forward, touched rows after the scatter"
+                                             if getattr(runner0, "split_dense", False) else
+                                             ("one launch after the scatter, gradients read for marked rows only"
+                                              if getattr(runner0, "grad_marks", False) else "one launch after the scatter")),
+                   "hip_graph": not args.no_graph, "scatter_mode": args.scatter_mode,
+                   "hip_runtime": {"HIP_FORCE_DEV_KERNARG": os.environ.get("HIP_FORCE_DEV_KERNARG")},
+                   "streams": 1 if not getattr(runner0, "overlap", True) else (3 if getattr(runner0, "split_dense", False) else 2),
+                   "early_fork": int(getattr(runner0, "early_fork", 0) or 0),
+                   "tables": "single GPU" if getattr(model, "_parallel", None) is None else
+                             {"row_sharded": "row-wise sharded over ranks (owner = (row + field) mod N), one all-to-all "
+                                             "per direction: keys / rows / row gradients",
+                              "replicated": "replicated, all-gather of (index, row-gradient) pairs",
+                              "table_wise": "table-wise sharded over ranks, all-to-all index/row/grad exchange"}[
+                                 args.parallel_mode],
+                   "algorithmic_per_sample": per},
+        "mean_loss_per_sample": round(main_r["loss"], 5),
+    }
+    if world > 1 or forced:
+        line["rccl_ranks"] = world if os.environ.get("MMLREC_BENCH_SHARE_GPU") != "1" else 0
+    if full:
+        full_fields(line, args, cfg, model, dev, world, forced, results, runner0, infer, lazy)
     # RCCL writes its version banner through C stdio (block-buffered when stdout is a pipe or a file): push it out
     # first, so that the JSON line is the LAST line of stdout
     import ctypes

@@ -311,9 +311,12 @@ def _bench_oracle(W, cfg, names, vocab, dense, start, nsteps=3):
     return c["losses"], c["params"], c["Xs"]
 
 
-def _bench_model(W, table_update):
-    """Exactly what bench.py builds: mmoe_ae30, reference initialisation (seed 0, built on the host), HIP graphs on."""
-    model, cfg, vocab, dense = W.build_model("mmoe_ae30", dev(), table_update=table_update, use_hip_graph=True)
+def _bench_model(W, table_update, scatter_mode=None):
+    """What bench.py builds: mmoe_ae30, reference initialisation (seed 0, built on the host), HIP graphs on.  The library's
+    default scatter (float atomics, what fit() trains with) unless `scatter_mode` says otherwise; bench.py times one GPU
+    with scatter_mode="deterministic" (bitwise repeatable runs)."""
+    kw = {} if scatter_mode is None else dict(scatter_mode=scatter_mode)
+    model, cfg, vocab, dense = W.build_model("mmoe_ae30", dev(), table_update=table_update, use_hip_graph=True, **kw)
     model.compile(cfg["optim_config"]["optimizer"], cfg["optim_config"]["loss"], cfg["optim_config"]["metrics"])
     model.train()
     return model, cfg, vocab, dense
@@ -327,7 +330,18 @@ def test_bench_configuration_steps_match_oracle(W, table_update, streams):
     replays them, step 2 is a pure replay.  Losses, every MLP tensor and every table (touched rows element-wise,
     untouched rows bit for bit) against oracle.train_step on the same batches.  lazy_exact: after the flush that
     state_dict() triggers, the same dense-Adam state."""
-    model, cfg, vocab, dense = _bench_model(W, table_update)
+    _check_bench_steps(W, table_update, streams, None)
+
+
+def test_bench_deterministic_scatter_steps_match_oracle(W):
+    """The step a one-GPU bench.py run times: as test_bench_configuration_steps_match_oracle (B = 65 536, one stream,
+    eager step, capture, replay; losses, MLP tensors, every table against the oracle) with the deterministic
+    table-gradient scatter (integer fixed-point row totals + the finalize launch) -- and that path really taken."""
+    _check_bench_steps(W, "dense_exact", 1, "deterministic")
+
+
+def _check_bench_steps(W, table_update, streams, scatter_mode):
+    model, cfg, vocab, dense = _bench_model(W, table_update, scatter_mode)
     names = [f.name for f in model._sparse_cols()]
     before = {k: v.detach().cpu().numpy().copy() for k, v in model.state_dict().items()}
     B, T, lr = 65536, W.num_tasks(cfg), cfg["optim_config"]["lr"]
@@ -343,6 +357,8 @@ def test_bench_configuration_steps_match_oracle(W, table_update, streams):
         calls = [c for part in runner.whole.parts if part[0] == "c" for c in part[1]]
         assert runner.tower_head_fused and sum(c[0] is lib_.mml_tower_head_fwd_bwd for c in calls) == 1
         assert not any(c[0] is lib_.mml_head_bce_fwd_bwd_phase for c in calls)
+        det = sum(c[0] is lib_.mml_scatter_bwd_det for c in calls)
+        assert det == (1 if scatter_mode == "deterministic" else 0), det
     for i in range(nsteps):
         X, y = W.synth_batch(vocab, 0, B, T, seed=1 + i)
         runner.plan.X.copy_(X.to(dev()))

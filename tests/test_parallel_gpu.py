@@ -285,7 +285,7 @@ def test_bench_two_ranks_control_flow():
         #  on the box takes it in between -- EADDRINUSE, a fault of this harness, not of the run: another port)
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
-               "--warmup", "2", "--batch", "4096", "--alt-batch", "0"]
+               "--warmup", "2", "--batch", "4096", "--alt-batch", "0", "--full"]
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
         if r.returncode == 0 or "EADDRINUSE" not in r.stderr:
             break
@@ -328,7 +328,7 @@ def test_bench_plain_command_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MMLREC_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--batch",
-           "4096", "--alt-batch", "0"]
+           "4096", "--alt-batch", "0", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=850)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -347,3 +347,75 @@ def test_bench_refuses_a_world_that_is_not_gpus():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 2 and "WORLD_SIZE=1" in r.stderr
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain one-GPU bench run prints the headline line only (the secondary measurements and checks are behind --full)
+    and, with --dump-outputs, writes the last timed step's outputs as float32 .npy files; the inputs are seeded and the
+    table gradients are deterministic sums, so a second run with the same arguments dumps the same bits."""
+    import json
+    import subprocess
+
+    def run(out):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch",
+               "4096", "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and r.stdout.rstrip().endswith(lines[0]), r.stdout[-2000:]
+        return json.loads(lines[0])
+
+    d = run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 4096 * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+    for k in ("roofline", "kernels_ms_per_step", "whole_step", "gradients_finite", "alt", "inference", "lazy_exact",
+              "table_update_modes", "configs", "cpu_baseline", "loss_check", "collectives_ms_per_step",
+              "collectives_per_step"):
+        assert k not in d, k
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert "prob.npy" in files and "loss.npy" in files and any(f.startswith("param.embedding_dict.") for f in files)
+    total = 0
+    for f in files:
+        a = np.load(tmp_path / "a" / f)
+        assert a.dtype in (np.float32, np.float64), (f, a.dtype)
+        assert np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    prob = np.load(tmp_path / "a" / "prob.npy")
+    assert prob.shape[0] == 4096 and ((prob >= 0) & (prob <= 1)).all()
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) > 0
+    # same arguments, same inputs, deterministic table-gradient sums: the second run computes the same bits
+    d2 = run(tmp_path / "b")
+    assert d["config"]["scatter_mode"] == d2["config"]["scatter_mode"] == "deterministic"
+    assert sorted(os.listdir(tmp_path / "b")) == files
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+
+
+@pytest.mark.timeout(600)
+def test_bench_two_ranks_dump_outputs(tmp_path):
+    """--dump-outputs with two ranks on row-sharded tables: the dump's state_dict() brings the sharded tables up to date
+    with collectives, so every rank takes part and rank 0 alone writes the files -- the run ends instead of leaving the
+    other rank waiting in a barrier.  Both ranks share the test box's GPU over gloo (MMLREC_BENCH_SHARE_GPU=1)."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(MMLREC_BENCH_SHARE_GPU="1")
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch",
+           "4096", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=500)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["config"]["scatter_mode"] == "atomic" and "row-wise sharded" in d["config"]["tables"]
+    files = sorted(os.listdir(out))
+    assert "prob.npy" in files and "loss.npy" in files and any(f.startswith("param.embedding_dict.") for f in files)
+    assert np.load(out / "prob.npy").shape[0] == 4096
+    for f in files:
+        a = np.load(out / f)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), f

@@ -1,13 +1,15 @@
 #!/bin/bash
 # SURVEY 8(d) "Secondary": the same pure-step measurement for BASELINE configs[1], [2], [4] on one MI355X.
-# One JSON line per run -> gpurun_out/secondary.jsonl (tools/update_profiles.py copies it to profiles/).
-mkdir -p gpurun_out
-out=gpurun_out/secondary.jsonl
+# One JSON line per run -> <output dir>/secondary.jsonl (tools/update_profiles.py copies it to profiles/).
+# usage: tools/bench_secondary.sh <output dir>
+dir=${1:?usage: tools/bench_secondary.sh <output dir>}
+mkdir -p "$dir"
+out=$dir/secondary.jsonl
 : > $out
 run() {  # name, extra env, args...
   local tag=$1; shift
   local envs=$1; shift
-  env $envs timeout 600 python3 bench.py --no-cpu-baseline --no-configs --no-lazy --alt-batch 0 --steps 50 "$@" 2> gpurun_out/secondary_$tag.err | tail -1 \
+  env $envs timeout 600 python3 bench.py --full --no-cpu-baseline --no-configs --no-lazy --alt-batch 0 --steps 50 "$@" 2> ${out%.jsonl}_$tag.err | tail -1 \
     | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); d['tag']='$tag'; print(json.dumps(d))" >> $out \
     || echo "{\"tag\": \"$tag\", \"failed\": true}" >> $out
 }
@@ -25,9 +27,9 @@ done
 # SNR-trans on two alternating batches overfits (loss 0.004 by step 31) and then diverges (all-NaN input gradients by step
 # 41: every run() above takes 5 + 50 + 10 steps): 12 timed steps keep the measurement inside the training regime
 run snr_trans_ae30_b65536 "MMLREC_GEMM_MODE=4" --workload snr_trans_ae30 --batch 65536 --steps 12 --warmup 3
-python3 - <<'PY'
-import json
-for l in open('gpurun_out/secondary.jsonl'):
+python3 - "$out" <<'PY'
+import json, sys
+for l in open(sys.argv[1]):
     d = json.loads(l)
     if d.get('failed'):
         print(d['tag'], 'FAILED'); continue

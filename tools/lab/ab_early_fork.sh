@@ -3,7 +3,7 @@
 one() {  # label, env value, bench args
   local lab=$1 v=$2; shift 2
   echo -n "$lab EARLY_WGRAD=$v  "
-  MMLREC_EARLY_WGRAD=$v python3 bench.py --no-cpu-baseline --no-configs --alt-batch 0 --steps 40 --warmup 5 --no-loss-check "$@" 2>/dev/null | python3 -c "
+  MMLREC_EARLY_WGRAD=$v python3 bench.py --full --no-cpu-baseline --no-configs --alt-batch 0 --steps 40 --warmup 5 --no-loss-check "$@" 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 lz=d.get('lazy_exact')

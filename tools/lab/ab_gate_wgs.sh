@@ -1,7 +1,7 @@
 #!/bin/bash
 # KuaiRec-32 bf16: workgroups per CU of the gate row kernels (H = 256: one sample per wave and trip)
 cd $GRAFT_REPO_ROOT
-run() { env $1 MMLREC_GEMM_MODE=1 python3 bench.py --workload mmoe_kuairec --no-configs --no-cpu-baseline --no-lazy --alt-batch 0 --table-update auto --steps 30 --warmup 5 --no-loss-check 2>/dev/null | python3 -c "
+run() { env $1 MMLREC_GEMM_MODE=1 python3 bench.py --full --workload mmoe_kuairec --no-configs --no-cpu-baseline --no-lazy --alt-batch 0 --table-update auto --steps 30 --warmup 5 --no-loss-check 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,7 +2,7 @@
 # cut-once kernel for launches of >= 16 tiles), 1 (every qualifying launch).  usage: bash tools/lab/ab_nt.sh [reps] [workload]
 N=${1:-2}
 WL=${2:-mmoe_ae30}
-run() { MMLREC_GEMM_NT=$1 python bench.py --workload $WL --steps 60 --warmup 10 --no-cpu-baseline --no-lazy --alt-batch 0 --no-configs --no-loss-check 2>/dev/null | python -c "
+run() { MMLREC_GEMM_NT=$1 python bench.py --full --workload $WL --steps 60 --warmup 10 --no-cpu-baseline --no-lazy --alt-batch 0 --no-configs --no-loss-check 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

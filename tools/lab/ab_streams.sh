@@ -3,7 +3,7 @@
 N=${1:-3}
 B=${2:-65536}
 WL=${3:-mmoe_ae30}
-run() { python bench.py --workload $WL --batch $B --steps 60 --warmup 10 --no-cpu-baseline --no-lazy --alt-batch 0 --no-configs --no-loss-check $2 2>/dev/null | python -c "
+run() { python bench.py --full --workload $WL --batch $B --steps 60 --warmup 10 --no-cpu-baseline --no-lazy --alt-batch 0 --no-configs --no-loss-check $2 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,7 +1,7 @@
 #!/bin/bash
 one() {
   echo -n "TAIL_BLOCKS=$1 U=$2  "
-  MMLREC_TAIL_BLOCKS=$1 MMLREC_OPT_U=$2 python3 bench.py --no-cpu-baseline --no-configs --no-lazy --alt-batch 0 --steps 60 --warmup 10 --no-loss-check 2>/dev/null | python3 -c "
+  MMLREC_TAIL_BLOCKS=$1 MMLREC_OPT_U=$2 python3 bench.py --full --no-cpu-baseline --no-configs --no-lazy --alt-batch 0 --steps 60 --warmup 10 --no-loss-check 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels_ms_per_step']

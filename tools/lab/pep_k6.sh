@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 6: PepNet / Amazon-8 at B = 65 536: K7 fusion off / on (products in the GEMM turns) / on with gated heads (default)
 cd $GRAFT_REPO_ROOT
-run() { env $1 python3 bench.py --workload pepnet_amazon --steps 40 --warmup 8 --no-cpu-baseline --no-lazy --alt-batch 0 --no-configs --no-loss-check 2>/dev/null | python3 -c "
+run() { env $1 python3 bench.py --full --workload pepnet_amazon --steps 40 --warmup 8 --no-cpu-baseline --no-lazy --alt-batch 0 --no-configs --no-loss-check 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

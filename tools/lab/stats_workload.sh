@@ -4,5 +4,5 @@
 out=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf $out; mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-configs --alt-batch 0 --no-lazy --no-loss-check "$@" > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -- python3 bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-configs --alt-batch 0 --no-lazy --no-loss-check "$@" > $out/bench.log 2>&1
 ls $out/*/*kernel_stats.csv | head -1

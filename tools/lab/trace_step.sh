@@ -4,7 +4,7 @@
 out=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -rf $out; mkdir -p $out
-rocprofv3 --kernel-trace --output-format csv -d $out -- python3 bench.py --no-cpu-baseline --no-lazy --alt-batch 0 --steps 20 --warmup 5 "$@" > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $out -- python3 bench.py --full --no-cpu-baseline --no-lazy --alt-batch 0 --steps 20 --warmup 5 "$@" > $out/bench.log 2>&1
 python3 - $out <<'PY'
 import csv, glob, sys
 f = sorted(glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True))[-1]

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Copies the judged profile summaries from gpurun_out/ (scratch) into profiles/ (tracked).
-usage: update_profiles.py <traffic dir> <serial prof dir> [round tag]"""
+"""Copies the judged profile summaries from an evidence pass's output directory (scratch) into profiles/ (tracked).
+usage: update_profiles.py <traffic dir> <serial prof dir> [round tag] [bench output dir]
+(bench output dir: where bench_default.json and secondary.jsonl lie; default: the folder that holds <traffic dir>,
+as tools/final_pass.sh lays them out)"""
 import collections
 import csv
 import glob
@@ -37,7 +39,7 @@ if os.path.exists(log):
     lines = [l for l in open(log) if l.startswith("{")]
     if lines:
         open(os.path.join(out, f"{tag}_kernel_stats_bench_line.json"), "w").write(lines[-1])
-gout = os.path.join(root, "gpurun_out")
+gout = sys.argv[4] if len(sys.argv) > 4 else os.path.dirname(os.path.abspath(traffic))
 for src, dst in (("secondary.jsonl", f"{tag}_secondary.jsonl"), ("bench_default.json", f"{tag}_bench_line.json")):
     p = os.path.join(gout, src)
     if os.path.exists(p):
