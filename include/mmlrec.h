@@ -169,6 +169,81 @@ int mml_index_unique_idx32(const int64_t* vocab, int32_t F, int32_t E, const int
                            int32_t touched_cap, uint8_t* row_marks, int32_t* status, mml_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * K1p / K2p  multi-valued (pooled) sparse features beside the single-valued ones.
+ * Replaces, for a schema with VarLenSparseFeat columns, BaseModel.input_from_feature_columns
+ * (model/basemodel.py:461-487), varlen_embedding_lookup (model/utils.py:520-533: nn.Embedding over the maxlen id
+ * columns), get_varlen_pooling_list (model/utils.py:449-463: the mask from `ids != 0` or from the length column),
+ * SequencePoolingLayer (model/utils.py:258-326: sum / mean / max over the positions) and combined_dnn_input
+ * (model/utils.py:434-446), and their autograd backward.
+ *
+ * The descriptor names every TABLE once and every field, single-valued or pooled, names its table by index: an item
+ * id column and a history of item ids share one table, one `seen` bitmap and one mark range.  All arrays are HOST
+ * arrays; table[] holds DEVICE pointers ([vocab, E] fp32: the embedding tables for the gather, the gradient
+ * accumulators for the scatter, unused by mml_index_unique_pool).
+ * Caps: n_tables <= MML_MAX_FIELDS, n_single + n_pooled <= MML_MAX_FIELDS, n_pooled <= MML_MAX_POOLED,
+ * 1 <= p_maxlen <= MML_POOL_MAX_LEN, E in {4, 8, 16}, vocab < 2^31; 16-byte aligned tables, out and dOut with
+ * ldo % 4 == 0.  Anything else returns MML_ERR_ARG.
+ *
+ * Layout of out / dOut (the reference's dnn_input): [ single-valued blocks in array order | pooled blocks in array
+ * order | Nd dense columns ], every block E wide.
+ * Pooled field p owns the X columns [p_col0, p_col0 + p_maxlen) (ids as fp32, truncated toward zero).  Position t is
+ * VALID iff  p_len_col <  0 (mask mode):   trunc(X[b, p_col0 + t]) != 0            (id 0 is padding, anywhere)
+ *            p_len_col >= 0 (length mode): t < min(max(trunc(X[b, p_len_col]), 0), p_maxlen)   (id 0 is a row)
+ *   MML_POOL_SUM   out = sum over the valid t of row_t                   (fp32, tree order)
+ *   MML_POOL_MEAN  out = that sum / ((float)n_valid + 1e-8f)             (n_valid = 0 gives 0)
+ *   MML_POOL_MAX   out = max over ALL t of (valid_t ? row_t : row_t - 1e9f); the first (lowest t) position that
+ *                  attains it is stored per element in argmax[b * ldarg + p * E + e] (one byte; ldarg >= n_pooled * E,
+ *                  ldarg % 4 == 0; argmax may be NULL when no field uses MML_POOL_MAX)
+ * Indices are validated through `status` (bits of mml_gather_fwd) at VALID positions only; the id of a padded
+ * position is clamped into the table before it is used as an address.
+ * ---------------------------------------------------------------------------------------------- */
+#define MML_MAX_POOLED 16
+#define MML_POOL_MAX_LEN 256
+#define MML_POOL_SUM 0
+#define MML_POOL_MEAN 1
+#define MML_POOL_MAX 2
+typedef struct mml_pool_desc {
+  int32_t n_tables, E, n_single, n_pooled;
+  float* table[MML_MAX_FIELDS];
+  int64_t vocab[MML_MAX_FIELDS];
+  int32_t s_col[MML_MAX_FIELDS];   /* single-valued field f: its X column ... */
+  int32_t s_table[MML_MAX_FIELDS]; /* ... and its table index */
+  int32_t p_col0[MML_MAX_POOLED], p_maxlen[MML_MAX_POOLED], p_len_col[MML_MAX_POOLED];
+  int32_t p_combiner[MML_MAX_POOLED], p_table[MML_MAX_POOLED];
+} mml_pool_desc;
+/* K1p: ONE launch writes the whole dnn_input.  Single-valued blocks and dense columns are bit-exact copies (the
+ * contract of mml_gather_fwd).  wg_max (optional): workgroup w stores the largest |value| it wrote to wg_max[w]
+ * (contract of mml_gather_fwd_wgmax); wg_max_len must equal mml_gather_pool_wgmax_len(). */
+int64_t mml_gather_pool_wgmax_len(const mml_pool_desc* d, int32_t Nd, int64_t B);
+int mml_gather_pool_fwd(const mml_pool_desc* d, const float* X, int64_t ldX, int32_t dense_col0, int32_t Nd, int64_t B,
+                        float* out, int64_t ldo, uint8_t* argmax, int64_t ldarg, float* wg_max, int64_t wg_max_len,
+                        int32_t* status, mml_stream_t stream);
+/* K2p: ONE launch adds the table gradients of every field: a single-valued field adds dOut[b, block] to its row,
+ * a pooled field adds to the row of every VALID position  dOut (sum),  dOut / ((float)n_valid + 1e-8f) (mean),  or
+ * dOut[e] where argmax[e] == t and 0 elsewhere (max; argmax as the gather left it).  Padded positions add nothing
+ * and their row is not touched.  Duplicates (inside a sequence, across samples, across the fields of one table) are
+ * folded in LDS in 64-bit fixed point in front of the float atomics, as in mml_scatter_bwd.
+ * Bookkeeping per TABLE under the contracts of mml_scatter_bwd: seen[n_tables] bitmaps, rowbase[n_tables + 1],
+ * touched / touched_count / touched_cap, row_marks (32 * sum_t ceil(V_t / 32) bytes, table t from
+ * 32 * sum_{u<t} ceil(V_u / 32)), with or without a touched list.  A row reached through several fields is listed
+ * once.  One difference from mml_scatter_bwd: the pool entry points ALWAYS rebuild the touched list by compaction
+ * (mml_rows_compact over the tables), with or without a mark map -- *touched_count is reset and touched[] holds every
+ * row whose bit is set in `seen` afterwards, rows of earlier calls included until the caller clears the bitmaps; no
+ * form appends to an existing list.
+ * An out-of-range id at a valid position (status bit set) is read as the clamped row by the gather and counts in
+ * n_valid there; the scatter skips it and, in mask mode, does not count it: results of a batch whose status word is
+ * set are not defined beyond "no address outside the tables is touched". */
+int mml_scatter_pool_bwd(const mml_pool_desc* d, const float* X, int64_t ldX, int64_t B, const float* dOut,
+                         int64_t ldo, const uint8_t* argmax, int64_t ldarg, uint32_t* const* seen,
+                         const int64_t* rowbase, int32_t* touched, int32_t* touched_count, int32_t touched_cap,
+                         uint8_t* row_marks, int32_t* status, mml_stream_t stream);
+/* The distinct VALID rows of a batch without gradients (the counterpart of mml_index_unique, same outputs, per
+ * table): what the lazy-exact table optimizer brings up to date before the gather reads it. */
+int mml_index_unique_pool(const mml_pool_desc* d, const float* X, int64_t ldX, int64_t B, uint32_t* const* seen,
+                          const int64_t* rowbase, int32_t* touched, int32_t* touched_count, int32_t touched_cap,
+                          uint8_t* row_marks, int32_t* status, mml_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Row-wise sharded tables (replaces the reference's dead --is_parallel stub, main.py:81-83,
  * model/basemodel.py:235-238).  Row r of field f lives on rank (r + f) mod world at local row r / world; a rank keeps
  * its F shards back to back in one flat [R, E] buffer and a lookup travels as the int32 key keybase[f] + r / world.

@@ -11,6 +11,8 @@ import torch  # noqa: F401,E402
 from . import build as _build
 
 MAX_FIELDS, MAX_GROUP, MAX_SRC, MAX_EXPERTS, MAX_GATES, MAX_HEADS, MAX_OPT_TENSORS = 64, 16, 8, 16, 8, 8, 32
+MAX_POOLED, POOL_MAX_LEN = 16, 256
+POOL_COMBINERS = {"sum": 0, "mean": 1, "max": 2}
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SIGMOID2 = 0, 1, 2, 3
 OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_RMSPROP = 0, 1, 2, 3
 OPT_KINDS = {"sgd": OPT_SGD, "adam": OPT_ADAM, "adagrad": OPT_ADAGRAD, "rmsprop": OPT_RMSPROP}
@@ -25,6 +27,13 @@ class GemmFwdDesc(C.Structure):
                 ("relu_mask", fp), ("ldmask", i64), ("amax_a", fp), ("amax_w", fp), ("amax_out", fp),
                 ("w_planes", fp), ("w_kexp", fp),
                 ("mul", fp), ("prod", fp), ("ldmul", i64), ("ldprod", i64), ("amax_prod", fp)]
+
+
+class PoolDesc(C.Structure):
+    _fields_ = [("n_tables", i32), ("E", i32), ("n_single", i32), ("n_pooled", i32),
+                ("table", fp * MAX_FIELDS), ("vocab", i64 * MAX_FIELDS), ("s_col", i32 * MAX_FIELDS),
+                ("s_table", i32 * MAX_FIELDS), ("p_col0", i32 * MAX_POOLED), ("p_maxlen", i32 * MAX_POOLED),
+                ("p_len_col", i32 * MAX_POOLED), ("p_combiner", i32 * MAX_POOLED), ("p_table", i32 * MAX_POOLED)]
 
 
 class AmaxDesc(C.Structure):
@@ -252,6 +261,11 @@ _SIGS = {
     "mml_index_unique": (C.c_int, [_PP(i64), _PP(i32), i32, i32, fp, i64, i64, _PP(fp), _PP(i64), fp, fp, i32, fp, fp,
                                    fp]),
     "mml_counter_update": (C.c_int, [fp, i32, i32, fp]),
+    "mml_gather_pool_wgmax_len": (i64, [_PP(PoolDesc), i32, i64]),
+    "mml_gather_pool_fwd": (C.c_int, [_PP(PoolDesc), fp, i64, i32, i32, i64, fp, i64, fp, i64, fp, i64, fp, fp]),
+    "mml_scatter_pool_bwd": (C.c_int, [_PP(PoolDesc), fp, i64, i64, fp, i64, fp, i64, _PP(fp), _PP(i64), fp, fp, i32,
+                                       fp, fp, fp]),
+    "mml_index_unique_pool": (C.c_int, [_PP(PoolDesc), fp, i64, i64, _PP(fp), _PP(i64), fp, fp, i32, fp, fp, fp]),
 }
 EXPORTS = tuple(_SIGS)
 

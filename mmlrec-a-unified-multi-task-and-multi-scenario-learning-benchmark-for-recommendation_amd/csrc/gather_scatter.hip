@@ -8,6 +8,7 @@
 // K2 restates aten::embedding_dense_backward (sparse=False, model/basemodel.py:122): row-granular float
 // atomics into dense [V,E] accumulators, shaped as E contiguous floats per row per wave-instruction.
 #include "common.hpp"
+#include "fold_fixed.hpp"
 
 #include <stdlib.h>
 
@@ -442,24 +443,6 @@ struct ScatterPlan {
   int32_t grp_base[MML_MAX_FIELDS + 1];  // prefix sum of per-field group counts (per XCD slot)
 };
 constexpr int kDirectReps = 4;
-
-__device__ __forceinline__ long long to_fixed(float x, int emax, const int shift = 28) {
-  const unsigned u = __float_as_uint(x);
-  int e = (int)((u >> 23) & 0xffu);
-  if (e == 255) return 0;             // Inf / NaN: added to the table row directly (scatter_fold_kernel), not folded
-  unsigned m = u & 0x7fffffu;
-  if (e) m |= 0x800000u; else e = 1;  // subnormal
-  const int sh = e - emax + shift;    // <= shift: x = m * 2^(e - 150) in units of 2^(emax - 150 - shift)
-  long long v;
-  if (sh >= 0) v = (long long)m << sh;
-  else if (sh > -25) v = ((long long)m + (1ll << (-sh - 1))) >> (-sh);
-  else v = 0;
-  return (u >> 31) ? -v : v;
-}
-
-__device__ __forceinline__ float from_fixed(long long v, int emax, const int shift = 28) {
-  return (float)ldexp((double)v, emax - 150 - shift);  // int64 -> f64 is exact below 2^53 and rounds once above; one rounding to f32
-}
 
 // NT threads per workgroup: the insert is a chain of LDS round trips (claim -> list -> shuffle -> add), so the kernel
 // wants every wave slot of the CU: 2 workgroups x 1024 threads at 76 KiB of LDS each (256 threads: 98 us, 512: 89 us,

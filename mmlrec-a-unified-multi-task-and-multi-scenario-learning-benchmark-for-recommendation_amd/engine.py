@@ -1072,6 +1072,89 @@ class GatherOp(Op):
                  (plan.status.data_ptr(),), meta)]
 
 
+class PooledGatherOp(GatherOp):
+    """K1p / K2p: the gather of a schema with multi-valued (pooled) fields and its scatter backward.  `tables` holds
+    every TABLE once (the order of ParamStore.table_names, which is also the order of the touched-row bookkeeping);
+    `singles` = [(X column, table number)], `pooled` = [(first X column, maxlen, combiner, table number, length column
+    or None)] (model.utils.pooled_layout)."""
+
+    def __init__(self, tables, X, singles, pooled, dense_col0, nd, out, sparse_rows=None):
+        super().__init__(tables, X, None, dense_col0, nd, out, sparse_rows=sparse_rows)
+        self.singles, self.pooled = list(singles), list(pooled)
+        self.argmax = None
+
+    def _desc(self, plan, which):
+        d = ops.make_pool_desc([getattr(t, which) for t in self.tables], self.singles,
+                               [ops.PooledField(*pf) for pf in self.pooled])
+        plan.keep.append(d)
+        return d
+
+    def _lookups(self):
+        return len(self.singles) + sum(pf[1] for pf in self.pooled)
+
+    def fwd_calls(self, plan):
+        lib = L.load()
+        if self.out.is16 or self.mark_rows is not None:
+            raise L.MMLError("the pooled gather has no bf16-storage form and no row-marking form")
+        E, P = self.tables[0].data.shape[1], len(self.pooled)
+        d = self._desc(plan, "data")
+        if any(pf[2] == "max" for pf in self.pooled):
+            self.argmax = plan.zeros(plan.B, P * E, dtype=torch.uint8)
+        out = self.out.buf
+        # ids + rows read (every position: an upper bound of the valid ones) + blocks and dense columns written
+        meta = dict(kernel="gather_pool_kernel",
+                    bytes=float(plan.B) * (len(self.singles) * (4 + 8 * E) + 8 * self.nd +
+                                           sum(4 * pf[1] + 4 * E * pf[1] + 4 * E for pf in self.pooled)))
+        wg, nwg = None, 0
+        if plan.amax_pool is not None and os.environ.get("MMLREC_GATHER_WGMAX", "1") != "0":
+            nwg = int(lib.mml_gather_pool_wgmax_len(C.byref(d), self.nd, plan.B))
+            if nwg > 0:
+                wg = plan.zeros(1, nwg)
+                self.out.amax_src = wg
+        return [(lib.mml_gather_pool_fwd, (C.byref(d), self.X.data_ptr(), ops._ld(self.X), self.dense_col0, self.nd,
+                                           plan.B, out.data_ptr(), ops._ld(out), L.ptr(self.argmax),
+                                           0 if self.argmax is None else ops._ld(self.argmax), L.ptr(wg), nwg,
+                                           plan.status.data_ptr()), meta)]
+
+    def bwd_calls(self, plan):
+        if self.out.grad is None or not any(t.needs_grad for t in self.tables):
+            return []
+        lib = L.load()
+        E, T = self.tables[0].data.shape[1], len(self.tables)
+        d = self._desc(plan, "grad")
+        for t in self.tables:
+            _claim(t)
+        sr = self.sparse_rows
+        if sr is not None:
+            seen = ops._ptr_array(sr.seen)
+            rb = (L.i64 * (T + 1))(*sr.rowbase)
+            plan.keep += [seen, rb]
+            extra = (seen, rb, sr.touched.data_ptr(), sr.count.data_ptr(), sr.touched.numel(), sr.marks.data_ptr())
+        else:
+            extra = (None, None, None, None, 0, L.ptr(self.grad_marks))
+        meta = dict(kernel="scatter_pool_fold_kernel", tail=True,  # ids + dOut block read + row read-modify-write
+                    bytes=float(plan.B) * (len(self.singles) * (4 + 12 * E) +
+                                           sum(4 * pf[1] + 4 * E + 8 * E * pf[1] for pf in self.pooled)))
+        return [(lib.mml_scatter_pool_bwd, (C.byref(d), self.X.data_ptr(), ops._ld(self.X), plan.B,
+                                            self.out.grad.data_ptr(), ops._ld(self.out.grad), L.ptr(self.argmax),
+                                            0 if self.argmax is None else ops._ld(self.argmax)) + extra +
+                 (plan.status.data_ptr(),), meta)]
+
+    def unique_calls(self, plan, rows):
+        """The batch's distinct VALID rows per table -> `seen` bitmaps + touched list (the index pre-pass of lazy_exact)."""
+        lib = L.load()
+        T = len(self.tables)
+        d = self._desc(plan, "data")
+        ps = ops._ptr_array(rows.seen)
+        rb = (L.i64 * (T + 1))(*rows.rowbase)
+        plan.keep += [ps, rb]
+        X, nrows = self.index_view(plan)
+        return [(lib.mml_index_unique_pool, (C.byref(d), X.data_ptr(), ops._ld(X), nrows, ps, rb,
+                                             rows.touched.data_ptr(), rows.count.data_ptr(), rows.touched.numel(),
+                                             rows.marks.data_ptr(), plan.status.data_ptr()),
+                 dict(kernel="mark_pool_rows_kernel+rows_compact_kernel", bytes=float(nrows) * self._lookups() * 5))]
+
+
 def g16_layer_ok(B, K, N, training):
     """A Linear(K -> N) at batch B can run on the bf16-storage kernels (include/mmlrec.h K3': tile-aligned extents; the
     weight gradient's tiles are 128 x 128)."""
@@ -2621,7 +2704,7 @@ class Optimizer:
         if self.table_update != "dense_exact" or self._table_reg(self._reg_map()):
             return False
         gop = plan.ops[0] if plan.ops else None
-        if not isinstance(gop, GatherOp):
+        if not isinstance(gop, GatherOp) or isinstance(gop, PooledGatherOp):  # (the pooled gather marks no rows)
             return False
         return all(t.data.shape[1] <= 16 and t.data.shape[1] % 4 == 0 for t in gop.tables)
 
@@ -2836,6 +2919,8 @@ class Optimizer:
             return []
         if not isinstance(gop, GatherOp):
             raise L.MMLError("lazy_exact table updates are not available on the table-wise sharded path")
+        if isinstance(gop, PooledGatherOp):
+            return gop.pre_index_calls(plan) + gop.unique_calls(plan, rows) + [catchup]
         X, nrows = gop.index_view(plan)
         col = (L.i32 * F)(*gop.cols)
         plan.keep.append(col)

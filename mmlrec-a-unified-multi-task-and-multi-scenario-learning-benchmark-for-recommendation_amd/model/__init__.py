@@ -14,4 +14,4 @@ from .ple import PLE  # noqa: F401
 from .sharedbottom import SharedBottom  # noqa: F401
 from .snr_trans import SNR_trans  # noqa: F401
 from .star import STAR  # noqa: F401
-from .utils import DenseFeat, SparseFeat, VarLenSparseFeat, get_feature_names  # noqa: F401
+from .utils import DenseFeat, SparseFeat, VarLenSparseFeat, get_feature_names, pooled_layout  # noqa: F401

@@ -54,6 +54,7 @@ class APG(BaseModel):
         if scene_feature == "":
             raise NotImplementedError("APG needs data_config.scene_feature (the reference fails in forward without it)")
         self.scene_index = self.feature_index[scene_feature]
+        self._refuse_pooled_before(scene_feature)
         input_dim = self.compute_input_dim(dnn_feature_columns)
         dims = [input_dim] + list(self.dnn_hidden_units)
         self.apg_layers = nn.ModuleList([APGLayer(dims[i], dims[i + 1], scene_emb_dim,

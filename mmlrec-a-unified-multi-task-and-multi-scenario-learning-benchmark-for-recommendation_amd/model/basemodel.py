@@ -125,7 +125,10 @@ class BaseModel(nn.Module):
                 raise NotImplementedError("regression heads are outside the MI355X hot path (every shipped config is "
                                           "binary)")
         if any(isinstance(f, VarLenSparseFeat) for f in dnn_feature_columns):
-            raise NotImplementedError("VarLenSparseFeat is outside the MI355X hot path (never built by ctrdataset)")
+            from .utils import pooled_layout
+            pooled_layout(dnn_feature_columns)  # (one embedding_dim, known combiners, equal sizes of a shared table)
+            if any(isinstance(f, VarLenSparseFeat) for f in linear_feature_columns):
+                raise NotImplementedError("VarLenSparseFeat in the wide (linear) columns")
         l2_reg_linear = self.model_config.get("l2_reg_linear", 1e-5)
         l2_reg_embedding = self.model_config.get("l2_reg_embedding", 1e-5)
 
@@ -145,6 +148,25 @@ class BaseModel(nn.Module):
     def _sparse_cols(self):
         return [f for f in self.dnn_feature_columns if isinstance(f, SparseFeat)]
 
+    def _pooled_cols(self):
+        return [f for f in self.dnn_feature_columns if isinstance(f, VarLenSparseFeat)]
+
+    def _lookups_per_sample(self):
+        """Table rows one sample can name: the bound of the touched-row list per sample."""
+        return len(self._sparse_cols()) + sum(int(f.maxlen) for f in self._pooled_cols())
+
+    def _refuse_pooled_before(self, scene_feature):
+        """PepNet / APG take the scene embedding as sparse_embedding_list[feature_index[scene][0]] (reference
+        model/pepnet.py:97,126): the scene's X COLUMN used as a LIST position.  A pooled feature declared in front of it
+        shifts the column by maxlen and the list position by nothing, so the reference reads another feature's block."""
+        for f in self.dnn_feature_columns:
+            if f.name == scene_feature:
+                return
+            if isinstance(f, VarLenSparseFeat):
+                raise NotImplementedError(
+                    f"{type(self).__name__}: the pooled feature {f.name!r} is declared before the scene feature "
+                    f"{scene_feature!r}; declare multi-valued features after all single-valued ones")
+
     def _dense_cols(self):
         return [f for f in self.dnn_feature_columns if isinstance(f, DenseFeat)]
 
@@ -160,7 +182,7 @@ class BaseModel(nn.Module):
 
     @property
     def embedding_size(self):
-        sizes = {f.embedding_dim for f in self._sparse_cols()}
+        sizes = {f.embedding_dim for f in self._sparse_cols() + self._pooled_cols()}
         if len(sizes) > 1:
             raise ValueError("embedding_dim of SparseFeat and VarlenSparseFeat must be same in this model!")
         return list(sizes)[0]
@@ -285,11 +307,33 @@ class BaseModel(nn.Module):
                     raise NotImplementedError("dense feature columns must be contiguous in X")
                 pos += f.dimension
         par_ = getattr(self, "_parallel", None)
-        x0 = plan.val(len(sp) * E_dim + nd, needs_grad=training, name="dnn_input", pad_k=True,
-                      store16=(plan.bf16 and par_ is None and mark_rows is None and E_dim % 4 == 0 and
+        vl = self._pooled_cols()
+        if vl:
+            if par_ is not None:
+                raise NotImplementedError("multi-valued (pooled) features on sharded / replicated tables")
+            if self._scatter_mode() == "deterministic" and training:
+                raise NotImplementedError("scatter_mode='deterministic' with multi-valued (pooled) features")
+            if mark_rows is not None:
+                raise NotImplementedError("the row-marking gather of the split dense update has no pooled form")
+        # (pooled fields: dnn_input stays fp32 -- the pooled gather has no bf16-storage form)
+        x0 = plan.val((len(sp) + len(vl)) * E_dim + nd, needs_grad=training, name="dnn_input", pad_k=True,
+                      store16=(plan.bf16 and par_ is None and mark_rows is None and E_dim % 4 == 0 and not vl and
                                self._dnn_input_store16(plan)))
         if nd:
-            x0.grad_cols = len(sp) * E_dim  # the dense features' gradient has no reader (they are input data)
+            x0.grad_cols = (len(sp) + len(vl)) * E_dim  # the dense features' gradient has no reader (they are input data)
+        if vl:
+            from .utils import pooled_layout
+            lay = pooled_layout(self.dnn_feature_columns, self.feature_index)
+            ptabs = [store.pvals[f"embedding_dict.{n}.weight"] for n in lay["table_names"]]
+            if [f"embedding_dict.{n}.weight" for n in lay["table_names"]] != list(store.table_names):
+                raise L.MMLError("pooled gather: the tables of the layout are not the store's tables")
+            gop = E.PooledGatherOp(ptabs, plan.X, lay["singles"], lay["pooled"], dense_col0, nd, x0,
+                                   sparse_rows=sparse_rows)
+            if grad_marks and training and sparse_rows is None:
+                gop.grad_marks = store.ensure_grad_marks(ptabs)[0]
+            plan.add(gop)
+            plan.layer_outputs["dnn_input"] = x0
+            return self._finish_record(plan, store, x0)
         tables = [store.pvals[f"embedding_dict.{f.embedding_name}.weight"] for f in sp]
         cols = [self.feature_index[f.name][0] for f in sp]
         par = getattr(self, "_parallel", None)
@@ -327,6 +371,9 @@ class BaseModel(nn.Module):
             self._maybe_deterministic(gop, store, tables, training, E_dim)
             plan.add(gop)
         plan.layer_outputs["dnn_input"] = x0
+        return self._finish_record(plan, store, x0)
+
+    def _finish_record(self, plan, store, x0):
         head = self._build_graph(plan, store, x0)
         head.mask_cols = self._head_mask_cols()
         plan.finish(head)

@@ -61,6 +61,7 @@ class PepNet(BaseModel):
         if scene_feature == "":
             raise NotImplementedError("PepNet needs data_config.scene_feature")
         self.scene_index = self.feature_index[scene_feature]
+        self._refuse_pooled_before(scene_feature)
         task_dim = scene_emb_dim
         input_dim = self.compute_input_dim(dnn_feature_columns)
         self.feature_gate = GateNN(input_dim=input_dim + scene_emb_dim, hidden_dim=128, output_dim=input_dim,

@@ -36,8 +36,10 @@ class SparseFeat(namedtuple("SparseFeat", ["name", "vocabulary_size", "embedding
 
 
 class VarLenSparseFeat(namedtuple("VarLenSparseFeat", ["sparsefeat", "maxlen", "combiner", "length_name"])):
-    """Accepted for API compatibility; the hot path never builds one (utils/data_utils.py:73-75), and the
-    step plans reject it."""
+    """A multi-valued categorical feature: `maxlen` id columns of X pooled into one embedding_dim-wide block ("sum",
+    "mean" or "max" over the valid positions: ids != 0, or the first X[:, length_name] positions).  The pooled-row
+    kernels (include/mmlrec.h K1p / K2p) take it through pooled_layout(): in a model's step plan as
+    engine.PooledGatherOp, outside a model as functional.pooled_dnn_input."""
     __slots__ = ()
 
     def __new__(cls, sparsefeat, maxlen, combiner="mean", length_name=None):
@@ -84,6 +86,57 @@ def build_input_features(feature_columns):
             features[feat.length_name] = (start, start + 1)
             start += 1
     return features
+
+
+def pooled_layout(feature_columns, feature_index=None):
+    """How the reference lays a schema with multi-valued features out, as the pooled-row kernels take it.
+
+    dnn_input (reference model/basemodel.py:461-487, model/utils.py:434-446) is [ every SparseFeat in declaration order |
+    every VarLenSparseFeat in declaration order | dense columns ]: the pooled blocks come after ALL single-valued ones,
+    wherever they were declared.  Features that name one embedding_name share ONE table (create_embedding_matrix).
+    Returns a dict: table_names (distinct embedding names, single-valued features' first), vocab, E, singles
+    [(X column, table number)], pooled [(first X column, maxlen, combiner, table number, length column or None)],
+    dense_col0, nd, offsets {feature name: (first, one-past-last column of dnn_input)}, width."""
+    if feature_index is None:
+        feature_index = build_input_features(feature_columns)
+    sp = [f for f in feature_columns if isinstance(f, SparseFeat)]
+    vl = [f for f in feature_columns if isinstance(f, VarLenSparseFeat)]
+    de = [f for f in feature_columns if isinstance(f, DenseFeat)]
+    if not sp and not vl:
+        raise ValueError("pooled_layout: no sparse feature column")
+    dims = {f.embedding_dim for f in sp + vl}
+    if len(dims) != 1:
+        raise ValueError("embedding_dim of SparseFeat and VarlenSparseFeat must be same in this model!")
+    E = dims.pop()
+    names, vocab = [], []
+    for f in sp + vl:
+        if f.embedding_name not in names:
+            names.append(f.embedding_name)
+            vocab.append(int(f.vocabulary_size))
+        elif vocab[names.index(f.embedding_name)] != int(f.vocabulary_size):
+            # (the reference builds the table from whichever feature comes last and indexes out of range)
+            raise ValueError(f"features sharing the table {f.embedding_name!r} must have one vocabulary_size")
+    for f in vl:
+        if f.combiner not in ("sum", "mean", "max"):
+            raise ValueError("parameter mode should in [sum, mean, max]")
+    singles = [(feature_index[f.name][0], names.index(f.embedding_name)) for f in sp]
+    pooled = [(feature_index[f.name][0], int(f.maxlen), f.combiner, names.index(f.embedding_name),
+               None if f.length_name is None else feature_index[f.length_name][0]) for f in vl]
+    offsets, pos = OrderedDict(), 0
+    for f in sp + vl:
+        offsets[f.name] = (pos, pos + E)
+        pos += E
+    nd = sum(f.dimension for f in de)
+    dense_col0 = feature_index[de[0].name][0] if de else 0
+    run = dense_col0
+    for f in de:  # the gather copies ONE contiguous run of dense columns
+        if feature_index[f.name][0] != run:
+            raise NotImplementedError("dense feature columns must be contiguous in X")
+        offsets[f.name] = (pos, pos + f.dimension)
+        pos += f.dimension
+        run += f.dimension
+    return dict(table_names=names, vocab=vocab, E=E, singles=singles, pooled=pooled, dense_col0=dense_col0, nd=nd,
+                offsets=offsets, width=pos)
 
 
 def get_feature_names(feature_columns):

@@ -196,6 +196,101 @@ def gather_fwd_idx32(tables, idx, dense=None, out=None, status=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- K1p / K2p
+class PooledField:
+    """A multi-valued sparse feature as the kernels see it: `maxlen` id columns of X from `col0`, pooled by `combiner`
+    ("sum" / "mean" / "max") over the valid positions -- ids != 0 (len_col None: mask mode) or the first X[:, len_col]
+    positions (length mode) -- with the rows of table number `table`."""
+    __slots__ = ("col0", "maxlen", "combiner", "table", "len_col")
+
+    def __init__(self, col0, maxlen, combiner, table, len_col=None):
+        if combiner not in L.POOL_COMBINERS:
+            raise ValueError(f"combiner {combiner!r}: expected one of {sorted(L.POOL_COMBINERS)}")
+        self.col0, self.maxlen, self.combiner, self.table = int(col0), int(maxlen), combiner, int(table)
+        self.len_col = None if len_col is None else int(len_col)
+
+
+def make_pool_desc(tables, singles, pooled, vocab=None):
+    """mml_pool_desc (include/mmlrec.h): `tables` = the distinct [V, E] tensors (or None with `vocab` = (sizes, E) for
+    the index-only pass), `singles` = [(X column, table number)], `pooled` = [PooledField]."""
+    d = L.PoolDesc()
+    if tables is not None:
+        _need_gpu(*tables)
+        sizes, E = [t.shape[0] for t in tables], tables[0].shape[1]
+        for t in tables:
+            if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != E or not t.is_contiguous():
+                raise L.MMLError("pooled rows: every table must be a contiguous float32 [V, E] tensor of one width E")
+    else:
+        sizes, E = vocab
+    if len(sizes) > L.MAX_FIELDS or len(pooled) > L.MAX_POOLED or len(singles) + len(pooled) > L.MAX_FIELDS:
+        raise L.MMLError(f"pooled rows: at most {L.MAX_FIELDS} tables, {L.MAX_POOLED} pooled fields and "
+                         f"{L.MAX_FIELDS} fields in all per launch")
+    d.n_tables, d.E, d.n_single, d.n_pooled = len(sizes), int(E), len(singles), len(pooled)
+    for i, v in enumerate(sizes):
+        d.vocab[i] = int(v)
+        d.table[i] = tables[i].data_ptr() if tables is not None else None
+    for i, (c, t) in enumerate(singles):
+        d.s_col[i], d.s_table[i] = int(c), int(t)
+    for i, pf in enumerate(pooled):
+        d.p_col0[i], d.p_maxlen[i], d.p_table[i] = pf.col0, pf.maxlen, pf.table
+        d.p_len_col[i] = -1 if pf.len_col is None else pf.len_col
+        d.p_combiner[i] = L.POOL_COMBINERS[pf.combiner]
+    return d
+
+
+def gather_pool_fwd(tables, X, singles, pooled, dense_col0=0, nd=0, out=None, argmax=None, wgmax=False, status=None):
+    """dnn_input = [single-valued blocks | pooled blocks | dense columns] in ONE launch (mml_gather_pool_fwd).
+    Returns (out, argmax, wg_max): argmax = uint8 [B, P * E] when a field pools by max (else None), wg_max = the
+    per-workgroup maxima of |out| when wgmax is set (else None)."""
+    lib = L.load()
+    _need_gpu(X)
+    X = _f32_2d(X, "X")
+    d = make_pool_desc(tables, singles, pooled)
+    B, E, P = X.shape[0], d.E, len(pooled)
+    if out is None:  # rows padded to whole 16-byte pieces (the kernel stores float4s: ldo % 4 == 0)
+        K0 = (len(singles) + P) * E + nd
+        out = torch.empty((B, (K0 + 3) // 4 * 4), dtype=torch.float32, device=X.device)[:, :K0]
+    if argmax is None and any(pf.combiner == "max" for pf in pooled):
+        argmax = torch.zeros((B, P * E), dtype=torch.uint8, device=X.device)
+    wg, n = None, 0
+    if wgmax:
+        n = int(lib.mml_gather_pool_wgmax_len(C.byref(d), nd, B))
+        wg = torch.full((1, max(n, 1)), float("nan"), dtype=torch.float32, device=X.device)
+    rc = lib.mml_gather_pool_fwd(C.byref(d), X.data_ptr(), _ld(X), dense_col0, nd, B, out.data_ptr(), _ld(out),
+                                 L.ptr(argmax), 0 if argmax is None else _ld(argmax), L.ptr(wg), n, L.ptr(status),
+                                 _stream())
+    L.check(rc, "mml_gather_pool_fwd")
+    return out, argmax, wg
+
+
+def scatter_pool_bwd(grad_tables, X, singles, pooled, d_out, argmax=None, seen=None, rowbase=None, touched=None,
+                     touched_count=None, status=None, marks=None):
+    """Table gradients of every field, single-valued and pooled, in ONE launch (mml_scatter_pool_bwd); seen / rowbase /
+    marks are per TABLE (marks: marks_bytes of the tables' sizes)."""
+    lib = L.load()
+    _need_gpu(X, d_out)
+    d = make_pool_desc(grad_tables, singles, pooled)
+    T = len(grad_tables)
+    rc = lib.mml_scatter_pool_bwd(C.byref(d), X.data_ptr(), _ld(X), X.shape[0], d_out.data_ptr(), _ld(d_out),
+                                  L.ptr(argmax), 0 if argmax is None else _ld(argmax),
+                                  _ptr_array(seen) if seen is not None else None,
+                                  (L.i64 * (T + 1))(*rowbase) if rowbase is not None else None, L.ptr(touched),
+                                  L.ptr(touched_count), 0 if touched is None else touched.numel(), L.ptr(marks),
+                                  L.ptr(status), _stream())
+    L.check(rc, "mml_scatter_pool_bwd")
+
+
+def index_unique_pool(vocab, E, X, singles, pooled, seen, rowbase, touched, touched_count, status=None, marks=None):
+    """The distinct VALID rows of a batch per table, without gradients (mml_index_unique_pool)."""
+    _need_gpu(X, touched, touched_count)
+    d = make_pool_desc(None, singles, pooled, vocab=(list(vocab), E))
+    T = len(vocab)
+    rc = L.load().mml_index_unique_pool(C.byref(d), X.data_ptr(), _ld(X), X.shape[0], _ptr_array(seen),
+                                        (L.i64 * (T + 1))(*rowbase), touched.data_ptr(), touched_count.data_ptr(),
+                                        touched.numel(), L.ptr(marks), L.ptr(status), _stream())
+    L.check(rc, "mml_index_unique_pool")
+
+
 def marks_bytes(vocab):
     """Size of the row-mark scratch map of mml_scatter_bwd / mml_index_unique (include/mmlrec.h: row_marks)."""
     return 32 * sum((int(v) + 31) // 32 for v in vocab)

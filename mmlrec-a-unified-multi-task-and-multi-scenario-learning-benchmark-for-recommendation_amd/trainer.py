@@ -182,11 +182,12 @@ class TrainStep:
         # (split_dense="force").
         split = (split_dense == "force" and self.opt.table_update == "dense_exact" and
                  (par is None or par.mode == "replicated") and
+                 not model._pooled_cols() and  # (the pooled gather marks no rows: the single-launch schedule)
                  not self.opt._table_reg(self.opt._reg_map()) and model.embedding_size <= 16 and
                  model.embedding_size % 4 == 0)
         if self.opt.table_update in ("sparse_rows", "lazy_exact") or split:
             if par is None:
-                rows = self.store.ensure_rows(int(B) * max(len(model._sparse_cols()), 1))
+                rows = self.store.ensure_rows(int(B) * max(model._lookups_per_sample(), 1))
             elif par.mode == "row_sharded":  # one flat table: at most every local row is touched
                 rows = self.store.ensure_rows(par.sharding.R)
             elif par.mode == "replicated":
