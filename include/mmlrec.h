@@ -592,7 +592,28 @@ int mml_gate_mix_bwd_phase(const mml_gate_group* grp, void* workspace, int64_t w
  * model/utils.py:242-248), the optional domain-mask product (model/mmoe.py:101-106) and
  * sum_t F.binary_cross_entropy(reduction='sum') (model/basemodel.py:294-296) with its backward.
  * Forward-only (predict): y == NULL.
+ *
+ * Head kinds (mml_head_desc.kind, mml_tower_head_desc.kind): what a head predicts and what it is trained against.
+ * Low byte = output form (PredictionLayer("binary") / ("regression"), model/utils.py:242-248), second byte = the loss
+ * term when labels are given (model/basemodel.py:595-603: F.binary_cross_entropy / F.mse_loss / F.l1_loss, each with
+ * reduction='sum').  kind == 0 is the sigmoid head with BCE.  For logit z, mask value m, label y:
+ *     p  = sigmoid(z)              (MML_HEAD_OUT_SIGMOID)      |  p = z               (MML_HEAD_OUT_IDENTITY)
+ *     pm = p m  (stored in prob)
+ *     dz = d(pm) m p (1 - p)                                   |  dz = d(pm) m
+ *     BCE: loss = -(y log pm + (1 - y) log(1 - pm)), logs clamped at -100; d(pm) = (pm - y) / max(pm (1 - pm), 1e-12)
+ *     MSE: loss = (pm - y)^2,  d(pm) = 2 (pm - y)
+ *     MAE: loss = |pm - y|,    d(pm) = sign(pm - y) with sign(0) = 0
+ * With y == NULL (forward only, or dprob given) only the output form matters.  Identity output with BCE under labels is
+ * MML_ERR_UNSUPPORTED.  Kinds mix freely inside one group; a group of kind-0 heads runs the kernels it always ran.
  * ---------------------------------------------------------------------------------------------- */
+#define MML_HEAD_OUT_SIGMOID 0
+#define MML_HEAD_OUT_IDENTITY 1
+#define MML_HEAD_LOSS_BCE 0
+#define MML_HEAD_LOSS_MSE 1
+#define MML_HEAD_LOSS_MAE 2
+#define MML_HEAD_KIND(out, loss) ((int32_t)(((loss) << 8) | (out)))
+#define MML_HEAD_KIND_OUT(kind) ((kind) & 0xff)
+#define MML_HEAD_KIND_LOSS(kind) (((kind) >> 8) & 0xff)
 typedef struct {
   const float* Hin;  /* [B, H] tower output (or the stream itself when tower_dnn_hidden_units == []) */
   const float* w;    /* [H] final-layer weight ([1,H] row, or STAR's [H,1] column: same memory)       */
@@ -617,19 +638,19 @@ typedef struct {
   float* dgate;      /* [B, H] backward (required when gate != NULL and the group trains)              */
   int64_t ldgate, lddgate;
   int32_t gate_act;
-  int32_t pad_;
+  int32_t kind;      /* MML_HEAD_KIND(output form, loss); 0 = sigmoid + BCE                              */
 } mml_head_desc;
 typedef struct {
   int32_t n_heads;
   int32_t dh_bf16;    /* bf16-storage path (K3'): 1 = every head's dH is a bf16 [B, H] buffer (lddh in bf16 elements); fast kernel only */
   int64_t B;
-  float* prob;        /* [B, ldprob] probabilities, head t in column t                                 */
+  float* prob;        /* [B, ldprob] predictions (probabilities, or raw values of identity heads), head t in column t */
   int64_t ldprob;
   const float* y;     /* [B, ldy] labels or NULL (forward only)                                        */
   int64_t ldy;
   const float* mask;  /* [B, ldmask] domain mask or NULL                                               */
   int64_t ldmask;
-  float* loss;        /* [1] device scalar: sum of BCE over heads and samples (overwritten), or NULL   */
+  float* loss;        /* [1] device scalar: sum of the heads' loss terms over samples (overwritten), or NULL */
   const float* dprob; /* [B, lddprob] upstream dL/dprob used INSTEAD of the BCE gradient when y == NULL (autograd path) */
   int64_t lddprob;
   mml_head_desc head[MML_MAX_HEADS];
@@ -638,8 +659,8 @@ typedef struct {
 } mml_head_group;
 int64_t mml_head_workspace_bytes(const mml_head_group* grp);
 int mml_head_fwd(const mml_head_group* grp, mml_stream_t stream);
-/* forward + loss + backward of the heads in one pass (training).  With y != NULL the loss is the summed BCE;
- * with y == NULL and dprob != NULL the heads are differentiated against the given upstream gradient. */
+/* forward + loss + backward of the heads in one pass (training).  With y != NULL the loss is the sum of every head's
+ * term (BCE, or what its kind names); with y == NULL and dprob != NULL the heads are differentiated against the given upstream gradient. */
 int mml_head_bce_fwd_bwd(const mml_head_group* grp, void* workspace, int64_t workspace_bytes, mml_stream_t stream);
 /* The same in two launches: phase 1 = the row kernel (probabilities, dH), phase 2 = the reduction of the per-workgroup
  * partial sums into dw / dbias / loss (phase 0 = both); see mml_gate_mix_bwd_phase. */
@@ -671,7 +692,8 @@ int mml_rows_reduce_batch(const mml_rows_reduce_item* items, int32_t n, mml_stre
  * (overwritten), and the head's dw / dhbias and the loss through per-workgroup partial sums (phase 2: fixed order).
  * Arithmetic: the two-plane fp16 products of the GEMM family (the tower weight's pre-cut planes in BOTH layouts,
  * mml_gemm_planes_cut; the input's magnitude slot; dH is scaled per 32-row block by its own largest magnitude), the head
- * kernel's expressions for probability, clamped-log BCE and its derivative.  Training only (y required).
+ * kernel's expressions for probability, clamped-log BCE and its derivative -- or, per task, those of its `kind` (see K5:
+ * identity output, squared / absolute error; tasks of different kinds share the launch).  Training only (y required).
  * Served shapes: mml_tower_head_serves (all tasks of one (N, K) in {(64, 128), (64, 64)}, 16-byte aligned rows).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
@@ -697,7 +719,7 @@ typedef struct {
   int32_t K, N, n_hbias2;
   int32_t mask_col;             /* column of `mask` multiplied into the probability, or -1                */
   int32_t head;                 /* column of prob / y this task uses                                      */
-  int32_t pad_;
+  int32_t kind;                 /* MML_HEAD_KIND(output form, loss) as in mml_head_desc; 0 = sigmoid + BCE */
 } mml_tower_head_desc;
 typedef struct {
   int32_t n;                    /* tasks                                                                  */

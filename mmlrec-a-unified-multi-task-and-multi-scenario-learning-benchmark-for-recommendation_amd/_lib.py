@@ -14,6 +14,15 @@ MAX_FIELDS, MAX_GROUP, MAX_SRC, MAX_EXPERTS, MAX_GATES, MAX_HEADS, MAX_OPT_TENSO
 MAX_POOLED, POOL_MAX_LEN = 16, 256
 POOL_COMBINERS = {"sum": 0, "mean": 1, "max": 2}
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SIGMOID2 = 0, 1, 2, 3
+# head kinds (include/mmlrec.h, K5): low byte = output form, second byte = loss under labels
+HEAD_OUT_SIGMOID, HEAD_OUT_IDENTITY = 0, 1
+HEAD_LOSS_BCE, HEAD_LOSS_MSE, HEAD_LOSS_MAE = 0, 1, 2
+
+
+def head_kind(out=HEAD_OUT_SIGMOID, loss=HEAD_LOSS_BCE):
+    return (int(loss) << 8) | int(out)
+
+
 OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_RMSPROP = 0, 1, 2, 3
 OPT_KINDS = {"sgd": OPT_SGD, "adam": OPT_ADAM, "adagrad": OPT_ADAGRAD, "rmsprop": OPT_RMSPROP}
 
@@ -109,7 +118,7 @@ class HeadDesc(C.Structure):
     _fields_ = [("Hin", fp), ("w", fp), ("w2", fp), ("bias", fp), ("bias2", fp), ("dH", fp), ("dw", fp),
                 ("dbias", fp), ("ldh", i64), ("lddh", i64), ("H", i32), ("h_relu", i32), ("n_bias2", i32),
                 ("mask_col", i32), ("gate", fp), ("dgate", fp), ("ldgate", i64), ("lddgate", i64),
-                ("gate_act", i32), ("pad_", i32)]
+                ("gate_act", i32), ("kind", i32)]
 
 
 class HeadGroup(C.Structure):
@@ -123,7 +132,7 @@ class TowerHeadDesc(C.Structure):
                 ("ldpb", i64), ("kexp_fwd", fp), ("kexp_bwd", fp), ("bias1", fp), ("w", fp), ("hbias", fp),
                 ("hbias2", fp), ("dH", fp), ("dA", fp), ("lddh", i64), ("ldda", i64), ("dw", fp), ("dhbias", fp),
                 ("amax_dH", fp), ("amax_dA", fp), ("K", i32), ("N", i32), ("n_hbias2", i32), ("mask_col", i32),
-                ("head", i32), ("pad_", i32)]
+                ("head", i32), ("kind", i32)]
 
 
 class TowerHeadGroup(C.Structure):

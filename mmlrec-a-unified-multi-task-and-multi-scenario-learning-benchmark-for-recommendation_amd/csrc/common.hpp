@@ -70,7 +70,40 @@ namespace mml {
 // torch.clamp(x, min = -100) of F.binary_cross_entropy's log terms: a NaN stays a NaN (fmaxf alone returns the other
 // operand, and a diverged model would keep reporting a finite loss)
 __device__ __forceinline__ float bce_log_clamp(float x) { return x != x ? x : fmaxf(x, -100.f); }
+// The per-sample chain of a prediction head of any kind (include/mmlrec.h, K5: MML_HEAD_KIND): used by the instantiations
+// of the three head kernels that serve groups with a non-zero kind; the all-binary instantiations keep their own text.
+__device__ __forceinline__ float head_kind_out(int kind, float z) {
+  return MML_HEAD_KIND_OUT(kind) == MML_HEAD_OUT_IDENTITY ? z : 1.f / (1.f + expf(-z));
+}
+// loss term of one sample and its derivative against the stored (masked) prediction
+__device__ __forceinline__ void head_kind_loss(int kind, float pm, float y, float& loss, float& dpm) {
+  const int lk = MML_HEAD_KIND_LOSS(kind);
+  if (lk == MML_HEAD_LOSS_MSE) {
+    const float e = pm - y;
+    loss = e * e;
+    dpm = 2.f * e;
+  } else if (lk == MML_HEAD_LOSS_MAE) {
+    const float e = pm - y;
+    loss = fabsf(e);
+    dpm = e > 0.f ? 1.f : (e < 0.f ? -1.f : e);  // (sign(0) = 0 as F.l1_loss differentiates it; a NaN stays a NaN)
+  } else {
+    const float lp = bce_log_clamp(logf(pm));
+    const float l1p = bce_log_clamp(log1pf(-pm));
+    loss = -(y * lp + (1.f - y) * l1p);
+    dpm = (pm - y) / fmaxf((1.f - pm) * pm, 1e-12f);
+  }
+}
+__device__ __forceinline__ float head_kind_dz(int kind, float dpm, float m, float p) {
+  return MML_HEAD_KIND_OUT(kind) == MML_HEAD_OUT_IDENTITY ? dpm * m : dpm * m * p * (1.f - p);
+}
 #endif
+// host: 0 when every kind of the list is one the kernels implement under (labels ? its loss : any loss)
+inline int head_kind_check(int kind, bool labels) {
+  const int o = MML_HEAD_KIND_OUT(kind), l = MML_HEAD_KIND_LOSS(kind);
+  if ((kind >> 16) != 0 || o > MML_HEAD_OUT_IDENTITY || l > MML_HEAD_LOSS_MAE) return 1;  // not a kind
+  if (labels && o == MML_HEAD_OUT_IDENTITY && l == MML_HEAD_LOSS_BCE) return 2;           // BCE of a raw value
+  return 0;
+}
 }  // namespace mml
 
 // hipGetLastError() is sticky per host thread: an error left behind by an unrelated earlier HIP call (e.g. a device

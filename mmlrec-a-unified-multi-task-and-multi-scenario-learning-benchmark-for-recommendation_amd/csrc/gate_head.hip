@@ -188,6 +188,8 @@ struct HeadAux {
   int32_t pad_;
 };
 
+// KINDS: some head of the group has a non-zero kind (include/mmlrec.h K5); chosen on the host, uniform per head
+template <bool KINDS>
 __global__ __launch_bounds__(ROW_BLOCK) void head_kernel(const mml_head_group g, const HeadAux aux) {
   __shared__ float red[ROW_WAVES][MML_MAX_HEADS * (HEAD_SLOTS * 64 + 1) + 1];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -225,7 +227,8 @@ __global__ __launch_bounds__(ROW_BLOCK) void head_kernel(const mml_head_group g,
       }
       float logit = wave_sum(part) + d.bias[0];
       for (int i = 0; i < d.n_bias2; ++i) logit += d.bias2[i];
-      const float p = 1.f / (1.f + expf(-logit));
+      const int kind = KINDS ? d.kind : 0;
+      const float p = KINDS ? head_kind_out(kind, logit) : 1.f / (1.f + expf(-logit));
       const float m = (d.mask_col >= 0 && g.mask) ? g.mask[b * g.ldmask + d.mask_col] : 1.f;
       const float pm = p * m;
       if (lane == 0) g.prob[b * g.ldprob + t] = pm;
@@ -233,15 +236,21 @@ __global__ __launch_bounds__(ROW_BLOCK) void head_kernel(const mml_head_group g,
         float dpm;
         if (g.y) {
           const float y = g.y[b * g.ldy + t];
-          // F.binary_cross_entropy: log terms clamped at -100; backward divides by max(p(1-p), 1e-12)
-          const float lp = bce_log_clamp(logf(pm));
-          const float l1p = bce_log_clamp(log1pf(-pm));
-          if (lane == 0) lossacc += -(y * lp + (1.f - y) * l1p);
-          dpm = (pm - y) / fmaxf((1.f - pm) * pm, 1e-12f);
+          if constexpr (KINDS) {
+            float l;
+            head_kind_loss(kind, pm, y, l, dpm);
+            if (lane == 0) lossacc += l;
+          } else {
+            // F.binary_cross_entropy: log terms clamped at -100; backward divides by max(p(1-p), 1e-12)
+            const float lp = bce_log_clamp(logf(pm));
+            const float l1p = bce_log_clamp(log1pf(-pm));
+            if (lane == 0) lossacc += -(y * lp + (1.f - y) * l1p);
+            dpm = (pm - y) / fmaxf((1.f - pm) * pm, 1e-12f);
+          }
         } else {
           dpm = g.dprob[b * g.lddprob + t];
         }
-        const float dlogit = dpm * m * p * (1.f - p);
+        const float dlogit = KINDS ? head_kind_dz(kind, dpm, m, p) : dpm * m * p * (1.f - p);
         if (lane == 0) dbacc[t] += dlogit;
 #pragma unroll
         for (int s = 0; s < HEAD_SLOTS; ++s) {
@@ -428,6 +437,12 @@ static bool head_group_gated(const mml_head_group* g) {
   return false;
 }
 
+static bool head_group_kinds(const mml_head_group* g) {
+  for (int t = 0; t < g->n_heads; ++t)
+    if (g->head[t].kind) return true;
+  return false;
+}
+
 static int check_head_group(const mml_head_group* g, bool train, const char* who, int& hmax) {
   MML_REQUIRE(g, "%s: null group", who);
   MML_REQUIRE(g->n_heads >= 1 && g->n_heads <= MML_MAX_HEADS && g->B >= 0, "%s: n_heads=%d", who, g->n_heads);
@@ -447,6 +462,13 @@ static int check_head_group(const mml_head_group* g, bool train, const char* who
     MML_REQUIRE(!d.gate || d.gate_act == MML_ACT_NONE || d.gate_act == MML_ACT_SIGMOID || d.gate_act == MML_ACT_SIGMOID2,
                 "%s: gated head %d: gate_act must be none, sigmoid or 2 sigmoid", who, t);
     if (d.H > hmax) hmax = d.H;
+    const int kc = head_kind_check(d.kind, train && g->y);
+    MML_REQUIRE(kc != 1, "%s: head %d: kind 0x%x is not MML_HEAD_KIND(output form, loss)", who, t, d.kind);
+    if (kc == 2) {
+      set_error("%s: head %d: identity output with binary cross-entropy (the loss of a raw value is squared or absolute error)",
+                who, t);
+      return MML_ERR_UNSUPPORTED;
+    }
   }
   return MML_OK;
 }
@@ -474,7 +496,8 @@ extern "C" int mml_head_fwd(const mml_head_group* grp, mml_stream_t stream) {
   }
   HeadAux aux{};
   aux.hmax = hmax;
-  MML_LAUNCH(head_kernel, dim3(row_grid(grp->B)), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
+  if (head_group_kinds(grp)) MML_LAUNCH(head_kernel<true>, dim3(row_grid(grp->B)), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
+  else MML_LAUNCH(head_kernel<false>, dim3(row_grid(grp->B)), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
   return check_launch("mml_head_fwd");
 }
 
@@ -511,7 +534,8 @@ extern "C" int mml_head_bce_fwd_bwd_phase(const mml_head_group* grp, void* works
         set_error("mml_head_bce_fwd_bwd: dh_bf16 / gated heads on a shape the fast row kernel does not serve");
         return MML_ERR_UNSUPPORTED;
       }
-      MML_LAUNCH(head_kernel, dim3(grid), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
+      if (head_group_kinds(grp)) MML_LAUNCH(head_kernel<true>, dim3(grid), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
+      else MML_LAUNCH(head_kernel<false>, dim3(grid), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
       rc = check_launch("mml_head_bce_fwd_bwd");
     }
     if (rc) return rc;

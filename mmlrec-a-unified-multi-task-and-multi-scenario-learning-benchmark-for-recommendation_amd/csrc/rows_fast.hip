@@ -797,7 +797,9 @@ __global__ __launch_bounds__(FB) void gate_bwd_fast_kernel(const mml_gate_group 
 #ifndef MML_HEAD_U
 #define MML_HEAD_U (NT <= 2 ? 4 : ((NT <= 4 && !GATED) ? 4 : 2))
 #endif
-template <int LPS, int NT, bool GATED>
+// KINDS: some head of the group has a non-zero kind (identity output, squared / absolute error: include/mmlrec.h K5).  The
+// host picks the instantiation (head_fast_config), so the all-binary one carries no branch on it.
+template <int LPS, int NT, bool GATED, bool KINDS>
 __global__ __launch_bounds__(FB) void head_fast_kernel(const mml_head_group g, const HeadFastAux aux) {
   __shared__ float red[FW][NT * (4 * LPS + 1) + 1];
   constexpr int SPW = 64 / LPS;
@@ -892,21 +894,30 @@ __global__ __launch_bounds__(FB) void head_fast_kernel(const mml_head_group g, c
           bj = bb[u];
         }
     const bool own = vj && sub < NI;
-    const float pj = 1.f / (1.f + expf(-lgj));
+    // (KINDS: the lane's head is tj -- its kind from the packed bits, not from the descriptor array)
+    const int kj = KINDS ? MML_HEAD_KIND((aux.out_bits >> tj) & 1u, (aux.loss_bits >> (2 * tj)) & 3u) : 0;
+    const float pj = KINDS ? head_kind_out(kj, lgj) : 1.f / (1.f + expf(-lgj));
     const float pmj = pj * mj;
     if (own) g.prob[bj * g.ldprob + tj] = pmj;
     float dlj = 0.f;
     if (aux.train) {
       float dpm;
       if (g.y) {
-        const float lp = bce_log_clamp(logf(pmj));
-        const float l1p = bce_log_clamp(log1pf(-pmj));
-        if (own) lossacc += -(yj * lp + (1.f - yj) * l1p);
-        dpm = (pmj - yj) / fmaxf((1.f - pmj) * pmj, 1e-12f);
+        if constexpr (KINDS) {
+          float lj;
+          head_kind_loss(kj, pmj, yj, lj, dpm);
+          if (own) lossacc += lj;
+        } else {
+          const float lp = bce_log_clamp(logf(pmj));
+          const float l1p = bce_log_clamp(log1pf(-pmj));
+          if (own) lossacc += -(yj * lp + (1.f - yj) * l1p);
+          dpm = (pmj - yj) / fmaxf((1.f - pmj) * pmj, 1e-12f);
+        }
       } else {
         dpm = yj;
       }
-      dlj = vj ? dpm * mj * pj * (1.f - pj) : 0.f;
+      if constexpr (KINDS) dlj = vj ? head_kind_dz(kj, dpm, mj, pj) : 0.f;
+      else dlj = vj ? dpm * mj * pj * (1.f - pj) : 0.f;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         if (it0 + u >= iters) break;
@@ -1204,6 +1215,9 @@ int head_fast_config(const mml_head_group* g, bool train, int hmax, HeadFastAux&
     if (train && !ok4(d.dH, d.lddh)) return 0;
     if (d.gate && (!ok4(d.gate, d.ldgate) || (train && !ok4(d.dgate, d.lddgate)) || g->dh_bf16)) return 0;
     if (d.gate) aux.gated = 1;
+    if (d.kind) aux.kinds = 1;
+    aux.out_bits |= (uint32_t)(MML_HEAD_KIND_OUT(d.kind) & 1) << t;
+    aux.loss_bits |= (uint32_t)(MML_HEAD_KIND_LOSS(d.kind) & 3) << (2 * t);
   }
   aux.lps = pick_lps(hmax);
   aux.nt = g->n_heads <= 2 ? 2 : (g->n_heads <= 4 ? 4 : 8);
@@ -1220,18 +1234,24 @@ int head_fast_config(const mml_head_group* g, bool train, int hmax, HeadFastAux&
   return aux.lps;
 }
 
-template <int LPS>
-static void launch_head(const mml_head_group& g, const HeadFastAux& aux, hipStream_t st) {
+template <int LPS, bool KINDS>
+static void launch_head_k(const mml_head_group& g, const HeadFastAux& aux, hipStream_t st) {
   dim3 gr(aux.grid), bl(FB);
   if (aux.gated) {
-    if (aux.nt == 2) MML_LAUNCH((head_fast_kernel<LPS, 2, true>), gr, bl, 0, st, g, aux);
-    else if (aux.nt == 4) MML_LAUNCH((head_fast_kernel<LPS, 4, true>), gr, bl, 0, st, g, aux);
-    else MML_LAUNCH((head_fast_kernel<LPS, 8, true>), gr, bl, 0, st, g, aux);
+    if (aux.nt == 2) MML_LAUNCH((head_fast_kernel<LPS, 2, true, KINDS>), gr, bl, 0, st, g, aux);
+    else if (aux.nt == 4) MML_LAUNCH((head_fast_kernel<LPS, 4, true, KINDS>), gr, bl, 0, st, g, aux);
+    else MML_LAUNCH((head_fast_kernel<LPS, 8, true, KINDS>), gr, bl, 0, st, g, aux);
     return;
   }
-  if (aux.nt == 2) MML_LAUNCH((head_fast_kernel<LPS, 2, false>), gr, bl, 0, st, g, aux);
-  else if (aux.nt == 4) MML_LAUNCH((head_fast_kernel<LPS, 4, false>), gr, bl, 0, st, g, aux);
-  else MML_LAUNCH((head_fast_kernel<LPS, 8, false>), gr, bl, 0, st, g, aux);
+  if (aux.nt == 2) MML_LAUNCH((head_fast_kernel<LPS, 2, false, KINDS>), gr, bl, 0, st, g, aux);
+  else if (aux.nt == 4) MML_LAUNCH((head_fast_kernel<LPS, 4, false, KINDS>), gr, bl, 0, st, g, aux);
+  else MML_LAUNCH((head_fast_kernel<LPS, 8, false, KINDS>), gr, bl, 0, st, g, aux);
+}
+
+template <int LPS>
+static void launch_head(const mml_head_group& g, const HeadFastAux& aux, hipStream_t st) {
+  if (aux.kinds) launch_head_k<LPS, true>(g, aux, st);
+  else launch_head_k<LPS, false>(g, aux, st);
 }
 
 int head_fast(const mml_head_group* g, const HeadFastAux& aux, hipStream_t st) {

@@ -19,6 +19,8 @@ struct HeadFastAux {
   int32_t stride, hmax, train;
   int32_t lps, nt, grid;
   int32_t gated;                  // some head reads Hin (.) gate (mml_head_desc.gate)
+  int32_t kinds;                  // some head has a non-zero kind: the KINDS instantiation (out_bits / loss_bits below)
+  uint32_t out_bits, loss_bits;   // head t: output form in bit t, loss in bits 2t, 2t + 1 (a lane picks its head's by shifts)
 };
 
 // return the lane-group width (16/32/64) when the fast path applies, 0 otherwise

@@ -9,7 +9,7 @@
 // like gemm_ws_kernel's (same operand images: the tower weight's pre-cut fp16 planes in BOTH layouts stay in LDS, the input
 // rows come from HBM as MFMA fragments):
 //   rows -> h = relu(x W^T + b) [3 x NS MFMAs per k-step] -> logit = h . w + bias (lane sums + one half-wave exchange) ->
-//   p, masked p, clamped-log BCE, dlogit (the head kernel's expressions) -> dH = dlogit w relu'(h) -> cut into planes IN THE
+//   p, masked p, clamped-log BCE, dlogit (the head kernel's expressions; per task those of its kind: identity, MSE, MAE) -> dH = dlogit w relu'(h) -> cut into planes IN THE
 //   ACCUMULATOR LAYOUT (a lane's eight values of a 16-column block are exactly an A fragment: the planes' k order was chosen
 //   for this) -> dX = dH W [3 x NS2 MFMAs per k-step] -> row-major turn -> stores.
 // dH is scaled per 32-row block (its own largest magnitude: the rows of a block only meet their own products), so no magnitude
@@ -52,7 +52,7 @@ struct ThProblem {
   float* slab;               // [wg_per_prob][N + 1]: dw, dbias partial sums of this problem
   float* loss_slab;          // [wg_per_prob] loss partial sums of this problem (the problems' arrays stand back to back)
   int64_t lda, ldpf, ldpb, lddh, ldda;
-  int32_t n_hbias2, mask_col, head, pad_;
+  int32_t n_hbias2, mask_col, head, kind;
 };
 struct ThLaunch {
   int64_t M;
@@ -80,7 +80,9 @@ __device__ __forceinline__ int th_scale_exp(uint32_t bits) {  // (gemm.hip's rul
 __device__ __forceinline__ float th_pow2(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
 
 // NS: tower width / 32 (the head's H), NS2: tower input width / 32
-template <int NS, int NS2>
+// KINDS: some task has a non-zero kind (include/mmlrec.h K5; chosen on the host).  A workgroup serves ONE task, so its kind
+// is uniform over the workgroup.
+template <int NS, int NS2, bool KINDS>
 __global__ __launch_bounds__(512, 2) void tower_head_kernel(const ThLaunch L) {
   constexpr int N = NS * 32, K = NS2 * 32;
   constexpr int KBF = K / 16;   // k-steps of the forward GEMM
@@ -228,14 +230,26 @@ __global__ __launch_bounds__(512, 2) void tower_head_kernel(const ThLaunch L) {
         }
       const float logit = part + __shfl_xor(part, 32, 64) + hb;
       // ---- PredictionLayer, mask, summed BCE and its derivative (csrc/rows_fast.hip: head_fast_kernel's expressions)
-      const float pj = 1.f / (1.f + expf(-logit));
-      const float pm = pj * mv;
-      if (ok && h == 0) L.prob[row * L.ldprob + P.head] = pm;
-      const float lp = bce_log_clamp(logf(pm));
-      const float l1p = bce_log_clamp(log1pf(-pm));
-      if (ok && h == 0) lossacc += -(yv * lp + (1.f - yv) * l1p);
-      const float dpm = (pm - yv) / fmaxf((1.f - pm) * pm, 1e-12f);
-      const float dlogit = ok ? dpm * mv * pj * (1.f - pj) : 0.f;
+      float pj, pm, dlogit;
+      if constexpr (KINDS) {
+        const int kind = __builtin_amdgcn_readfirstlane(P.kind);
+        pj = head_kind_out(kind, logit);
+        pm = pj * mv;
+        if (ok && h == 0) L.prob[row * L.ldprob + P.head] = pm;
+        float ls, dpm;
+        head_kind_loss(kind, pm, yv, ls, dpm);
+        if (ok && h == 0) lossacc += ls;
+        dlogit = ok ? head_kind_dz(kind, dpm, mv, pj) : 0.f;
+      } else {
+        pj = 1.f / (1.f + expf(-logit));
+        pm = pj * mv;
+        if (ok && h == 0) L.prob[row * L.ldprob + P.head] = pm;
+        const float lp = bce_log_clamp(logf(pm));
+        const float l1p = bce_log_clamp(log1pf(-pm));
+        if (ok && h == 0) lossacc += -(yv * lp + (1.f - yv) * l1p);
+        const float dpm = (pm - yv) / fmaxf((1.f - pm) * pm, 1e-12f);
+        dlogit = ok ? dpm * mv * pj * (1.f - pj) : 0.f;
+      }
       if (h == 0) dbacc += dlogit;
       // ---- dH = dlogit w relu'(h); the head's dw; the block's largest |dH|
       float amb = 0.f;
@@ -421,6 +435,7 @@ extern "C" int mml_tower_head_serves(const mml_tower_head_group* g) {
     if (!aligned16(d.w_planes_fwd) || d.ldpf % 4 != 0 || d.ldpf < d.K || d.ldpb < d.K) return 0;
     if (d.n_hbias2 < 0 || (d.n_hbias2 > 0 && !d.hbias2)) return 0;
     if (d.mask_col >= 0 && !g->mask) return 0;
+    if (head_kind_check(d.kind, true)) return 0;  // (mml_tower_head_fwd_bwd names the reason)
   }
   return 1;
 }
@@ -434,6 +449,17 @@ extern "C" int64_t mml_tower_head_workspace_bytes(const mml_tower_head_group* g)
 extern "C" int mml_tower_head_fwd_bwd(const mml_tower_head_group* g, void* workspace, int64_t workspace_bytes, int32_t phase,
                                       mml_stream_t stream) {
   MML_REQUIRE(g != nullptr && phase >= 0 && phase <= 2, "mml_tower_head_fwd_bwd: null group or bad phase");
+  bool kinds = false;
+  for (int t = 0; t < g->n && t < MML_MAX_HEADS; ++t) {
+    const int kc = head_kind_check(g->t[t].kind, true);
+    MML_REQUIRE(kc != 1, "mml_tower_head_fwd_bwd: task %d: kind 0x%x is not MML_HEAD_KIND(output form, loss)", t, g->t[t].kind);
+    if (kc == 2) {
+      set_error("mml_tower_head_fwd_bwd: task %d: identity output with binary cross-entropy (the loss of a raw value is squared "
+                "or absolute error)", t);
+      return MML_ERR_UNSUPPORTED;
+    }
+    kinds = kinds || g->t[t].kind != 0;
+  }
   if (!mml_tower_head_serves(g)) {
     set_error("mml_tower_head_fwd_bwd: not a group this kernel serves (widths 64 <- 128 / 64 <- 64, fp32, 16-byte "
               "aligned rows, pre-cut planes in both layouts, the input's magnitude)");
@@ -452,14 +478,19 @@ extern "C" int mml_tower_head_fwd_bwd(const mml_tower_head_group* g, void* works
     P.A = d.A; P.amaxA = d.amax_a; P.planesF = d.w_planes_fwd; P.planesB = d.w_planes_bwd; P.kexpF = d.kexp_fwd;
     P.kexpB = d.kexp_bwd; P.bias1 = d.bias1; P.w = d.w; P.hbias = d.hbias; P.hbias2 = d.hbias2; P.dH = d.dH; P.dA = d.dA;
     P.amax_dH = d.amax_dH; P.amax_dA = d.amax_dA; P.lda = d.lda; P.ldpf = d.ldpf; P.ldpb = d.ldpb; P.lddh = d.lddh;
-    P.ldda = d.ldda; P.n_hbias2 = d.n_hbias2; P.mask_col = d.mask_col; P.head = d.head;
+    P.ldda = d.ldda; P.n_hbias2 = d.n_hbias2; P.mask_col = d.mask_col; P.head = d.head; P.kind = d.kind;
     P.slab = ws + (int64_t)t * L.wg_per_prob * (N + 1);
     P.loss_slab = ws + (int64_t)g->n * L.wg_per_prob * (N + 1) + (int64_t)t * L.wg_per_prob;
   }
   if (phase != 2) {
     const dim3 grid((unsigned)(L.wg_per_prob * L.n_prob)), block(512);
-    if (K == 128) MML_LAUNCH((tower_head_kernel<2, 4>), grid, block, 0, to_stream(stream), L);
-    else MML_LAUNCH((tower_head_kernel<2, 2>), grid, block, 0, to_stream(stream), L);
+    if (kinds) {
+      if (K == 128) MML_LAUNCH((tower_head_kernel<2, 4, true>), grid, block, 0, to_stream(stream), L);
+      else MML_LAUNCH((tower_head_kernel<2, 2, true>), grid, block, 0, to_stream(stream), L);
+    } else {
+      if (K == 128) MML_LAUNCH((tower_head_kernel<2, 4, false>), grid, block, 0, to_stream(stream), L);
+      else MML_LAUNCH((tower_head_kernel<2, 2, false>), grid, block, 0, to_stream(stream), L);
+    }
     const int rc = check_launch("mml_tower_head_fwd_bwd");
     if (rc != MML_OK || phase == 1) return rc;
   }

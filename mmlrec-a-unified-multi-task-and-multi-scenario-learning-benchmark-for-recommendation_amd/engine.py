@@ -128,6 +128,7 @@ class Plan:
                      L.load().mml_gemm_get_mode() == 1)
         if self.bf16:
             self.use_amax = False  # (mode 1 reads no operand magnitudes)
+        self.tower_head = None   # the mml_tower_head_group of the fused top of the network (fuse_tower_head), if any
         self.cast16_items = []   # (fp32 weight, bf16 copy, transposed): refreshed by ONE launch at the start of a step
         self.cast16_cache = {}
         self.amax_pool = ops.amax_slots(1024, device) if (device.type == "cuda" and self.use_amax) else None
@@ -766,7 +767,7 @@ class Plan:
             q.bias1, q.w, q.hbias, q.hbias2, q.n_hbias2 = f.bias, h.w, h.bias, h.bias2, h.n_bias2
             q.dH, q.lddh, q.dA, q.ldda, q.dw, q.dhbias = h.dH, h.lddh, d.dA, d.ldda, h.dw, h.dbias
             q.amax_dH, q.amax_dA = grp.amax_dH, d.amax_out
-            q.mask_col, q.head = h.mask_col, t
+            q.mask_col, q.head, q.kind = h.mask_col, t, h.kind
         if not lib.mml_tower_head_serves(C.byref(g)):
             return False
         nws = int(lib.mml_tower_head_workspace_bytes(C.byref(g)))
@@ -1698,8 +1699,9 @@ def _defer_reduce():
 
 
 class HeadOp(Op):
-    """K5: prediction heads (+ summed BCE and its backward when training).
-    heads: dicts with Hin (Val), w (PVal with H elements), bias (PVal [1]), bias2 (PVal [1] or None); a gated head (round 6,
+    """K5: prediction heads (+ the summed loss and its backward when training).
+    heads: dicts with Hin (Val), w (PVal with H elements), bias (PVal [1]), bias2 (PVal [1] or None), kind (L.head_kind(out,
+    loss), default 0 = sigmoid + BCE; BaseModel._finish_record fills it from task_types and the compiled losses); a gated head (round 6,
     PepNet's last PPNet layer, reference model/pepnet.py:72-78) also carries gate (Val: the input of the head is
     Hin (.) gate, formed inside the kernel; this op must be the only consumer of both values)."""
 
@@ -1726,7 +1728,8 @@ class HeadOp(Op):
             Hin = h["Hin"]
             q = dict(Hin=Hin.buf, w=h["w"].data, bias=h["bias"].data,
                      bias2=h["bias2"].data if h.get("bias2") is not None else None,
-                     mask_col=(self.mask_cols[t] if (self.mask_cols and plan.mask is not None) else -1))
+                     mask_col=(self.mask_cols[t] if (self.mask_cols and plan.mask is not None) else -1),
+                     kind=int(h.get("kind", 0)))  # (include/mmlrec.h K5: output form and loss of the head)
             G = h.get("gate")
             if G is not None:
                 if G.n != Hin.n or not _fast_row_width_ok(Hin.n) or Hin.is16 or G.is16:

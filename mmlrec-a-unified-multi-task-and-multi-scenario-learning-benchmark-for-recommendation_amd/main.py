@@ -69,29 +69,33 @@ def ordered_labels(label_columns):
 
 
 def evaluate_predictions(model, config, test, target, test_mask, pred_ans):
-    """Per-head LogLoss/AUC (+ total_auc for msl/mtmsl) rounded like the reference (main.py:128-172)."""
-    from sklearn.metrics import log_loss, roc_auc_score
+    """Per-head LogLoss/AUC (+ total_auc for msl/mtmsl) rounded like the reference (main.py:128-172); a regression task
+    writes mse_{i} / mae_{i} instead (the reference's rows have no regression form: INTEGRATION.md)."""
+    from sklearn.metrics import log_loss, mean_absolute_error, mean_squared_error, roc_auc_score
     dc, mc = config["data_config"], config["model_config"]
     res = {}
     labels = np.asarray(test[target].values)
     total_auc = None
-    for i, _ in enumerate(model.task_types):
+    D = dc.get("num_domains", 0)
+    for i, task_type in enumerate(model.task_types):
+        yl, yp = labels[:, i], pred_ans[:, i]
         if model.task_name in ("msl", "mtmsl"):
-            j = i if model.task_name == "msl" else i % dc.get("num_domains", 0)
+            j = i if model.task_name == "msl" else i % D
             m = test_mask[:, j].astype(bool)
-            ml, mp = labels[:, i][m].reshape(-1, 1), pred_ans[:, i][m].reshape(-1, 1)
-            ll, auc = round(log_loss(ml, mp), 4), round(roc_auc_score(ml, mp), 4)
-            if model.task_name == "msl":
-                total_auc = roc_auc_score(labels[:, 0], np.sum(pred_ans, axis=-1))
-            else:
-                l = dc.get("num_domains", 0)
-                yt = labels[:, [0, l]]
-                yp = np.stack([pred_ans[:, :l].sum(-1), pred_ans[:, l:].sum(-1)], -1)
-                total_auc = roc_auc_score(yt, yp)
+            yl, yp = yl[m].reshape(-1, 1), yp[m].reshape(-1, 1)
+        if task_type == "regression":
+            res[f"mse_{i}"] = round(float(mean_squared_error(yl, yp)), 4)
+            res[f"mae_{i}"] = round(float(mean_absolute_error(yl, yp)), 4)
         else:
-            ll = round(log_loss(labels[:, i], pred_ans[:, i]), 4)
-            auc = round(roc_auc_score(labels[:, i], pred_ans[:, i]), 4)
-        res[f"log_loss_{i}"], res[f"auc_{i}"] = ll, auc
+            res[f"log_loss_{i}"], res[f"auc_{i}"] = round(log_loss(yl, yp), 4), round(roc_auc_score(yl, yp), 4)
+    if model.task_name == "msl" and model.task_types[0] == "binary":
+        total_auc = roc_auc_score(labels[:, 0], np.sum(pred_ans, axis=-1))
+    elif model.task_name == "mtmsl":
+        groups = [g for g in (0, 1) if model.task_types[g * D] == "binary"]
+        if groups:
+            yt = labels[:, [g * D for g in groups]]
+            yp = np.stack([pred_ans[:, g * D:(g + 1) * D].sum(-1) for g in groups], -1)
+            total_auc = roc_auc_score(yt[:, 0], yp[:, 0]) if len(groups) == 1 else roc_auc_score(yt, yp)
     if total_auc is not None:
         res["total_auc"] = round(total_auc, 4)
     return res

@@ -12,6 +12,7 @@ from .utils import DNN, PredictionLayer, dnn_options, emit_dnn_stacks, l2_on_wei
 
 
 class AITM(BaseModel):
+    binary_only = "the calibrator constrains one probability by the other"
     def __init__(self, dnn_feature_columns, init_std=0.0001, device="cpu", gpus=None, config=None):
         super().__init__(linear_feature_columns=[], dnn_feature_columns=dnn_feature_columns, init_std=init_std,
                          device=device, gpus=gpus, config=config)

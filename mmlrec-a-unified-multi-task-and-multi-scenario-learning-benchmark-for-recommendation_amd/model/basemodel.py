@@ -80,6 +80,11 @@ class _PlanFunction(torch.autograd.Function):
 class BaseModel(nn.Module):
     num_outputs = None      # columns of forward()'s result when that differs from num_tasks (ESCM: 3 for 2 tasks)
     metric_columns = None   # ... and the output columns the metrics are computed on (basemodel.py:326-327)
+    binary_only = None      # models whose outputs are products of probabilities or constraints on them: the reason they
+                            # refuse regression tasks and losses other than binary_crossentropy (ESMM, ESCM, AITM)
+    LOSS_KINDS = {"binary_crossentropy": L.HEAD_LOSS_BCE, "mse": L.HEAD_LOSS_MSE, "mae": L.HEAD_LOSS_MAE}
+    METRIC_KINDS = {"auc": "binary", "acc": "binary", "accuracy": "binary", "logloss": "binary",
+                    "binary_crossentropy": "binary", "mse": "regression"}
 
     def __init__(self, linear_feature_columns, dnn_feature_columns, init_std=0.0001, device="cpu", gpus=None,
                  config=None):
@@ -121,9 +126,8 @@ class BaseModel(nn.Module):
         for task_type in self.task_types:
             if task_type not in ["binary", "regression"]:
                 raise ValueError("task must be binary or regression, {} is illegal".format(task_type))
-            if task_type != "binary":
-                raise NotImplementedError("regression heads are outside the MI355X hot path (every shipped config is "
-                                          "binary)")
+            if task_type != "binary" and self.binary_only:
+                raise NotImplementedError(f"{type(self).__name__}: task type {task_type!r}: {self.binary_only}")
         if any(isinstance(f, VarLenSparseFeat) for f in dnn_feature_columns):
             from .utils import pooled_layout
             pooled_layout(dnn_feature_columns)  # (one embedding_dim, known combiners, equal sizes of a shared table)
@@ -376,6 +380,12 @@ class BaseModel(nn.Module):
     def _finish_record(self, plan, store, x0):
         head = self._build_graph(plan, store, x0)
         head.mask_cols = self._head_mask_cols()
+        if len(head.heads) == self.num_tasks:  # head t is task t's PredictionLayer
+            for t, h in enumerate(head.heads):
+                h.setdefault("kind", self._head_kind(t))
+        elif any(t != "binary" for t in self.task_types) and any("kind" not in h for h in head.heads):
+            raise NotImplementedError(f"{type(self).__name__}: {len(head.heads)} heads for {self.num_tasks} tasks with a "
+                                      "regression task: the model must name each head's kind itself")
         plan.finish(head)
         plan.written_names = {n for n, pv in store.pvals.items() if pv.written}
         if (getattr(self, "optim_name", None) is None and plan.dropout_on and
@@ -419,6 +429,17 @@ class BaseModel(nn.Module):
         if self.task_name in ("msl", "mtmsl"):
             return [i if self.task_name == "msl" else i % self.num_domains for i in range(self.num_tasks)]
         return None
+
+    def _head_kind(self, t):
+        """mml_head_desc.kind of head t (include/mmlrec.h, K5): PredictionLayer(task_types[t])'s output form, and the loss
+        compile() named for the task -- before compile (forward, autograd through dprob) only the output form is read."""
+        out = L.HEAD_OUT_IDENTITY if self.task_types[t] == "regression" else L.HEAD_OUT_SIGMOID
+        names = getattr(self, "loss_func", None)
+        if names is None:
+            loss = L.HEAD_LOSS_MSE if out == L.HEAD_OUT_IDENTITY else L.HEAD_LOSS_BCE
+        else:
+            loss = self.LOSS_KINDS[names[t]]
+        return L.head_kind(out, loss)
 
     def _build_graph(self, plan, store, x0):
         raise NotImplementedError
@@ -508,10 +529,19 @@ class BaseModel(nn.Module):
         self._optimizer = None
 
     def _get_loss_func(self, loss):
-        names = loss if isinstance(loss, list) else [loss] * self.num_tasks
-        for n in names:
-            if n != "binary_crossentropy":
-                raise NotImplementedError(f"loss {n!r}: the fused head kernel implements binary_crossentropy")
+        """One loss name per task (reference :586-603): binary_crossentropy, mse (F.mse_loss) or mae (F.l1_loss), each summed
+        over the batch; the head kernels evaluate them (include/mmlrec.h, K5: MML_HEAD_LOSS_*)."""
+        names = list(loss) if isinstance(loss, (list, tuple)) else [loss] * self.num_tasks
+        if len(names) != self.num_tasks:
+            raise ValueError("the length of `loss` should be equal with `self.num_tasks`")
+        for n, task_type in zip(names, self.task_types):
+            if n not in self.LOSS_KINDS:
+                raise NotImplementedError(f"loss {n!r}: the head kernels implement binary_crossentropy, mse and mae")
+            if self.binary_only and n != "binary_crossentropy":
+                raise NotImplementedError(f"{type(self).__name__}: loss {n!r}: {self.binary_only}")
+            if task_type == "regression" and n == "binary_crossentropy":
+                raise ValueError("binary_crossentropy on a regression task: the cross-entropy of a raw value is undefined; "
+                                 "use mse or mae")
         return names
 
     @staticmethod
@@ -522,6 +552,7 @@ class BaseModel(nn.Module):
     def _get_metrics(self, metrics, set_eps=False):
         from sklearn.metrics import log_loss, mean_squared_error, roc_auc_score
         m = {}
+        self.metric_cols = {}
         for name in metrics or []:
             if name in ("binary_crossentropy", "logloss"):
                 m[name] = log_loss
@@ -531,8 +562,30 @@ class BaseModel(nn.Module):
                 m[name] = mean_squared_error
             if name in ("accuracy", "acc"):
                 m[name] = self._accuracy_score
+            if name in m:
+                self.metric_cols[name] = self._metric_columns_of(name)
             self.metrics_names.append(name)
         return m
+
+    def _metric_columns_of(self, name):
+        """The columns a metric scores, counted AFTER the task-mode reduction of _metric (mtl: the tasks; msl: the one
+        summed column; mtmsl: the two label groups).  None = all of them: every model whose tasks are all binary, as in the
+        reference.  Once a task is a regression, auc / acc / logloss score the binary columns and mse the regression
+        columns (the reference applies every metric to every column and so cannot score a mixed model at all:
+        INTEGRATION.md)."""
+        if all(t == "binary" for t in self.task_types):
+            return None
+        if self.task_name == "msl":
+            kinds = [self.task_types[0]]
+        elif self.task_name == "mtmsl":
+            kinds = [self.task_types[0], self.task_types[self.num_domains]]
+        else:
+            kinds = list(self.task_types)
+        cols = [i for i, k in enumerate(kinds) if k == self.METRIC_KINDS[name]]
+        if not cols:
+            raise ValueError(f"metric {name!r} scores {self.METRIC_KINDS[name]} tasks and this model has none "
+                             f"(task_types = {self.task_types})")
+        return cols
 
     def optimizer(self):
         """The fused optimizer bound to this model's parameter store (created on first use after compile)."""
@@ -629,6 +682,13 @@ class BaseModel(nn.Module):
         print("Train on {0} samples, validate on {1} samples, {2} steps per epoch".format(
             n_total, 0 if val_y is None else len(val_y), steps_per_epoch))
         best_auc, early_stop, best_model = 0, 0, None
+        # what validation selects on: `auc` when it is compiled (the reference's rule, unchanged).  A model with regression
+        # tasks may have no binary column for it (compile refuses `auc` then): it selects on falling `val_mse` when `mse`
+        # is compiled, and without either it neither selects nor stops early
+        select = "auc"
+        if "auc" not in self.metrics and any(t != "binary" for t in self.task_types):
+            select = "mse" if "mse" in self.metrics else None
+        best_mse = float("inf")
         self.history = []
         pred_epoch = torch.empty((n, self.num_outputs or self.num_tasks), dtype=torch.float32, device=dev)
         for epoch in range(initial_epoch, epochs):
@@ -679,7 +739,7 @@ class BaseModel(nn.Module):
                 vals = []
                 for s in range(steps_per_epoch):
                     sl = slice(s * batch_size, (s + 1) * batch_size)
-                    vals.append(self._metric(fn, ye[sl], pe[sl]))
+                    vals.append(self._metric(fn, ye[sl], pe[sl], self.metric_cols.get(name)))
                 epoch_logs[name] = np.sum(vals) / steps_per_epoch
             if world > 1:  # mean over ranks of the per-rank step averages
                 names = [m for m in self.metrics]
@@ -694,11 +754,20 @@ class BaseModel(nn.Module):
                 # models without BatchNorm -- every hot-path config -- the two are identical.)
                 eval_result = self.evaluate(val_x, val_y, batch_size)
                 print(eval_result)
-                if eval_result.get("auc", 0) > best_auc:
-                    best_auc = eval_result["auc"]
+                if select == "auc":
+                    better = eval_result.get("auc", 0) > best_auc
+                    if better:
+                        best_auc = eval_result["auc"]
+                elif select == "mse":
+                    better = eval_result["mse"] < best_mse
+                    if better:
+                        best_mse = eval_result["mse"]
+                else:
+                    better = None
+                if better:
                     best_model = copy.deepcopy(self)
                     early_stop = 0
-                else:
+                elif better is not None:
                     early_stop += 1
                 for name, result in eval_result.items():
                     epoch_logs["val_" + name] = result
@@ -726,7 +795,7 @@ class BaseModel(nn.Module):
         _metric: msl -> (label 0, sum of the heads); mtmsl -> per label group; mtl -> sklearn's multilabel behaviour
         (macro-average AUC over tasks, exact-match accuracy).  Returns {} when a metric cannot be done on the device
         (batches over 4096 rows): the caller then falls back to the host path."""
-        want = [m for m in self.metrics if m in ("auc", "acc", "accuracy")]
+        want = [m for m in self.metrics if m in ("auc", "acc", "accuracy", "mse")]
         if not want or batch_size > 4096 or not pred.is_cuda:
             return {}
         ye = yd.index_select(0, perm_d)
@@ -738,32 +807,48 @@ class BaseModel(nn.Module):
             pt = torch.stack([pred[:, :D].sum(-1), pred[:, D:].sum(-1)], -1)
         else:
             yt, pt = ye, pred
-        yt, pt = yt.contiguous(), pt.contiguous()
         n = pt.shape[0]
         steps = (n - 1) // batch_size + 1
         out = {}
+
+        def columns(name):  # (the metric's own columns once a task is a regression: _metric_columns_of)
+            cols = getattr(self, "metric_cols", {}).get(name)
+            if cols is None:
+                return yt.contiguous(), pt.contiguous()
+            return yt[:, cols].contiguous(), pt[:, cols].contiguous()
+
+        def step_means(v):  # [n] float64 -> mean over steps of the per-batch means
+            seg = torch.arange(n, device=v.device) // batch_size
+            per = torch.zeros(steps, dtype=torch.float64, device=v.device).index_add_(0, seg, v)
+            cnt = torch.zeros(steps, dtype=torch.float64, device=v.device).index_add_(0, seg, torch.ones_like(v))
+            return float((per / cnt).sum().item()) / steps
+
         if "auc" in want:
-            a = ops.auc_segments(pt, yt, batch_size)            # [steps, C]; NaN = single-class batch
+            ya, pa = columns("auc")
+            a = ops.auc_segments(pa, ya, batch_size)            # [steps, C]; NaN = single-class batch
             out["auc"] = float(a.mean(1).sum().item()) / steps  # macro average over columns, mean over steps
         for name in ("acc", "accuracy"):
             if name in want:
-                hit = ((pt > 0.5) == (yt > 0.5)).all(1).to(torch.float64)  # exact match over the columns
-                seg = torch.arange(n, device=pt.device) // batch_size
-                per = torch.zeros(steps, dtype=torch.float64, device=pt.device).index_add_(0, seg, hit)
-                cnt = torch.zeros(steps, dtype=torch.float64, device=pt.device).index_add_(0, seg, torch.ones_like(hit))
-                out[name] = float((per / cnt).sum().item()) / steps
+                ya, pa = columns(name)
+                out[name] = step_means(((pa > 0.5) == (ya > 0.5)).all(1).to(torch.float64))  # exact match over the columns
+        if "mse" in want:  # sklearn's mean_squared_error: the mean over samples and columns
+            ya, pa = columns("mse")
+            out["mse"] = step_means(((pa.double() - ya.double()) ** 2).mean(1))
         return out
 
-    def _metric(self, fn, y_true, y_pred):
-        """Task-mode specific metric reduction (reference :320-331, :383-392)."""
+    def _metric(self, fn, y_true, y_pred, cols=None):
+        """Task-mode specific metric reduction (reference :320-331, :383-392); cols: _metric_columns_of."""
         try:
             if self.task_name == "msl":
                 return fn(y_true[:, 0], y_pred.sum(-1))
             if self.task_name == "mtmsl":
                 D = self.num_domains
-                yn = y_true[:, [0, D]]
-                pn = np.stack([y_pred[:, :D].sum(-1), y_pred[:, D:].sum(-1)], -1)
-                return fn(yn, pn)
+                y_true = y_true[:, [0, D]]
+                y_pred = np.stack([y_pred[:, :D].sum(-1), y_pred[:, D:].sum(-1)], -1)
+            if cols is not None:
+                y_true, y_pred = y_true[:, cols], y_pred[:, cols]
+                if len(cols) == 1:
+                    y_true, y_pred = y_true[:, 0], y_pred[:, 0]
             return fn(y_true, y_pred)
         except ValueError:  # a batch with a single class has no AUC; the reference would raise here
             return float("nan")
@@ -773,10 +858,10 @@ class BaseModel(nn.Module):
         if self.metric_columns is not None:  # (the reference scores all columns here and raises for ESCM: model/escm.py)
             pred = pred[:, list(self.metric_columns)]
         y = np.asarray(y).reshape(len(pred), -1)
-        return {name: self._metric(fn, y, pred) for name, fn in self.metrics.items()}
+        return {name: self._metric(fn, y, pred, self.metric_cols.get(name)) for name, fn in self.metrics.items()}
 
     def predict(self, x, batch_size=256, domain_mask=None):
-        """float64 [N,T] probabilities (reference :395-457).  Like the reference's loop (:436-437) the heads
+        """float64 [N,T] predictions -- probabilities, raw values in the columns of regression tasks (reference :395-457).  Like the reference's loop (:436-437) the heads
         are NOT masked here; pass a mask to forward() directly for masked outputs."""
         was_training = self.training
         self.eval()

@@ -16,6 +16,7 @@ from .utils import DNN, dnn_options, emit_dnn_stacks, l2_on_weights
 
 
 class ESCM(BaseModel):
+    binary_only = "the outputs are products of probabilities and the loss is the counterfactual BCE branch"
     num_outputs = 3
     metric_columns = (0, 2)
 

@@ -9,6 +9,7 @@ from .utils import DNN, dnn_options, emit_dnn_stacks, l2_on_weights
 
 
 class ESMM(BaseModel):
+    binary_only = "the second output is a product of two probabilities"
     def __init__(self, dnn_feature_columns, init_std=0.0001, device="cpu", gpus=None, config=None):
         super().__init__(linear_feature_columns=[], dnn_feature_columns=dnn_feature_columns, init_std=init_std,
                          device=device, gpus=gpus, config=config)

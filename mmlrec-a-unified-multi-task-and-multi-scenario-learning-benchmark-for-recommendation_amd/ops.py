@@ -647,8 +647,8 @@ def gate_mix_bwd(group, device, phases=False):
 # ---------------------------------------------------------------------------------------------- K5
 def make_head_group(heads, prob, y=None, mask=None, loss=None, dprob=None):
     """heads: dicts with Hin [B,H], w [H] (any shape with H elements), bias [1], optional w2, bias2 (list of 1-element
-    tensors packed by the caller into one tensor), dH, dw, dbias, h_relu, mask_col; gated heads also gate [B,H], dgate,
-    gate_act."""
+    tensors packed by the caller into one tensor), dH, dw, dbias, h_relu, mask_col, kind (L.head_kind(out, loss); default 0 =
+    sigmoid + BCE); gated heads also gate [B,H], dgate, gate_act."""
     g = L.HeadGroup()
     g.n_heads = len(heads)
     g.B = prob.shape[0]
@@ -674,6 +674,7 @@ def make_head_group(heads, prob, y=None, mask=None, loss=None, dprob=None):
         d.dw, d.dbias = L.ptr(q.get("dw")), L.ptr(q.get("dbias"))
         d.h_relu = int(q.get("h_relu", 1))
         d.mask_col = int(q.get("mask_col", -1))
+        d.kind = int(q.get("kind", 0))
         if q.get("gate") is not None:  # gated head: the input is Hin (.) gate (include/mmlrec.h: mml_head_desc.gate)
             d.gate, d.ldgate = q["gate"].data_ptr(), _ld(q["gate"])
             d.gate_act = int(q.get("gate_act", L.ACT_NONE))
@@ -690,7 +691,7 @@ def make_head_group(heads, prob, y=None, mask=None, loss=None, dprob=None):
 def make_tower_head_group(tasks, prob, y, mask=None, loss=None):
     """K5' (include/mmlrec.h): tasks = dicts with A [M, K], amax_a, planes_fwd / kexp_fwd (MML_PLANES_ROWS image of the tower
     weight [N, K]), planes_bwd / kexp_bwd (MML_PLANES_COLS), bias1 [N] or None, w [N], hbias [1], hbias2 or None, dH [M, N],
-    dA [M, K], dw [N], dhbias [1], optional amax_dH / amax_dA, mask_col, head (column of prob / y)."""
+    dA [M, K], dw [N], dhbias [1], optional amax_dH / amax_dA, mask_col, head (column of prob / y), kind (as in make_head_group)."""
     g = L.TowerHeadGroup()
     g.n, g.M = len(tasks), prob.shape[0]
     g.prob, g.ldprob = prob.data_ptr(), _ld(prob)
@@ -715,6 +716,7 @@ def make_tower_head_group(tasks, prob, y, mask=None, loss=None):
         d.dw, d.dhbias = q["dw"].data_ptr(), q["dhbias"].data_ptr()
         d.amax_dH, d.amax_dA = L.ptr(q.get("amax_dH")), L.ptr(q.get("amax_dA"))
         d.mask_col, d.head = int(q.get("mask_col", -1)), int(q.get("head", t))
+        d.kind = int(q.get("kind", 0))
     return g
 
 
