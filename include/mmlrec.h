@@ -152,12 +152,31 @@ int mml_index_unique(const int64_t* vocab, const int32_t* col, int32_t F, int32_
  * marked rows into fp32, adds them to grad_tables and zeroes them again.  Integer sums do not depend on the order of
  * the addends, so the result is BITWISE repeatable and independent of the order of the samples in the batch (a sorted
  * fp32 sum would still depend on it); accuracy: addends down to 2^-(62 - 24 - ceil(log2 B)) of the largest |dOut| are
- * summed exactly.  row_marks: the byte map of mml_scatter_bwd (required: the second launch walks it); clear_marks = 0
- * leaves the marks for mml_opt_tensor.grad_marks / mml_rows_compact.  E in {4, 8, 16}, dOut 16-byte aligned. */
+ * summed exactly.  row_marks: the byte map of mml_scatter_bwd (required: the second launch walks it).  E in {4, 8, 16},
+ * dOut 16-byte aligned.
+ * flags (0 and 1 are the former clear_marks argument; any other bit than these three is MML_ERR_ARG):
+ *   MML_SCATTER_DET_CLEAR_MARKS    the second launch clears the marks it finds; without it they stay set for
+ *                                  mml_opt_tensor.grad_marks / mml_rows_compact.
+ *   MML_SCATTER_DET_AMAX_SUPPLIED  amax_slot already holds the magnitude of dOut[0:B, 0:F*E] -- raised by the launch that
+ *                                  wrote dOut (mml_gemm_dgrad_desc.amax_out) on a slot zeroed before it: the call issues
+ *                                  neither mml_amax_reset nor mml_amax_batch.  Only the exponent of the largest word is
+ *                                  used, so any producer that records the exact maximum of what it stored gives the bits
+ *                                  the call's own pass gives.
+ *   MML_SCATTER_DET_DEFER_TOTALS   no second launch: the row totals stay in acc64 and the marks stay set, and the caller
+ *                                  owes ONE mml_opt_step_dense over every table with mml_opt_tensor.acc64 / acc_amax /
+ *                                  acc_shift = acc64[f] / amax_slot / mml_scatter_det_shift(B), which adds the totals to
+ *                                  the gradient it reads, zeroes them and clears the marks.  Not with CLEAR_MARKS. */
+#define MML_SCATTER_DET_CLEAR_MARKS 1
+#define MML_SCATTER_DET_AMAX_SUPPLIED 2
+#define MML_SCATTER_DET_DEFER_TOTALS 4
 int mml_scatter_bwd_det(float* const* grad_tables, const int64_t* vocab, const int32_t* col, int32_t F, int32_t E,
                         const float* X, int64_t ldX, int64_t B, const float* dOut, int64_t ldo, int64_t* const* acc64,
-                        uint32_t* amax_slot, uint8_t* row_marks, int32_t clear_marks, int32_t* status,
+                        uint32_t* amax_slot, uint8_t* row_marks, int32_t flags, int32_t* status,
                         mml_stream_t stream);
+/* log2 of the fixed-point scale mml_scatter_bwd_det uses for a batch of B samples (a function of B alone: 24 significand
+ * bits + shift + ceil(log2 B) < 63, clamped to [4, 28]); a total t stands for t * 2^(emax - 150 - shift), emax = the
+ * exponent field of the slot's largest word clamped to [1, 254]. */
+int32_t mml_scatter_det_shift(int64_t B);
 /* Native-index variants (int32 idx[b*ldi + f], fields in array order): vocabularies >= 2^24 and the
  * owner side of row-sharded tables, which sees lookups as keys into its flat row space (F = 1). */
 int mml_scatter_bwd_idx32(float* const* grad_tables, const int64_t* vocab, int32_t F, int32_t E, const int32_t* idx,
@@ -1021,6 +1040,16 @@ typedef struct {
    * bytes per parameter of a dense Adam step, for 99 % of the rows.  The kernel clears the bytes it finds set.
    * Needs row_elems % 4 == 0 with row_elems / 4 a power of two <= 64, 16-byte aligned tensors, no skip_rows. */
   uint8_t* grad_marks;
+  /* Deferred totals of the deterministic scatter (mml_scatter_bwd_det with MML_SCATTER_DET_DEFER_TOTALS): acc64 != NULL
+   * makes the gradient of a MARKED row grad + from_fixed(acc64 row) -- every non-zero 64-bit total converted with the
+   * exponent of the slot acc_amax (MML_AMAX_WORDS words) and acc_shift = mml_scatter_det_shift(B), exactly what the
+   * scatter's second launch would have added to `grad` -- and the kernel zeroes the totals it used.  Unmarked rows read
+   * neither buffer.  Needs grad_marks, a 16-byte aligned [rows, row_elems] int64 array and the streaming launch; a
+   * launch that holds such a tensor takes grad_marks on every tensor.  All zero: the tensor is as before. */
+  int64_t* acc64;
+  const uint32_t* acc_amax;
+  int32_t acc_shift;
+  int32_t acc_pad_;
 } mml_opt_tensor;
 typedef struct {
   int32_t kind;      /* MML_OPT_* */

@@ -23,6 +23,9 @@ def head_kind(out=HEAD_OUT_SIGMOID, loss=HEAD_LOSS_BCE):
     return (int(loss) << 8) | int(out)
 
 
+ERR_ARG = -1
+# mml_scatter_bwd_det flags (include/mmlrec.h)
+SCATTER_DET_CLEAR_MARKS, SCATTER_DET_AMAX_SUPPLIED, SCATTER_DET_DEFER_TOTALS = 1, 2, 4
 OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_RMSPROP = 0, 1, 2, 3
 OPT_KINDS = {"sgd": OPT_SGD, "adam": OPT_ADAM, "adagrad": OPT_ADAGRAD, "rmsprop": OPT_RMSPROP}
 
@@ -142,7 +145,8 @@ class TowerHeadGroup(C.Structure):
 
 class OptTensor(C.Structure):
     _fields_ = [("param", fp), ("grad", fp), ("state1", fp), ("state2", fp), ("n", i64), ("l1", C.c_float),
-                ("l2", C.c_float), ("skip_rows", fp), ("row_elems", i32), ("zero_grads", i32), ("grad_marks", fp)]
+                ("l2", C.c_float), ("skip_rows", fp), ("row_elems", i32), ("zero_grads", i32), ("grad_marks", fp),
+                ("acc64", fp), ("acc_amax", fp), ("acc_shift", i32), ("acc_pad_", i32)]
 
 
 class Copy2dDesc(C.Structure):
@@ -184,6 +188,7 @@ _SIGS = {
                                   fp, fp, i32, fp, fp, fp]),
     "mml_scatter_bwd_det": (C.c_int, [_PP(fp), _PP(i64), _PP(i32), i32, i32, fp, i64, i64, fp, i64, _PP(fp), fp, fp, i32,
                                       fp, fp]),
+    "mml_scatter_det_shift": (i32, [i64]),
     "mml_scatter_bwd_idx32": (C.c_int, [_PP(fp), _PP(i64), i32, i32, fp, i64, i64, fp, i64, _PP(fp), _PP(i64),
                                         fp, fp, i32, fp, fp, fp]),
     "mml_index_unique_idx32": (C.c_int, [_PP(i64), i32, i32, fp, i64, i64, _PP(fp), _PP(i64), fp, fp, i32, fp, fp, fp]),

@@ -1105,9 +1105,17 @@ extern "C" int mml_rows_compact(uint32_t* const* seen, const int64_t* vocab, con
   return launch_compact(ft, a, to_stream(stream), "mml_rows_compact");
 }
 
+// headroom: a row may receive all B addends at the launch-wide maximum: 24 significand bits + shift + log2(B) < 63
+extern "C" int32_t mml_scatter_det_shift(int64_t B) {
+  int lg = 1;
+  while (lg < 62 && ((int64_t)1 << lg) < B) ++lg;
+  const int shift = 62 - 24 - lg;
+  return shift > 28 ? 28 : (shift < 4 ? 4 : shift);
+}
+
 extern "C" int mml_scatter_bwd_det(float* const* grad_tables, const int64_t* vocab, const int32_t* col, int32_t F,
                                    int32_t E, const float* X, int64_t ldX, int64_t B, const float* dOut, int64_t ldo,
-                                   int64_t* const* acc64, uint32_t* amax_slot, uint8_t* row_marks, int32_t clear_marks,
+                                   int64_t* const* acc64, uint32_t* amax_slot, uint8_t* row_marks, int32_t flags,
                                    int32_t* status, mml_stream_t stream) {
   FieldTable ft;
   int rc = fill_fields(ft, (const float* const*)grad_tables, vocab, col, F, "mml_scatter_bwd_det");
@@ -1116,15 +1124,23 @@ extern "C" int mml_scatter_bwd_det(float* const* grad_tables, const int64_t* voc
   MML_REQUIRE(B == 0 || (X && dOut), "mml_scatter_bwd_det: null X/dOut");
   MML_REQUIRE(acc64 && amax_slot && row_marks, "mml_scatter_bwd_det: acc64, amax_slot and row_marks are required");
   MML_REQUIRE(ldo % 4 == 0 && aligned16(dOut), "mml_scatter_bwd_det: dOut must be 16-byte aligned with ldo %% 4 == 0");
+  const int all_flags = MML_SCATTER_DET_CLEAR_MARKS | MML_SCATTER_DET_AMAX_SUPPLIED | MML_SCATTER_DET_DEFER_TOTALS;
+  MML_REQUIRE((flags & ~all_flags) == 0, "mml_scatter_bwd_det: unknown flag bits 0x%x", flags & ~all_flags);
+  const bool defer = (flags & MML_SCATTER_DET_DEFER_TOTALS) != 0;
+  const int clear_marks = flags & MML_SCATTER_DET_CLEAR_MARKS;
+  MML_REQUIRE(!(defer && clear_marks), "mml_scatter_bwd_det: deferred totals are found through the marks: "
+              "MML_SCATTER_DET_DEFER_TOTALS excludes MML_SCATTER_DET_CLEAR_MARKS");
   if (B == 0 || F == 0) return MML_OK;
   hipStream_t st = to_stream(stream);
-  // the launch-wide magnitude of dOut (a maximum does not depend on the order either)
-  rc = mml_amax_reset(amax_slot, 1, stream);
-  if (rc) return rc;
-  mml_amax_desc ad{};
-  ad.x = dOut; ad.rows = B; ad.ld = ldo; ad.cols = F * E; ad.slot = amax_slot;
-  rc = mml_amax_batch(&ad, 1, stream);
-  if (rc) return rc;
+  if (!(flags & MML_SCATTER_DET_AMAX_SUPPLIED)) {
+    // the launch-wide magnitude of dOut (a maximum does not depend on the order either)
+    rc = mml_amax_reset(amax_slot, 1, stream);
+    if (rc) return rc;
+    mml_amax_desc ad{};
+    ad.x = dOut; ad.rows = B; ad.ld = ldo; ad.cols = F * E; ad.slot = amax_slot;
+    rc = mml_amax_batch(&ad, 1, stream);
+    if (rc) return rc;
+  }
   ScatterArgs a{};
   DetFinalArgs fa{};
   for (int f = 0; f < F; ++f) {
@@ -1138,17 +1154,14 @@ extern "C" int mml_scatter_bwd_det(float* const* grad_tables, const int64_t* voc
   }
   a.X = X; a.ldX = ldX; a.B = B; a.dOut = dOut; a.ldo = ldo; a.F = F; a.E = E; a.status = status;
   a.amax_dout = amax_slot;
-  // headroom: a row may receive all B addends at the launch-wide maximum: 24 significand bits + shift + log2(B) < 63
-  int lg = 1;
-  while (((int64_t)1 << lg) < B) ++lg;
-  int shift = 62 - 24 - lg;
-  shift = shift > 28 ? 28 : (shift < 4 ? 4 : shift);
+  const int shift = mml_scatter_det_shift(B);
   a.fix_shift = shift;
   set_marks(a, ft, row_marks);
   if (E == 8) rc = launch_fold<1024, 8, 1024, true>(ft, a, st, "mml_scatter_bwd_det");
   else if (E == 4) rc = launch_fold<1024, 4, 512, true>(ft, a, st, "mml_scatter_bwd_det");
   else rc = launch_fold<512, 16, 1024, true>(ft, a, st, "mml_scatter_bwd_det");
   if (rc) return rc < 0 ? rc : MML_ERR_UNSUPPORTED;
+  if (defer) return MML_OK;  // (mml_opt_step_dense converts the marked rows' totals: mml_opt_tensor.acc64)
   int total = 0;
   for (int f = 0; f < F; ++f) {
     fa.markbase[f] = a.markbase[f];

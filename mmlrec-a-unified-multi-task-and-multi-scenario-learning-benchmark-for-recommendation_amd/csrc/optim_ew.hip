@@ -3,6 +3,7 @@
 // STAR (model/utils.py:214-218) and PepNet (model/pepnet.py:31-32, :72-78, :139-140).
 // All of these are pure streaming kernels: 16-byte accesses per lane, grid-stride, HBM-bound.
 #include "common.hpp"
+#include "fold_fixed.hpp"
 
 #include <stdlib.h>
 
@@ -19,6 +20,7 @@ struct OptLaunch {
   int32_t blk0[MML_MAX_OPT_TENSORS + 1];
   int32_t prop;
 };
+static_assert(sizeof(OptLaunch) <= 4096, "OptLaunch travels by value: the kernel-argument block holds 4 KB");
 
 struct StepConsts {
   float step_size;  // Adam: lr / (1 - beta1^t)
@@ -83,7 +85,9 @@ __device__ __forceinline__ float reg_grad(float g, float p, float l1, float l2) 
 // kernel: 170 VGPRs, two waves per SIMD -- and the plain loop, which needs 40, ran at that occupancy too):
 //   0 plain grid-stride loop (also the remainder loop of every other form)   1 two chunks per iteration
 //   2 split update, untouched rows, U chunks in flight per thread            3 marked gradients, U chunks in flight
-enum { OPT_PLAIN = 0, OPT_UNROLL2 = 1, OPT_SKIP_U = 2, OPT_MARK_U = 3 };
+//   4 marked gradients whose rows' 64-bit totals of the deterministic scatter are still in mml_opt_tensor.acc64 (the
+//     scatter's second launch folded in): as 3, plus 32 bytes of totals read, converted and zeroed per marked chunk
+enum { OPT_PLAIN = 0, OPT_UNROLL2 = 1, OPT_SKIP_U = 2, OPT_MARK_U = 3, OPT_MARK_ACC_U = 4 };
 template <bool STREAM, int PATH, int U>
 __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
   // (workgroup-uniform: scalar loads and compares)
@@ -143,6 +147,28 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
     // of ONE wave (row_elems / 4 is a power of two <= 64, chunk index = lane + multiple of 64): every lane of the row
     // reads the byte in the same wave-instruction, before the first chunk's lane clears it further down.
     uint8_t* const gm = T.grad_marks;
+    // deferred totals (PATH 4 only; a tensor of the launch without them is a plain marked tensor): chunk c of the table
+    // = totals [4c, 4c + 4) = two 16-byte pieces; the unit's exponent as scatter_det_finalize_kernel takes it
+    typedef long long l2 __attribute__((ext_vector_type(2)));
+    l2* const A64 = PATH == OPT_MARK_ACC_U ? reinterpret_cast<l2*>(T.acc64) : nullptr;
+    const l2 lzero = {0, 0};
+    int emax = 1;
+    if (PATH == OPT_MARK_ACC_U && A64) {
+      uint32_t m = 0;
+      for (int w = 0; w < MML_AMAX_WORDS; ++w) m = T.acc_amax[w] > m ? T.acc_amax[w] : m;
+      emax = (int)(m >> 23);
+      emax = emax < 1 ? 1 : (emax > 254 ? 254 : emax);
+    }
+    // g + from_fixed(total) for the non-zero totals (the expression of the finalize launch's dst[e] += ...), the totals
+    // it used zeroed again
+    auto add_totals = [&](f4& g, const l2& t0, const l2& t1, int64_t c) {
+      if (t0.x) g.x += from_fixed(t0.x, emax, T.acc_shift);
+      if (t0.y) g.y += from_fixed(t0.y, emax, T.acc_shift);
+      if (t1.x) g.z += from_fixed(t1.x, emax, T.acc_shift);
+      if (t1.y) g.w += from_fixed(t1.y, emax, T.acc_shift);
+      if (t0.x | t0.y) A64[2 * c] = lzero;
+      if (t1.x | t1.y) A64[2 * c + 1] = lzero;
+    };
     int64_t i = tid;
     if (PATH == OPT_UNROLL2 && !skip && !gm) {
       for (; i + stride < n4; i += 2 * stride) {  // eight 16-byte loads in flight per thread
@@ -228,6 +254,42 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
         }
       }
     }
+    if (PATH == OPT_MARK_ACC_U && gm && !skip) {
+      // the marked form above with the totals of the live chunks in flight beside the gradient (2 more 16-byte loads)
+      for (; i + (U - 1) * stride < n4; i += U * stride) {
+        f4 p[U], a[U], b[U], g[U];
+        l2 t0[U], t1[U];
+        bool lv[U];
+        int64_t rw[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          rw[k] = row_of(i + k * stride);
+          lv[k] = gm[rw[k]] != 0;
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          const int64_t j = i + k * stride;
+          p[k] = ld(P + j);
+          a[k] = S1 ? ld(S1 + j) : zero;
+          b[k] = S2 ? ld(S2 + j) : zero;
+          g[k] = (zg || !lv[k]) ? zero : ld(G + j);
+          t0[k] = (A64 && lv[k]) ? A64[2 * j] : lzero;
+          t1[k] = (A64 && lv[k]) ? A64[2 * j + 1] : lzero;
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          const int64_t j = i + k * stride;
+          f4 gs = g[k];
+          if (A64 && lv[k]) add_totals(gs, t0[k], t1[k], j);
+          one(p[k], gs, a[k], b[k]);
+          st(P + j, p[k]);
+          if (S1) st(S1 + j, a[k]);
+          if (S2) st(S2 + j, b[k]);
+          if (h.zero_grad && (g[k].x != 0.f || g[k].y != 0.f || g[k].z != 0.f || g[k].w != 0.f)) G[j] = zero;
+          if (lv[k] && (j << 2) == rw[k] * re) gm[rw[k]] = 0;
+        }
+      }
+    }
     for (; i < n4; i += stride) {
       if (skip && skipped(i)) continue;
       bool live = true;
@@ -240,7 +302,13 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
       const f4 g = (zg || !live) ? zero : ld(G + i);
       f4 a = S1 ? ld(S1 + i) : zero;
       f4 b = S2 ? ld(S2 + i) : zero;
-      one(p, g, a, b);
+      if (PATH == OPT_MARK_ACC_U) {  // (the remainder of the form above: the other forms keep their loop as it was)
+        f4 gs = g;
+        if (A64 && gm && live) add_totals(gs, A64[2 * i], A64[2 * i + 1], i);
+        one(p, gs, a, b);
+      } else {
+        one(p, g, a, b);
+      }
       st(P + i, p);
       if (S1) st(S1 + i, a);
       if (S2) st(S2 + i, b);
@@ -823,6 +891,12 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
                                    aligned16(t.param)),
                   "mml_opt_step_dense: tensor %d: skip_rows needs row_elems %% 4 == 0 dividing n and a 16-byte aligned "
                   "parameter (16-byte chunks must lie inside one row)", i);
+      if (t.acc64) {
+        MML_REQUIRE(t.grad_marks && !t.skip_rows && t.acc_amax && aligned16(t.acc64) && t.acc_shift >= 4 &&
+                        t.acc_shift <= 28,
+                    "mml_opt_step_dense: tensor %d: acc64 (deferred totals of mml_scatter_bwd_det) needs grad_marks, no "
+                    "skip_rows, a 16-byte aligned int64 array, acc_amax and acc_shift = mml_scatter_det_shift(B)", i);
+      }
       if (t.grad_marks) {
         const int cpr = t.row_elems / 4;
         MML_REQUIRE(t.row_elems > 0 && t.row_elems % 4 == 0 && cpr <= 64 && (cpr & (cpr - 1)) == 0 &&
@@ -851,8 +925,9 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
     int64_t nmax = 0;
     for (int k = 0; k < L.n; ++k) nmax = L.t[k].n > nmax ? L.t[k].n : nmax;
     // the loop form (see opt_dense_kernel): decided for the launch, so every tensor of it must qualify
-    bool all_gm = true, all_skip = true, none = true;
+    bool all_gm = true, all_skip = true, none = true, any_acc = false;
     for (int k = 0; k < L.n; ++k) {
+      any_acc = any_acc || L.t[k].acc64;
       all_gm = all_gm && L.t[k].grad_marks && !L.t[k].skip_rows;
       all_skip = all_skip && L.t[k].skip_rows;
       none = none && !L.t[k].grad_marks && !L.t[k].skip_rows;
@@ -860,6 +935,7 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
     // Round 6: a model's tables in ONE marked streaming launch (AE-30: 4 huge + 26 small; the small ones were a second
     // launch of the flat kernel, 31-34 us behind the stream): workgroups dealt in proportion to the tensors' sizes.
     const bool many = L.n > 4 && all_gm;
+    MML_REQUIRE(!any_acc || all_gm, "mml_opt_step_dense: a launch with acc64 tensors takes grad_marks on every tensor");
     if (total >= ((int64_t)1 << 24) && (L.n <= 4 || many)) {
       int64_t bx = cdiv(cdiv(nmax, 4), 256);
       if (bx > 256 * 8) bx = 256 * 8;
@@ -896,7 +972,10 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
         u_mark = e ? atoi(e) : 2;
       }
       hipStream_t st = to_stream(stream);
-      if ((L.variant & 4) && all_gm) {
+      if (any_acc) {  // (capped grid or not: the totals are only read by this form)
+        if (u_mark == 4) MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_ACC_U, 4>), grid, dim3(256), 0, st, L);
+        else MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_ACC_U, 2>), grid, dim3(256), 0, st, L);
+      } else if ((L.variant & 4) && all_gm) {
         if (u_mark == 4) MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_U, 4>), grid, dim3(256), 0, st, L);
         else if (u_mark == 8) MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_U, 8>), grid, dim3(256), 0, st, L);
         else MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_U, 2>), grid, dim3(256), 0, st, L);
@@ -909,8 +988,8 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
       }
     } else {
       for (int k = 0; k < L.n; ++k)
-        MML_REQUIRE(!L.t[k].grad_marks, "mml_opt_step_dense: grad_marks is only honoured by the streaming launch "
-                    "(>= 2^24 parameters in <= 4 tensors)");
+        MML_REQUIRE(!L.t[k].grad_marks, "mml_opt_step_dense: grad_marks (and acc64) is only honoured by the streaming "
+                    "launch (>= 2^24 parameters in <= 4 tensors, or any number of marked tensors)");
       int64_t bx = cdiv(chunks, 256);
       if (bx > 256 * 8) bx = 256 * 8;
       if (hyper->max_blocks > 0 && bx > hyper->max_blocks) bx = hyper->max_blocks;

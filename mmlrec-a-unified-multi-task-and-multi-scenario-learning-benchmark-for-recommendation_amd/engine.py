@@ -937,10 +937,12 @@ def scatter_symbol(E):
 def _opt_dense_symbol(numel, ntensors, form=0):
     """Kernel symbol of a dense optimizer launch (csrc/optim_ew.hip: mml_opt_step_dense's choice).  form: the loop form
     of the streaming kernel -- 0 plain, 1 two chunks per iteration (MMLREC_OPT_VARIANT bit 1), 2 untouched rows of the
-    split update under a capped grid, 3 marked gradients under a capped grid."""
-    if not (numel >= (1 << 24) and (ntensors <= 4 or form == 3)):
+    split update under a capped grid, 3 marked gradients under a capped grid, 4 marked gradients plus the deferred totals
+    of the deterministic scatter (any grid)."""
+    if not (numel >= (1 << 24) and (ntensors <= 4 or form in (3, 4))):
         return "opt_flat_kernel"
-    u = {0: 1, 1: 1, 2: 4, 3: int(os.environ.get("MMLREC_OPT_U", "2"))}[form]
+    u = {0: 1, 1: 1, 2: 4, 3: int(os.environ.get("MMLREC_OPT_U", "2")),
+         4: 4 if os.environ.get("MMLREC_OPT_U") == "4" else 2}[form]
     return "opt_dense_kernel<true, %d, %d>" % (form, u)
 
 
@@ -975,6 +977,9 @@ class GatherOp(Op):
         # True: the backward is mml_scatter_bwd_det -- order-independent integer fixed-point sums, bitwise repeatable
         # (BaseModel.scatter_mode = "deterministic"); needs store.ensure_det(tables)
         self.deterministic = None
+        # set by bwd_calls when the deterministic scatter leaves its 64-bit row totals to the table optimizer
+        # (MML_SCATTER_DET_DEFER_TOTALS): dict(slot, shift) that Optimizer.calls_split hands to mml_opt_tensor
+        self.det_deferred = None
 
     def outputs(self):
         return [self.out]
@@ -1052,17 +1057,35 @@ class GatherOp(Op):
                     bytes=float(plan.B) * F * (4 + 12 * E), tail=True)  # idx + grad read + row RMW
         det = self.deterministic
         if det is not None:
-            # deterministic scatter: 64-bit integer row totals, then fp32 (two launches + the magnitude of d(dnn_input));
+            # deterministic scatter: 64-bit integer row totals, then fp32 (two launches + the magnitude of d(dnn_input),
+            # or the fold alone: MML_SCATTER_DET_AMAX_SUPPLIED / _DEFER_TOTALS below);
             # the marks feed the marked dense update (left set) or the touched-row list (compaction, which clears them)
             acc = ops._ptr_array(det["acc64"])
             marks = self.grad_marks if self.grad_marks is not None else (sr.marks if sr is not None else det["marks"])
             keep_marks = self.grad_marks is not None or sr is not None
             slot = det["slot"]
             plan.keep += [acc]
+            flags = 0 if keep_marks else L.SCATTER_DET_CLEAR_MARKS
+            fused = os.environ.get("MMLREC_DET_FUSED", "1") != "0"  # (0: the call measures and finalizes for itself)
+            g = self.out
+            # the magnitude of d(dnn_input) from the launch that wrote it: the one writer raised g.gamax (a slot of the
+            # pool the step's opening mml_amax_reset zeroes) with the exact maximum over the [B, F * E] region read here
+            if (fused and self.nd == 0 and getattr(g, "gamax_exact", False) and g.gamax is not None and
+                    g.written == 1 and g.gamax_writers == 1 and g.n == F * E):
+                slot = g.gamax
+                flags |= L.SCATTER_DET_AMAX_SUPPLIED
+            # the totals stay in acc64 for the ONE marked streaming launch of the dense table optimizer
+            self.det_deferred = None
+            if (fused and type(self) is GatherOp and self.grad_marks is not None and sr is None and
+                    len(self.tables) <= L.MAX_OPT_TENSORS and
+                    sum(t.data.numel() for t in self.tables) >= (1 << 24)):
+                flags |= L.SCATTER_DET_DEFER_TOTALS
+                self.det_deferred = dict(slot=slot, shift=int(lib.mml_scatter_det_shift(plan.B)))
             calls = [(lib.mml_scatter_bwd_det, (gt, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), plan.B,
                                                 self.out.grad.data_ptr(), ops._ld(self.out.grad), acc, slot.data_ptr(),
-                                                marks.data_ptr(), 0 if keep_marks else 1, plan.status.data_ptr()),
-                      dict(meta, kernel="scatter_fold_kernel<det>"))]
+                                                marks.data_ptr(), flags, plan.status.data_ptr()),
+                      dict(meta, kernel="scatter_fold_kernel<det>", det_flags=flags,
+                           ptrs=[a.data_ptr() for a in det["acc64"]]))]
             if sr is not None:
                 calls.append((lib.mml_rows_compact, (seen, vocab, rb, F, sr.touched.data_ptr(), sr.count.data_ptr(),
                                                      sr.touched.numel(), sr.marks.data_ptr()),
@@ -1562,10 +1585,19 @@ class LinearGroupOp(Op):
                 gp = [plan.weight_planes(q, ops.PLANES_COLS, ch, padded=bool(padded)) for q in ch]
                 if any(pl is None for pl, _ in gp):
                     gp = [(None, None)] * len(ch)
+                # a launch of the shape csrc/gemm_os.hip serves (mml_gemm_os_try_dgrad: its conditions) stores exactly
+                # x.grad's [B, n] region and raises the slot with the exact maximum of what it stored: GatherOp's
+                # deterministic scatter may take its fixed-point unit from it (tests/test_scatter_det_fused_gpu.py)
+                exact = (out_slot is not None and len(chunks) == 1 and not fuse and not padded and not gc and
+                         not x.kpad and plan.B >= 16384 and 192 <= x.n <= 256 and x.n % 4 == 0 and len(ch) >= 2 and
+                         all(pl is not None for pl, _ in gp) and not any(q.get("w_kn", 0) for q in ch) and
+                         all(q["out"].n % 16 == 0 for q in ch) and sum(q["out"].n for q in ch) >= 256 and
+                         x.grad.dtype == torch.float32 and x.grad.stride(0) % 4 == 0 and
+                         os.environ.get("MMLREC_GEMM_OS", "1")[:1] != "0")
                 waves[ci].append(dict(dA=cut(_padded_view(x.grad, x.kpad) if padded else x.grad),
                                       Y=x.buf if fuse else None, act=x.act if fuse else L.ACT_NONE,
                                       mask=x.mask if (fuse and x.act == L.ACT_RELU) else None,
-                                      accumulate=acc, amax_out=out_slot,
+                                      accumulate=acc, amax_out=out_slot, exact_amax_of=x if exact else None,
                                       srcs=[(q["out"].grad, cut(q["Wp"] if padded else q["W"].data), q.get("w_kn", 0),
                                              q["amax_dc"], q["amax_w"]) + ((pl, kx) if pl is not None else ())
                                             for q, (pl, kx) in zip(ch, gp)]))
@@ -1574,6 +1606,8 @@ class LinearGroupOp(Op):
         for dg in waves:
             descs = ops.make_dgrad_descs(dg)
             plan.keep.append(descs)
+            if len(dg) == 1 and dg[0].get("exact_amax_of") is not None:  # (that kernel takes one problem per launch)
+                dg[0]["exact_amax_of"].gamax_exact = True
             kn = dg[0]["srcs"][0][2]
             meta = dict(kernel=_gemm_symbol(True, bool(kn), [q["dA"].shape[1] for q in dg], 1,
                                             kreds=[sr[0].shape[1] for q in dg for sr in q["srcs"]],
@@ -2610,7 +2644,8 @@ class ParamStore:
 
     def ensure_det(self, tables):
         """Buffers of the deterministic scatter for `tables` (a gather's field order): int64 [V, E] totals per table (kept
-        all zero between steps by the scatter's second launch), a mark map of its own and a magnitude slot."""
+        all zero between steps by the scatter's second launch, or by the table optimizer that takes the totals over), a
+        mark map of its own and a magnitude slot."""
         key = tuple(t.data.data_ptr() for t in tables)
         if getattr(self, "_det_key", None) != key:
             uniq = {}
@@ -2797,25 +2832,41 @@ class Optimizer:
                 one_launch = (big and small and cap > 0 and len(tabs) <= L.MAX_OPT_TENSORS and not split_dense and
                               all(id(t) in marks_of for t in tabs) and
                               os.environ.get("MMLREC_OPT_ONE_LAUNCH", "0") == "1")
+                # Deterministic scatter with deferred totals (GatherOp.det_deferred): the scatter's second launch is
+                # folded into this one -- every table in ONE marked streaming launch that adds the marked rows' 64-bit
+                # totals to the gradient it reads (mml_opt_tensor.acc64) -- so the small tables cannot go to the flat
+                # kernel, which reads neither marks nor totals
+                dd = getattr(gop, "det_deferred", None)
+                acc_of = {}
+                if dd is not None:
+                    if (split_dense or {id(t) for t in tabs} != {id(t) for t in gop.tables} or
+                            not all(id(t) in marks_of for t in tabs)):
+                        raise L.MMLError("the deterministic scatter deferred its totals to a marked dense update of "
+                                         "exactly its tables")
+                    acc_of = {id(t): a for t, a in zip(gop.tables, gop.deterministic["acc64"])}
+                    one_launch = True
                 if one_launch:
                     big = small + big   # (the small tables' workgroups first: they start with the launch)
                     groups = [big]
                 for grp in groups:
                     marked = grp is big and all(id(tabs[i]) in marks_of for i in grp)
                     arr = ops.make_opt_tensors([(tabs[i].data, tabs[i].grad) + self.state[tnames[i]] +
-                                                (treg, seen_of.get(tnames[i]), marks_of[id(tabs[i])] if marked else None)
+                                                (treg, seen_of.get(tnames[i]), marks_of[id(tabs[i])] if marked else None,
+                                                 (acc_of[id(tabs[i])], dd["slot"], dd["shift"]) if dd else None)
                                                 for i in grp])
                     plan.keep.append(arr)
                     numel = sum(tabs[i].data.numel() for i in grp)
                     nbytes = float(per) * numel
                     v = int(os.environ.get("MMLREC_OPT_VARIANT", "0"))
-                    form = (3 if (cap > 0 and marked) else 2 if (cap > 0 and split_dense) else
+                    form = (4 if dd else 3 if (cap > 0 and marked) else 2 if (cap > 0 and split_dense) else
                             1 if (v & 2 and not marked and not split_dense) else 0)
                     if marked:  # g is read for the touched rows only (~1 %): count the mark bytes instead
                         nbytes += sum(tabs[i].data.shape[0] - 4.0 * tabs[i].data.numel() for i in grp)
-                    (early if split_dense else calls).append(
-                        (lib.mml_opt_step_dense, (arr, len(grp), C.byref(hz)),
-                         dict(kernel=_opt_dense_symbol(numel, len(grp), form), bytes=nbytes)))
+                    m = dict(kernel=_opt_dense_symbol(numel, len(grp), form), bytes=nbytes)
+                    if dd:  # (+ 32 bytes of totals read and zeroed per 16-byte chunk of a marked row; the buffers the
+                        # descriptors hide from trainer.fork_conflicts)
+                        m.update(det_acc64=True, ptrs=[dd["slot"].data_ptr()] + [a.data_ptr() for a in acc_of.values()])
+                    (early if split_dense else calls).append((lib.mml_opt_step_dense, (arr, len(grp), C.byref(hz)), m))
             if self.table_update != "dense_exact" or split_dense:
                 rows = st.rows
                 lazy = self.table_update == "lazy_exact"

@@ -312,9 +312,12 @@ def scatter_bwd(grad_tables, X, cols, d_out, seen=None, rowbase=None, touched=No
     L.check(rc, "mml_scatter_bwd")
 
 
-def scatter_bwd_det(grad_tables, X, cols, d_out, acc64, marks, amax_slot=None, clear_marks=True, status=None):
+def scatter_bwd_det(grad_tables, X, cols, d_out, acc64, marks, amax_slot=None, clear_marks=True, status=None,
+                    amax_supplied=False, defer_totals=False):
     """Deterministic scatter (mml_scatter_bwd_det): acc64 = per-table int64 [V, E] accumulators (all zero between calls),
-    marks = the byte map of marks_bytes(vocab).  Bitwise repeatable, independent of the order of the samples."""
+    marks = the byte map of marks_bytes(vocab).  Bitwise repeatable, independent of the order of the samples.
+    amax_supplied: amax_slot already holds the magnitude of d_out (no magnitude pass); defer_totals: the totals stay in
+    acc64 and the marks set, for opt_step_dense entries that carry (acc64, slot, scatter_det_shift(B))."""
     lib = L.load()
     _need_gpu(X, d_out, *grad_tables)
     F, E, B = len(grad_tables), grad_tables[0].shape[1], X.shape[0]
@@ -324,8 +327,15 @@ def scatter_bwd_det(grad_tables, X, cols, d_out, acc64, marks, amax_slot=None, c
         amax_slot = amax_slots(1, X.device)[0]
     rc = lib.mml_scatter_bwd_det(_ptr_array(grad_tables), vocab, col, F, E, X.data_ptr(), _ld(X), B, d_out.data_ptr(),
                                  _ld(d_out), _ptr_array(acc64), amax_slot.data_ptr(), marks.data_ptr(),
-                                 int(bool(clear_marks)), L.ptr(status), _stream())
+                                 (L.SCATTER_DET_CLEAR_MARKS if clear_marks else 0) |
+                                 (L.SCATTER_DET_AMAX_SUPPLIED if amax_supplied else 0) |
+                                 (L.SCATTER_DET_DEFER_TOTALS if defer_totals else 0), L.ptr(status), _stream())
     L.check(rc, "mml_scatter_bwd_det")
+
+
+def scatter_det_shift(B):
+    """log2 of the fixed-point scale the deterministic scatter uses for B samples (mml_opt_tensor.acc_shift)."""
+    return int(L.load().mml_scatter_det_shift(int(B)))
 
 
 def scatter_bwd_idx32(grad_tables, idx, d_out, seen=None, rowbase=None, touched=None, touched_count=None, status=None,
@@ -822,9 +832,10 @@ def make_hyper(kind, lr, step=1, step_dev=None, zero_grad=False, max_blocks=0):
 
 
 def make_opt_tensors(entries):
-    """entries: (param, grad, state1 or None, state2 or None[, (l1, l2)[, skip bitmap[, gradient marks]]]) with equal
-    element counts, contiguous.  A skip bitmap (int32 words, one bit per table row) turns the entry into the untouched-rows half of the
-    split dense table update (include/mmlrec.h: mml_opt_tensor.skip_rows)."""
+    """entries: (param, grad, state1 or None, state2 or None[, (l1, l2)[, skip bitmap[, gradient marks[, totals]]]]) with
+    equal element counts, contiguous.  A skip bitmap (int32 words, one bit per table row) turns the entry into the untouched-rows half of the
+    split dense table update (include/mmlrec.h: mml_opt_tensor.skip_rows).  totals = (acc64 tensor, magnitude slot,
+    scatter_det_shift(B)): the deferred row totals of the deterministic scatter (mml_opt_tensor.acc64)."""
     arr = (L.OptTensor * len(entries))()
     for d, ent in zip(arr, entries):
         p, g, s1, s2 = ent[:4]
@@ -834,6 +845,8 @@ def make_opt_tensors(entries):
             d.skip_rows, d.row_elems, d.zero_grads = ent[5].data_ptr(), p.shape[1], 1
         if len(ent) > 6 and ent[6] is not None:  # byte marks of the rows whose gradient is non-zero (uint8 view)
             d.grad_marks, d.row_elems = ent[6].data_ptr(), p.shape[1]
+        if len(ent) > 7 and ent[7] is not None:
+            d.acc64, d.acc_amax, d.acc_shift = ent[7][0].data_ptr(), ent[7][1].data_ptr(), int(ent[7][2])
     return arr
 
 

@@ -95,6 +95,10 @@ def fork_conflicts(side_calls, mid_calls, shared_scratch=()):
                 # batch of 65 536 rows is 0x10000 in BOTH lists -- stay below)
                 if isinstance(a, int) and not isinstance(a, bool) and a >= (1 << 32):
                     out.add(a)
+            # (buffers a call reads or writes through its descriptors and names in its meta: the 64-bit totals and the
+            # magnitude slot the deterministic scatter hands to the table optimizer)
+            if isinstance(c[-1], dict):
+                out.update(int(p) for p in c[-1].get("ptrs", ()))
         return out
     a, b = ptrs(side_calls), ptrs(mid_calls)
     scratch = {int(x) for x in shared_scratch if x}
