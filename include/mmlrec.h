@@ -920,6 +920,56 @@ int mml_bn_fwd(const float* z, int64_t ldz, const float* gamma, const float* bet
 int mml_bn_bwd(const float* dy, int64_t lddy, const float* z, int64_t ldz, const float* gamma, const float* mean,
                const float* rstd, float* dz, int64_t lddz, float* dgamma, float* dbeta, int32_t accumulate, int64_t B,
                int32_t n, void* workspace, int64_t workspace_bytes, mml_stream_t stream);
+/* PReLU with one learnable slope per layer (model/utils.py:25-26 `nn.PReLU()`; DNN applies fc -> bn -> activation ->
+ * dropout, :153-159; STAR one activation per layer for every domain, model/star.py:29-31, :47-49).  torch's semantics:
+ *     forward : y  = z > 0 ? z  : alpha * z       (one fp32 multiply; z = +-0 takes the alpha * z branch)
+ *     backward: dz = z > 0 ? dy : alpha * dy,     dalpha = sum over the elements with z <= 0 of dy * z
+ * The backward reads z, not y: for alpha <= 0 the sign of y does not give the sign of z.
+ * ONE launch serves n independent items (`d` is a HOST array, 1 <= n <= mml_prelu_max_batch(), which is >= MML_MAX_GROUP).
+ * Item: z / y [rows, cols] with row pitches ldz / ldy >= cols; columns [cols, ld) are neither read nor written.  16-byte
+ * accesses when every pitch of the item is a multiple of 4 and every pointer 16-byte aligned, single elements otherwise.
+ * alpha is a DEVICE pointer read by the kernel when it runs (a replayed HIP graph sees what the optimizer wrote).
+ * amax_out (optional): an operand-magnitude slot (MML_AMAX_WORDS words) raised with the exact max |y| (forward) /
+ * max |dz| (backward, after accumulate_dz) of what the item stores -- mml_copy2d_desc.amax_out's contract.
+ * Backward: dz may be dy (each element is read before it is written); accumulate_dz != 0 adds to dz.  Items that name
+ * the same dalpha are summed into it in descriptor order (STAR: one slope, every domain's activations) and must agree on
+ * accumulate_dalpha (!= 0: added to the old value).  dalpha is a fixed-order reduction -- lane, wave, workgroup
+ * partials in the workspace (mml_prelu_workspace_bytes(n)), one ordered final sum in double -- with no float atomics:
+ * two launches on the same inputs give the same bits.
+ * MML_ERR_ARG: n < 1, n > mml_prelu_max_batch(), a null pointer (amax_out excepted), rows < 0, cols < 1, ld < cols,
+ * a workspace that is null or too small. */
+typedef struct mml_prelu_desc {
+  const float* z;
+  int64_t ldz;
+  float* y;
+  int64_t ldy;
+  int64_t rows;
+  int32_t cols;
+  int32_t pad_;
+  const float* alpha;
+  uint32_t* amax_out;
+} mml_prelu_desc;
+typedef struct mml_prelu_bwd_desc {
+  const float* dy;
+  int64_t lddy;
+  const float* z;
+  int64_t ldz;
+  float* dz;
+  int64_t lddz;
+  int64_t rows;
+  int32_t cols;
+  int32_t pad_;
+  const float* alpha;
+  float* dalpha;
+  int32_t accumulate_dz;
+  int32_t accumulate_dalpha;
+  uint32_t* amax_out;
+} mml_prelu_bwd_desc;
+int32_t mml_prelu_max_batch(void);
+int mml_prelu_batch_fwd(const mml_prelu_desc* d, int32_t n, mml_stream_t stream);
+int64_t mml_prelu_workspace_bytes(int32_t n);
+int mml_prelu_batch_bwd(const mml_prelu_bwd_desc* d, int32_t n, void* workspace, int64_t workspace_bytes,
+                        mml_stream_t stream);
 /* DomainBatchNorm (model/utils.py:553-636; STAR applies it after its first star layer when forward() is given a domain
  * mask, model/star.py:50-51).  gamma / beta are unregistered there, frozen at (1, 0).  Training mode normalises with
  * the statistics of the WHOLE batch for every domain (= mml_bn_fwd with gamma 1 / beta 0; the caller issues that) and

@@ -154,6 +154,17 @@ class Copy2dDesc(C.Structure):
                 ("accumulate", i32), ("amax_out", fp)]
 
 
+class PreluDesc(C.Structure):
+    _fields_ = [("z", fp), ("ldz", i64), ("y", fp), ("ldy", i64), ("rows", i64), ("cols", i32), ("pad_", i32),
+                ("alpha", fp), ("amax_out", fp)]
+
+
+class PreluBwdDesc(C.Structure):
+    _fields_ = [("dy", fp), ("lddy", i64), ("z", fp), ("ldz", i64), ("dz", fp), ("lddz", i64), ("rows", i64),
+                ("cols", i32), ("pad_", i32), ("alpha", fp), ("dalpha", fp), ("accumulate_dz", i32),
+                ("accumulate_dalpha", i32), ("amax_out", fp)]
+
+
 class SumProdDesc(C.Structure):
     _fields_ = [("out", fp), ("x", fp * 8), ("y", fp * 8), ("n", i64), ("n_terms", i32), ("accumulate", i32),
                 ("deriv_of", fp), ("act", i32), ("pad_", i32), ("amax_out", fp)]
@@ -247,6 +258,10 @@ _SIGS = {
     "mml_copy2d": (C.c_int, [fp, i64, fp, i64, i64, i32, i32, fp]),
     "mml_dropout": (C.c_int, [fp, i64, fp, i64, i64, i32, i64, C.c_float, C.c_uint64, C.c_uint32, fp, i32, i32, fp]),
     "mml_copy2d_batch": (C.c_int, [_PP(Copy2dDesc), i32, fp]),
+    "mml_prelu_max_batch": (i32, []),
+    "mml_prelu_batch_fwd": (C.c_int, [_PP(PreluDesc), i32, fp]),
+    "mml_prelu_workspace_bytes": (i64, [i32]),
+    "mml_prelu_batch_bwd": (C.c_int, [_PP(PreluBwdDesc), i32, fp, i64, fp]),
     "mml_auc_segments": (C.c_int, [fp, i64, fp, i64, i64, i32, i32, fp, fp]),
     "mml_bn_workspace_bytes": (C.c_int64, [i64, i32]),
     "mml_bn_fwd": (C.c_int, [fp, i64, fp, fp, fp, fp, fp, fp, fp, fp, i64, i64, i32, i32, i32, C.c_float, C.c_float, fp,

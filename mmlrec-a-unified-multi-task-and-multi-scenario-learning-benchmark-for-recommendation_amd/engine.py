@@ -19,6 +19,10 @@ from . import ops
 
 ACT = {"none": L.ACT_NONE, None: L.ACT_NONE, "linear": L.ACT_NONE, "relu": L.ACT_RELU, "sigmoid": L.ACT_SIGMOID,
        "sigmoid2": L.ACT_SIGMOID2}
+# PReLU is not an MML_ACT_* code (no GEMM epilogue applies it): the layer's Linear / BatchNorm runs with ACT_NONE and a
+# PReluBatchOp follows.  The marker never reaches a kernel descriptor.
+ACT_PRELU = 100
+ACT["prelu"] = ACT_PRELU
 
 
 class PVal:
@@ -2020,6 +2024,73 @@ class DropoutOp(Op):
             return []
         g = plan.grad_of(self.x)
         return [self._call(plan, self.y.grad, g, _claim(self.x))]
+
+
+class PReluBatchOp(Op):
+    """nn.PReLU() of one layer depth of sibling stacks (reference model/utils.py:25-26, :156-157; STAR model/star.py:47-49):
+    y_j = z_j > 0 ? z_j : a_j * z_j for every stack in ONE launch each way (mml_prelu_batch_fwd / _bwd).
+    items: (z Val, y Val, alpha PVal); both values carry ACT_NONE -- downstream, y is the output of a `linear` layer.  The
+    backward reads z (kept: for a slope <= 0 the sign of y does not give the sign of z), writes dL/dz once and claims the
+    slope's gradient like BatchNorm's gamma; items that share a slope (STAR: one per layer, every domain) are summed by the
+    launch.  Where the plan has a magnitude pool the launches raise the slots of y and of dL/dz themselves."""
+
+    def __init__(self, items):
+        self.items = list(items)
+        for z, y, _ in self.items:
+            if z.act != L.ACT_NONE or y.act != L.ACT_NONE or z.is16 or y.is16 or z.n != y.n:
+                raise L.MMLError("PReluBatchOp: fp32 values of one width without an activation of their own")
+
+    def inputs(self):
+        return [z for z, _, _ in self.items]
+
+    def outputs(self):
+        return [y for _, y, _ in self.items]
+
+    def fwd_calls(self, plan):
+        rows = []
+        for z, y, a in self.items:
+            if y.amax is None:
+                y.amax = plan.new_amax()
+            rows.append(dict(z=z.buf, y=y.buf, alpha=a.data, amax=y.amax))
+        calls = []
+        for ch in ops.prelu_chunks(rows):
+            arr = ops.make_prelu_descs(ch)
+            plan.keep.append(arr)
+            calls.append((L.load().mml_prelu_batch_fwd, (arr, len(ch)),
+                          dict(kernel="prelu_fwd_kernel", bytes=8.0 * sum(r["z"].numel() for r in ch))))
+        return calls
+
+    def bwd_calls(self, plan):
+        rows, acc_da = [], {}
+        for z, y, a in self.items:
+            if y.grad is None or not (z.needs_grad or a.needs_grad):
+                continue
+            if y.grad.dtype != torch.float32:
+                raise L.MMLError(f"PReLU output {y.name!r}: its gradient must be fp32")
+            g = plan.grad_of(z)
+            acc = _claim(z)
+            if id(a) not in acc_da:  # (later items of the slope: the launch sums them behind the first)
+                acc_da[id(a)] = _claim(a)
+            slot = None  # magnitude of the gradient as stored (tracked like a dgrad GEMM's amax_out)
+            if plan.amax_pool is not None:
+                if z.gamax is None:
+                    z.gamax = plan.new_amax()
+                if z.gamax_writers == z.written - 1:
+                    z.gamax_writers += 1
+                    slot = z.gamax
+            rows.append(dict(dy=y.grad, z=z.buf, dz=g, alpha=a.data, dalpha=a.grad, acc_dz=acc,
+                             acc_dalpha=acc_da[id(a)], amax=slot))
+        calls, seen = [], set()
+        for ch in ops.prelu_chunks(rows):
+            arr = ops.make_prelu_bwd_descs(ch, seen)
+            seen.update(d.dalpha for d in arr)
+            nbytes = int(L.load().mml_prelu_workspace_bytes(len(ch)))
+            ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=plan.device)
+            plan.keep += [arr, ws]
+            calls.append((L.load().mml_prelu_batch_bwd, (arr, len(ch), ws.data_ptr(), ws.numel()),
+                          dict(kernel="prelu_bwd_kernel", bytes=sum((16.0 if r["acc_dz"] else 12.0) * r["z"].numel()
+                                                                    for r in ch))))
+        return calls
 
 
 def dropout_site(name):

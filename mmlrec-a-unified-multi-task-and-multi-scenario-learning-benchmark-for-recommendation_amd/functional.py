@@ -36,6 +36,32 @@ def linear_act(x, W, b=None, act=L.ACT_NONE):
     return _LinearAct.apply(x.float(), W, b, int(act))
 
 
+class _PReLU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, alpha):
+        y = torch.empty_like(z)
+        ops.prelu_fwd([dict(z=z, y=y, alpha=alpha)])
+        ctx.save_for_backward(z, alpha)  # (z, not y: for alpha <= 0 the sign of y does not give the sign of z)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, alpha = ctx.saved_tensors
+        dz, da = torch.empty_like(z), torch.empty_like(alpha)
+        ops.prelu_bwd([dict(dy=dy.contiguous(), z=z, dz=dz, alpha=alpha, dalpha=da)])
+        return dz, da
+
+
+def prelu(z, alpha):
+    """PReLU with ONE slope (nn.PReLU()'s weight, a one-element tensor): z > 0 ? z : alpha * z on a [B, n] value,
+    differentiable in both (K: mml_prelu_batch_fwd / _bwd; torch.nn.functional.prelu's semantics)."""
+    if not z.is_cuda:
+        raise L.MMLError("mmlrec_amd.functional needs CUDA(HIP) tensors; there is no CPU fallback")
+    if z.dim() != 2 or alpha.numel() != 1:
+        raise L.MMLError("functional.prelu: a [B, n] value and a one-element slope")
+    return _PReLU.apply(z.float().contiguous(), alpha)
+
+
 class _PooledDnnInput(torch.autograd.Function):
     @staticmethod
     def forward(ctx, X, layout, status, *tables):

@@ -15,7 +15,7 @@ import torch.nn as nn
 
 from .. import engine as E
 from .basemodel import BaseModel
-from .utils import DNN, PredictionLayer, activation_code
+from .utils import DNN, PredictionLayer, activation_code, refuse_prelu
 
 
 class APGLayer(nn.Module):
@@ -28,6 +28,7 @@ class APGLayer(nn.Module):
         if not use_uv_shared or use_mf_p or inner_activation is not None or generate_activation is not None:
             raise NotImplementedError("APGLayer options outside the configuration the reference's APG model builds")
         self.input_dim, self.output_dim = input_dim, output_dim
+        refuse_prelu(activation, "APGLayer (its activation follows weights generated per sample)")
         self.act_code = activation_code(activation)
         min_dim = min(int(input_dim), int(output_dim))
         self.p_dim = math.ceil(float(min_dim) / float(mf_p))

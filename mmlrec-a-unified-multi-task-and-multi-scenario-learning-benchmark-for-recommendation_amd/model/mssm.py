@@ -12,7 +12,7 @@ import torch.nn as nn
 from .basemodel import BaseModel
 from .snr_trans import SNR_trans
 from .towers import build_tower_modules
-from .utils import DNN
+from .utils import DNN, refuse_prelu
 
 
 class gate(nn.Module):
@@ -49,6 +49,8 @@ class MSSM(SNR_trans):
         if self.num_experts <= 1:
             raise ValueError("num_experts must be greater than 1")
         act, bn = mc.get("dnn_activation", "relu"), mc.get("dnn_use_bn", False)
+        # (reference model/mssm.py:25: every gate builds activation_layer(dnn_activation) -- a slope it never applies)
+        refuse_prelu(act, "the routing `gate` module of MSSM")
         drop = mc.get("dnn_dropout", 0)  # experts and towers (reference model/mssm.py:76, :89, :127)
         units, Ne, T = self.expert_dnn_hidden_units, self.num_experts, self.num_tasks
         self.mssm = nn.ModuleDict()

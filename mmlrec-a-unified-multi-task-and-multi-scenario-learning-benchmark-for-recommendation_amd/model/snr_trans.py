@@ -13,7 +13,7 @@ from .. import _lib as L
 from .. import engine as E
 from .basemodel import BaseModel
 from .towers import build_tower_modules, emit_towers
-from .utils import DNN, blocks_out_act, dnn_options, emit_blocks_into
+from .utils import DNN, blocks_out_act, dnn_options, emit_blocks_into, refuse_prelu
 
 
 class gate(nn.Module):  # (lower-case class name of the reference: it shows in nothing but repr)
@@ -48,6 +48,8 @@ class SNR_trans(BaseModel):
         if self.num_experts <= 1:
             raise ValueError("num_experts must be greater than 1")
         l2 = mc.get("l2_reg_dnn", 0)
+        # (reference model/snr_trans.py:25: every gate builds activation_layer(dnn_activation) -- a slope it never applies)
+        refuse_prelu(mc.get("dnn_activation", "relu"), "the routing `gate` module of SNR_trans")
         opts = dnn_options(mc, init_std, device)
         units, Ne, T = self.expert_dnn_hidden_units, self.num_experts, self.num_tasks
         self.trans = nn.ModuleDict()

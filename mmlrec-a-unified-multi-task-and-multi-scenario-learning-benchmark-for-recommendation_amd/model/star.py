@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from .. import engine as E
 from .basemodel import BaseModel
-from .utils import DomainBatchNorm, PredictionLayer, SharedSpecificLinear, activation_code
+from .utils import DomainBatchNorm, PredictionLayer, SharedSpecificLinear, activation_code, value_act
 
 
 class STAR(BaseModel):
@@ -33,6 +33,8 @@ class STAR(BaseModel):
         self.linears = nn.ModuleList([SharedSpecificLinear(hidden_units[i], hidden_units[i + 1], T,
                                                            use_shared=use_shared, device=device)
                                       for i in range(len(hidden_units) - 1)])
+        if self.act_code == E.ACT_PRELU:  # one slope per LAYER, applied to every domain's branch (reference :29-31, :49)
+            self.activation_layers = nn.ModuleList([nn.PReLU() for _ in range(len(hidden_units) - 1)])
         if self.dnn_use_bn:
             self.domain_bn = DomainBatchNorm(num_features=hidden_units[1], num_domains=T, device=device)
         self.final_layers = nn.ModuleList([SharedSpecificLinear(hidden_units[-1], 1, T, use_shared=use_shared,
@@ -81,14 +83,21 @@ class STAR(BaseModel):
                for j in range(nl) for i in range(T)}
         eff_final = [self._star_params(plan, store, f"final_layers.{i}", self.final_layers[i], i) for i in range(T)]
         plan.add(E.SumProdBatchOp(self._derived))
+        prelu = self.act_code == E.ACT_PRELU
         for j in range(nl):
             probs = []
             for i in range(T):
                 weff, beff = eff[(j, i)]
-                o = plan.val(self.dnn_hidden_units[j], act=self.act_code, name=f"star.{j}.{i}")
+                o = plan.val(self.dnn_hidden_units[j], act=value_act(self.act_code),
+                             name=f"star.{j}.{i}" + (".z" if prelu else ""))
                 probs.append(dict(x=hs[i], W=weff, b=beff, out=o, w_kn=1))
             plan.add(E.LinearGroupOp(probs))
             hs = [q["out"] for q in probs]
+            if prelu:  # ONE launch each way for the T branches; the backward sums their slope gradients (shared dalpha)
+                a = store.pvals[f"activation_layers.{j}.weight"]
+                ys = [plan.val(self.dnn_hidden_units[j], name=f"star.{j}.{i}") for i in range(T)]
+                plan.add(E.PReluBatchOp([(hs[i], ys[i], a) for i in range(T)]))
+                hs = ys
             if j == 0 and use_dbn:  # model/star.py:50-51: after the activation of the first layer, head by head
                 ys = []
                 for i in range(T):

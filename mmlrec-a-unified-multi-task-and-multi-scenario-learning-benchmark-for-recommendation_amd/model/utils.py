@@ -167,14 +167,33 @@ def activation_code(name):
         key = name.lower()
         if key in E.ACT:
             return E.ACT[key]
+        if key == "dice":
+            # (reference model/utils.py:27: `Dice(hidden_size, dice_dim)` -- a class the reference never defines)
+            raise NotImplementedError("activation 'dice': the reference's activation_layer names a class `Dice` that it "
+                                      "does not define (NameError there); there is nothing to port")
     if name is None:
         return L.ACT_NONE
-    raise NotImplementedError(f"activation {name!r} (the hot path supports relu / sigmoid / linear)")
+    raise NotImplementedError(f"activation {name!r} (the hot path supports relu / sigmoid / linear / prelu)")
+
+
+def refuse_prelu(name, site):
+    """Activation sites outside DNN and STAR that have no PReLU kernel path (INTEGRATION.md lists them)."""
+    if activation_code(name) == E.ACT_PRELU:
+        raise NotImplementedError(f"dnn_activation 'prelu' is not supported by {site} (the reference builds an nn.PReLU "
+                                  "there too); DNN stacks and STAR's layers take it")
+
+
+def value_act(code):
+    """The activation a GEMM / BatchNorm epilogue applies for a layer of activation `code`: none for PReLU, whose
+    engine.PReluBatchOp follows."""
+    return L.ACT_NONE if code == E.ACT_PRELU else code
 
 
 def activation_layer(act_name, hidden_size=None, dice_dim=2):
-    """Kept for API compatibility (modules built from it are descriptive only)."""
+    """Kept for API compatibility (modules built from it are descriptive only, nn.PReLU() holds a layer's slope)."""
     code = activation_code(act_name)
+    if code == E.ACT_PRELU:
+        return nn.PReLU()
     return {L.ACT_RELU: nn.ReLU(inplace=True), L.ACT_SIGMOID: nn.Sigmoid(), L.ACT_NONE: nn.Identity()}[code]
 
 
@@ -182,7 +201,9 @@ def activation_layer(act_name, hidden_size=None, dice_dim=2):
 class DNN(nn.Module):
     """[Linear -> act] x L parameter stack (reference model/utils.py:92-161).  Weights N(0, init_std), biases keep
     nn.Linear's default init.  use_bn adds a BatchNorm1d after every Linear (engine.BNOp); dropout_rate > 0 adds an
-    engine.DropoutOp after every activation while the model is in training mode (reference :159)."""
+    engine.DropoutOp after every activation while the model is in training mode (reference :159).  activation "prelu":
+    one nn.PReLU() per layer (`activation_layers.{l}.weight`, a scalar slope at 0.25, no random draw; reference :136-138)
+    applied by engine.PReluBatchOp -- fc -> bn -> prelu -> dropout."""
 
     def __init__(self, inputs_dim, hidden_units, activation="relu", l2_reg=0, dropout_rate=0, use_bn=False,
                  init_std=0.0001, dice_dim=3, device="cpu"):
@@ -197,6 +218,8 @@ class DNN(nn.Module):
         self.linears = nn.ModuleList([nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1)])
         if use_bn:  # fc -> bn -> activation (reference :132-134, :153-157); registered right after the linears
             self.bn = nn.ModuleList([nn.BatchNorm1d(dims[i + 1]) for i in range(len(dims) - 1)])
+        if self.act_code == E.ACT_PRELU:  # after linears and bn (reference :136-138): named_parameters order and keys
+            self.activation_layers = nn.ModuleList([nn.PReLU() for _ in range(len(dims) - 1)])
         for name, p in self.linears.named_parameters():
             if "weight" in name:
                 nn.init.normal_(p, mean=0, std=init_std)
@@ -211,7 +234,9 @@ class DNN(nn.Module):
         launches layer l of sibling stacks together (emit_dnn_stacks)."""
         h = x
         out = []
-        plain = not self.use_bn and not (self.dropout_rate and plan.dropout_on)
+        prelu = self.act_code == E.ACT_PRELU
+        act = value_act(self.act_code)
+        plain = not self.use_bn and not (self.dropout_rate and plan.dropout_on) and not prelu
         for l, lin in enumerate(self.linears):
             q = dict(x=h, W=store.pvals[f"{prefix}.linears.{l}.weight"], b=store.pvals[f"{prefix}.linears.{l}.bias"])
             # bf16-storage path (engine.Plan.bf16): the value between two layers of the stack is read by the next layer's
@@ -224,12 +249,17 @@ class DNN(nn.Module):
                         else bool(last16)))
             if self.use_bn:  # the GEMM writes the pre-normalisation value; emit_dnn_stacks adds the BatchNorm op
                 q["out"] = plan.val(lin.out_features, name=f"{prefix}.{l}.z")
-                q["bn"] = dict(y=plan.val(lin.out_features, act=self.act_code, name=f"{prefix}.{l}"),
+                q["bn"] = dict(y=plan.val(lin.out_features, act=act, name=f"{prefix}.{l}" + (".n" if prelu else "")),
                                gamma=store.pvals[f"{prefix}.bn.{l}.weight"], beta=store.pvals[f"{prefix}.bn.{l}.bias"],
                                module=self.bn[l])
                 h = q["bn"]["y"]
             else:
-                q["out"] = h = plan.val(lin.out_features, act=self.act_code, name=f"{prefix}.{l}", store16=store16)
+                q["out"] = h = plan.val(lin.out_features, act=act, name=f"{prefix}.{l}" + (".z" if prelu else ""),
+                                        store16=store16)
+            if prelu:  # fc -> bn -> prelu (reference :153-157); emit_dnn_stacks launches one depth of all stacks together
+                q["prelu"] = dict(z=h, y=plan.val(lin.out_features, name=f"{prefix}.{l}"),
+                                  alpha=store.pvals[f"{prefix}.activation_layers.{l}.weight"])
+                h = q["prelu"]["y"]
             if self.dropout_rate and plan.dropout_on:  # act -> dropout (reference :156-159); emit_dnn_stacks adds the op
                 q["drop"] = dict(x=h, y=plan.val(lin.out_features, name=f"{prefix}.{l}.drop"), p=self.dropout_rate,
                                  site=E.dropout_site(f"{prefix}.{l}"))
@@ -238,33 +268,57 @@ class DNN(nn.Module):
         return out
 
     def forward(self, inputs):
-        from ..functional import linear_act
+        from ..functional import linear_act, prelu
         if self.use_bn:
             raise NotImplementedError("stand-alone DNN.forward with BatchNorm: use the model's forward")
         if self.dropout_rate and self.training:
             raise NotImplementedError("stand-alone DNN.forward with dropout in training mode: use the model's forward")
         h = inputs
-        for lin in self.linears:
-            h = linear_act(h, lin.weight, lin.bias, self.act_code)
+        for l, lin in enumerate(self.linears):
+            h = linear_act(h, lin.weight, lin.bias, value_act(self.act_code))
+            if self.act_code == E.ACT_PRELU:
+                h = prelu(h, self.activation_layers[l].weight)
         return h
+
+
+def emit_layer_group(plan, probs):
+    """One layer depth of sibling stacks: ONE grouped GEMM, each problem's BatchNorm, ONE PReLU launch for every problem
+    that has one, each problem's dropout (fc -> bn -> activation -> dropout, reference model/utils.py:153-159)."""
+    plan.add(E.LinearGroupOp(probs))
+
+    def drop(q):
+        d = q["drop"]
+        plan.add(E.DropoutOp(d["x"], d["y"], d["p"], plan.dropout_seed, d["site"]))
+
+    for q in probs:
+        if "bn" in q:
+            b = q["bn"]
+            plan.add(E.BNOp(q["out"], b["y"], b["gamma"], b["beta"], b["module"]))
+        if "drop" in q and "prelu" not in q:
+            drop(q)
+    acts = [q for q in probs if "prelu" in q]
+    if acts:
+        plan.add(E.PReluBatchOp([(q["prelu"]["z"], q["prelu"]["y"], q["prelu"]["alpha"]) for q in acts]))
+        for q in acts:
+            if "drop" in q:
+                drop(q)
+
+
+def problem_output(q):
+    for k in ("drop", "prelu", "bn"):
+        if k in q:
+            return q[k]["y"]
+    return q["out"]
 
 
 def emit_dnn_stacks(plan, stacks):
     """stacks: list of per-stack problem lists (from DNN.layer_problems).  Layer l of every stack is launched as ONE
-    grouped GEMM (experts + gate DNNs of an MMoE share the input and the launch)."""
+    grouped GEMM (experts + gate DNNs of an MMoE share the input and the launch), and ONE PReLU launch where the stacks
+    have that activation."""
     depth = max(len(s) for s in stacks)
     for l in range(depth):
-        probs = [s[l] for s in stacks if len(s) > l]
-        plan.add(E.LinearGroupOp(probs))
-        for q in probs:
-            if "bn" in q:
-                b = q["bn"]
-                plan.add(E.BNOp(q["out"], b["y"], b["gamma"], b["beta"], b["module"]))
-            if "drop" in q:
-                d = q["drop"]
-                plan.add(E.DropoutOp(d["x"], d["y"], d["p"], plan.dropout_seed, d["site"]))
-    return [s[-1]["drop"]["y"] if "drop" in s[-1] else (s[-1]["bn"]["y"] if "bn" in s[-1] else s[-1]["out"])
-            for s in stacks]
+        emit_layer_group(plan, [s[l] for s in stacks if len(s) > l])
+    return [problem_output(s[-1]) for s in stacks]
 
 
 def blocks_out_act(plan, blocks):
@@ -272,7 +326,7 @@ def blocks_out_act(plan, blocks):
     between the activation and the output (training mode)."""
     if plan.dropout_on and any(b.dropout_rate for b in blocks):
         return L.ACT_NONE
-    return L.ACT_RELU
+    return value_act(blocks[0].act_code)
 
 
 def emit_blocks_into(plan, store, blocks, prefixes, ins, outs):
@@ -287,24 +341,25 @@ def emit_blocks_into(plan, store, blocks, prefixes, ins, outs):
         if drop and o.act != L.ACT_NONE:
             raise L.MMLError("emit_blocks_into: the given output of a block with dropout must carry no activation "
                              "(blocks_out_act)")
-        a = plan.val(o.n, act=blk.act_code, name=o.name + ".a") if drop else o
+        prelu = blk.act_code == E.ACT_PRELU
+        if prelu and o.act != L.ACT_NONE:
+            raise L.MMLError("emit_blocks_into: the given output of a PReLU block must carry no activation "
+                             "(blocks_out_act)")
+        a = plan.val(o.n, act=value_act(blk.act_code), name=o.name + ".a") if drop else o
+        # with PReLU the Linear / BatchNorm output is a scratch value and the PReLU launch produces the activation's
+        pre = plan.val(o.n, name=o.name + ".p") if prelu else a
         if blk.use_bn:
             q["out"] = plan.val(o.n, name=o.name + ".z")
-            q["bn"] = dict(y=a, gamma=store.pvals[f"{pfx}.bn.0.weight"], beta=store.pvals[f"{pfx}.bn.0.bias"],
+            q["bn"] = dict(y=pre, gamma=store.pvals[f"{pfx}.bn.0.weight"], beta=store.pvals[f"{pfx}.bn.0.bias"],
                            module=blk.bn[0])
         else:
-            q["out"] = a
+            q["out"] = pre
+        if prelu:
+            q["prelu"] = dict(z=pre, y=a, alpha=store.pvals[f"{pfx}.activation_layers.0.weight"])
         if drop:
             q["drop"] = dict(x=a, y=o, p=blk.dropout_rate, site=E.dropout_site(f"{pfx}.0"))
         probs.append(q)
-    plan.add(E.LinearGroupOp(probs))
-    for q in probs:
-        if "bn" in q:
-            b = q["bn"]
-            plan.add(E.BNOp(q["out"], b["y"], b["gamma"], b["beta"], b["module"]))
-        if "drop" in q:
-            d = q["drop"]
-            plan.add(E.DropoutOp(d["x"], d["y"], d["p"], plan.dropout_seed, d["site"]))
+    emit_layer_group(plan, probs)
 
 
 class DomainBatchNorm(nn.Module):

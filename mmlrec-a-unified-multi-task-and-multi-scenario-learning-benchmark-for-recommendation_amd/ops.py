@@ -812,6 +812,72 @@ def copy2d(src, dst, accumulate=False):
                                 _stream()), "mml_copy2d")
 
 
+def prelu_max_batch():
+    return int(L.load().mml_prelu_max_batch())
+
+
+def make_prelu_descs(items):
+    """items: dicts z, y [rows, cols] views, alpha (a device tensor holding the slope), optional amax (a slot)."""
+    arr = (L.PreluDesc * len(items))()
+    for d, it in zip(arr, items):
+        z, y = _f32_2d(it["z"], "prelu z"), _f32_2d(it["y"], "prelu y")
+        if y.shape != z.shape or it["alpha"].dtype != torch.float32 or it["alpha"].numel() != 1:
+            raise L.MMLError("prelu: y must have z's shape and alpha one float32 element")
+        d.z, d.ldz, d.y, d.ldy, d.rows, d.cols = z.data_ptr(), _ld(z), y.data_ptr(), _ld(y), z.shape[0], z.shape[1]
+        d.alpha, d.amax_out = it["alpha"].data_ptr(), L.ptr(it.get("amax"))
+    return arr
+
+
+def make_prelu_bwd_descs(items, seen=None):
+    """items: dicts dy, z, dz [rows, cols] views (dz may be dy), alpha, dalpha (one-element device tensors), optional
+    acc_dz, acc_dalpha, amax.  seen: the dalpha addresses earlier launches of the same backward already wrote -- an item
+    that names one of them accumulates."""
+    arr = (L.PreluBwdDesc * len(items))()
+    for d, it in zip(arr, items):
+        dy, z, dz = _f32_2d(it["dy"], "prelu dy"), _f32_2d(it["z"], "prelu z"), _f32_2d(it["dz"], "prelu dz")
+        if dy.shape != z.shape or dz.shape != z.shape:
+            raise L.MMLError("prelu backward: dy, z and dz must have one shape")
+        for k in ("alpha", "dalpha"):
+            if it[k].dtype != torch.float32 or it[k].numel() != 1:
+                raise L.MMLError(f"prelu backward: {k} must be one float32 element")
+        d.dy, d.lddy, d.z, d.ldz, d.dz, d.lddz = dy.data_ptr(), _ld(dy), z.data_ptr(), _ld(z), dz.data_ptr(), _ld(dz)
+        d.rows, d.cols, d.alpha, d.dalpha = z.shape[0], z.shape[1], it["alpha"].data_ptr(), it["dalpha"].data_ptr()
+        d.accumulate_dz = int(bool(it.get("acc_dz")))
+        d.accumulate_dalpha = int(bool(it.get("acc_dalpha")) or (seen is not None and d.dalpha in seen))
+        d.amax_out = L.ptr(it.get("amax"))
+    return arr
+
+
+def prelu_chunks(items):
+    """A list of problems in launches of at most mml_prelu_max_batch() items."""
+    cap = prelu_max_batch()
+    return [items[i:i + cap] for i in range(0, len(items), cap)]
+
+
+def prelu_fwd(items):
+    """y = z > 0 ? z : alpha * z for a list of problems, ONE launch per mml_prelu_max_batch() of them."""
+    _need_gpu(*[it["z"] for it in items])
+    for chunk in prelu_chunks(items):
+        L.check(L.load().mml_prelu_batch_fwd(make_prelu_descs(chunk), len(chunk), _stream()), "mml_prelu_batch_fwd")
+
+
+def prelu_bwd(items):
+    """dz (+)= z > 0 ? dy : alpha * dy and dalpha (+)= sum_{z <= 0} dy * z; items that share a dalpha tensor are summed
+    into it (include/mmlrec.h: mml_prelu_batch_bwd)."""
+    _need_gpu(*[it["z"] for it in items])
+    seen = set()
+    for chunk in prelu_chunks(items):
+        arr = make_prelu_bwd_descs(chunk, seen)
+        # an item whose dalpha an EARLIER item of this launch names must carry that item's flag
+        first = {}
+        for d in arr:
+            d.accumulate_dalpha = first.setdefault(d.dalpha, d.accumulate_dalpha)
+        nbytes = int(L.load().mml_prelu_workspace_bytes(len(chunk)))
+        ws = workspace(nbytes, chunk[0]["z"].device)
+        L.check(L.load().mml_prelu_batch_bwd(arr, len(chunk), ws.data_ptr(), nbytes, _stream()), "mml_prelu_batch_bwd")
+        seen.update(d.dalpha for d in arr)
+
+
 def act_bwd(y, dy, dst, act):
     L.check(L.load().mml_act_bwd(y.data_ptr(), dy.data_ptr(), dst.data_ptr(), y.numel(), act, _stream()), "mml_act_bwd")
 
