@@ -544,6 +544,14 @@ int mml_gemm_grouped_wgrad_phase(const mml_gemm_wgrad_desc* descs, int32_t n, vo
  * launches (engine.Plan.merge_wgrad) asks here, so that its grouping and the library's decision cannot drift apart.  No GPU
  * work, no error text. */
 int mml_gemm_nt_serves(const mml_gemm_wgrad_desc* desc);
+/* 1 when mml_gemm_grouped_dgrad(desc, n) would run the output-stationary input-gradient kernel (csrc/gemm_os.hip:
+ * gemm_os_kernel) on these descriptors, else 0: the GEMM mode is auto / two-plane, MMLREC_GEMM_OS is not 0 (read on every
+ * call), n == 1, and the problem meets every condition of that kernel (plain epilogue, 2 .. MML_MAX_SRC nn.Linear-layout
+ * sources with pre-cut planes of ONE exponent word and their gradients' magnitudes, M >= 16384, 192 <= K <= 256, summed
+ * N >= 256, alignment and row pitches).  That kernel stores exactly dA's [M, K] region and raises amax_out with the exact
+ * maximum of what it stored; a caller that relies on that (engine.LinearGroupOp -> the deterministic scatter's fixed-point
+ * unit) asks here, so that its belief and the library's dispatch cannot drift apart.  No GPU work, no error text. */
+int mml_gemm_os_serves(const mml_gemm_dgrad_desc* desc, int32_t n);
 
 /* ------------------------------------------------------------------------------------------------
  * K4  gate: skinny linear [Gd -> ne] (no bias) + softmax over experts + expert mix.

@@ -220,6 +220,7 @@ _SIGS = {
     "mml_gemm_set_ws": (C.c_int, [i32]),
     "mml_gemm_set_nt": (C.c_int, [i32]),
     "mml_gemm_nt_serves": (C.c_int, [_PP(GemmWgradDesc)]),
+    "mml_gemm_os_serves": (C.c_int, [_PP(GemmDgradDesc), i32]),
     "mml_tower_head_serves": (C.c_int, [_PP(TowerHeadGroup)]),
     "mml_tower_head_workspace_bytes": (i64, [_PP(TowerHeadGroup)]),
     "mml_tower_head_fwd_bwd": (C.c_int, [_PP(TowerHeadGroup), fp, i64, i32, fp]),

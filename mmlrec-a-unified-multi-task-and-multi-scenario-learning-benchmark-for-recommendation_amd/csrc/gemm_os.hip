@@ -374,28 +374,39 @@ __global__ __launch_bounds__(512, 1) void gemm_os_kernel(const OsLaunch Larg) {
 
 using namespace mml;
 
-// MML_OK: served; MML_ERR_UNSUPPORTED (no error text): not a launch of this kernel -- the caller goes on to the
-// weight-stationary and the tile kernel.  MMLREC_GEMM_OS=0 (read on every call: a test switches it inside one process)
-// turns the kernel off.
-int mml_gemm_os_try_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, hipStream_t st) {
+// The launches this kernel takes (mml_gemm_os_serves in gemm.hip: the host side asks the same question).
+// MMLREC_GEMM_OS=0 (read on every call: a test switches it inside one process) turns the kernel off.
+bool mml_gemm_os_takes(const mml_gemm_dgrad_desc* d, int32_t n) {
   const char* e = getenv("MMLREC_GEMM_OS");
-  if ((e && e[0] == '0') || n != 1) return MML_ERR_UNSUPPORTED;
+  if ((e && e[0] == '0') || !d || n != 1) return false;
   const mml_gemm_dgrad_desc& q = d[0];
-  if (q.gate_h || q.Y || q.relu_mask || q.act != MML_ACT_NONE || !q.dA) return MML_ERR_UNSUPPORTED;
-  if (q.n_src < 2 || q.n_src > MML_MAX_SRC) return MML_ERR_UNSUPPORTED;  // (one source: the weight-stationary kernel's)
+  if (q.gate_h || q.Y || q.relu_mask || q.act != MML_ACT_NONE || !q.dA) return false;
+  if (q.n_src < 2 || q.n_src > MML_MAX_SRC) return false;  // (one source: the weight-stationary kernel's)
   // (every workgroup computes OS_NC = 256 columns: a narrower gradient wastes the difference -- PLE's K = 128 launches
   // measured 1 % slower per step with this kernel than with the tile kernel, so they stay there)
-  if (q.M < 16384 || q.K < 192 || q.K > OS_NC || q.K % 4 != 0) return MML_ERR_UNSUPPORTED;
-  if (!aligned16(q.dA) || q.ldda % 4 != 0 || q.ldda < q.K) return MML_ERR_UNSUPPORTED;
-  if ((int64_t)q.M * q.ldda >= (1ll << 40)) return MML_ERR_UNSUPPORTED;
+  if (q.M < 16384 || q.K < 192 || q.K > OS_NC || q.K % 4 != 0) return false;
+  if (!aligned16(q.dA) || q.ldda % 4 != 0 || q.ldda < q.K) return false;
+  if ((int64_t)q.M * q.ldda >= (1ll << 40)) return false;
+  int64_t ntot = 0;
+  for (int s = 0; s < q.n_src; ++s) {
+    if (q.w_kn[s] != 0 || !q.dC[s] || !q.w_planes[s] || !q.w_kexp[s] || !q.amax_dc[s]) return false;
+    if (q.w_kexp[s] != q.w_kexp[0]) return false;  // (one group, one exponent)
+    if (q.N[s] <= 0 || q.N[s] % 16 != 0) return false;
+    if (!aligned16(q.dC[s]) || q.lddc[s] % 4 != 0 || q.lddc[s] < q.N[s]) return false;
+    if (!aligned16(q.w_planes[s]) || q.ldw[s] % 4 != 0 || q.ldw[s] < q.K) return false;
+    ntot += q.N[s];
+  }
+  return ntot >= 256;  // (short reductions: the ring would not fill)
+}
+
+// MML_OK: served; MML_ERR_UNSUPPORTED (no error text): not a launch of this kernel -- the caller goes on to the
+// weight-stationary and the tile kernel.
+int mml_gemm_os_try_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, hipStream_t st) {
+  if (!mml_gemm_os_takes(d, n)) return MML_ERR_UNSUPPORTED;
+  const mml_gemm_dgrad_desc& q = d[0];
   OsLaunch L{};
   int64_t ntot = 0;
   for (int s = 0; s < q.n_src; ++s) {
-    if (q.w_kn[s] != 0 || !q.dC[s] || !q.w_planes[s] || !q.w_kexp[s] || !q.amax_dc[s]) return MML_ERR_UNSUPPORTED;
-    if (q.w_kexp[s] != q.w_kexp[0]) return MML_ERR_UNSUPPORTED;  // (one group, one exponent)
-    if (q.N[s] <= 0 || q.N[s] % 16 != 0) return MML_ERR_UNSUPPORTED;
-    if (!aligned16(q.dC[s]) || q.lddc[s] % 4 != 0 || q.lddc[s] < q.N[s]) return MML_ERR_UNSUPPORTED;
-    if (!aligned16(q.w_planes[s]) || q.ldw[s] % 4 != 0 || q.ldw[s] < q.K) return MML_ERR_UNSUPPORTED;
     OsSource& S = L.s[s];
     S.dC = q.dC[s];
     S.planes = q.w_planes[s];
@@ -405,7 +416,6 @@ int mml_gemm_os_try_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, hipStream_t s
     S.N = q.N[s];
     ntot += q.N[s];
   }
-  if (ntot < 256) return MML_ERR_UNSUPPORTED;  // (short reductions: the ring would not fill)
   L.dA = q.dA;
   L.kexp = q.w_kexp[0];
   L.amax_out = q.amax_out;

@@ -8,6 +8,7 @@ Gradient convention: `Val.grad` holds dL/d(pre-activation) once every consumer h
 the ONLY consumer of a value folds the activation derivative into its own kernel epilogue (dgrad / gate / head
 kernels do this); otherwise consumers add raw contributions and one `mml_act_bwd` pass finalises the sum.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -78,6 +79,12 @@ class Val:
 INLINE = object()  # call-list marker: (INLINE, python_callable, args) run in place like a PY entry but do NOT cut a HIP graph
 # (stream fork / join of trainer.InnerFork: event record / wait, capturable)
 PY = object()  # call-list marker: (PY, python_callable, args[, meta]) entries (collectives) next to (c_fn, args[, meta])
+
+
+def call_meta(c):
+    """The meta dict of a call-list entry -- (fn, args[, meta]), (PY, callable, args[, meta]) or (INLINE, callable, args) --
+    or {} when the entry carries none.  The dict itself: a caller may mutate it in place (Plan.finish: `ready`)."""
+    return c[-1] if isinstance(c[-1], dict) else {}
 
 
 def _claim(x):
@@ -308,17 +315,45 @@ class Plan:
             need.append((src if src is not None else view, v.amax))
         return v.amax
 
+    def raised_grad_slot(self, v):
+        """v's gradient slot if every writer of v.grad recorded so far raised it (grad_slot / shared_grad_slot), else None."""
+        return v.gamax if (v.gamax is not None and v.gamax_writers == v.written and v.written > 0) else None
+
     def grad_amax(self, v, need):
         """Slot of v.grad as a GEMM operand, called when every writer of the gradient has been recorded: the slot the
         writers raised if ALL of them did, else measured now."""
         if self.amax_pool is None:
             return None
-        if v.gamax is not None and v.gamax_writers == v.written and v.written > 0:
+        if self.raised_grad_slot(v) is not None:
             return v.gamax
         v.gamax = self.new_amax()
         v.gamax_writers = v.written
         need.append((v.grad, v.gamax))
         return v.gamax
+
+    def grad_slot(self, v):
+        """The magnitude slot of v.grad that the launch being recorded must raise with what it stores, or None.  Called by a
+        writer right after its _claim(v).  The slot stays valid for grad_amax as long as EVERY writer so far came through
+        here: one that did not leaves the count behind, and neither it nor any later writer gets the slot."""
+        if self.amax_pool is None:
+            return None
+        if v.gamax is None:
+            v.gamax = self.new_amax()
+        if v.gamax_writers != v.written - 1:
+            return None
+        v.gamax_writers += 1
+        return v.gamax
+
+    def shared_grad_slot(self, vals, slot=None):
+        """ONE magnitude slot (`slot`, or a fresh one) for the gradients of all `vals`: the op that calls this has claimed
+        each of them, is their only writer and raises the slot with every gradient it stores -- an upper bound for each."""
+        if self.amax_pool is None:
+            return None
+        if slot is None:
+            slot = self.new_amax()
+        for v in vals:
+            v.gamax, v.gamax_writers = slot, v.written
+        return slot
 
     def amax_call(self, need, **meta):
         arr = ops.make_amax_descs(need)
@@ -336,8 +371,7 @@ class Plan:
                 if c[0] is INLINE:  # (stream fork / join: the calls it issues open their own ranges)
                     c[1](*c[2])
                     continue
-                meta = c[3] if (c[0] is PY and len(c) > 3) else (c[2] if (c[0] is not PY and len(c) > 2) else {})
-                with profiling.range(meta.get("kernel") or getattr(c[1] if c[0] is PY else c[0], "__name__", "call")):
+                with profiling.range(call_meta(c).get("kernel") or getattr(c[1] if c[0] is PY else c[0], "__name__", "call")):
                     if c[0] is PY:
                         c[1](*c[2])
                     else:
@@ -373,16 +407,12 @@ class Plan:
                     L.check(rc, c[0].__name__)
             b.record(s)
             label = None
-            meta0 = c[2] if (c[0] is not PY and len(c) > 2 and isinstance(c[2], dict)) else {}
-            if str(meta0.get("kernel", "")).startswith("gemm<"):
+            if c[0] is not PY and str(call_meta(c).get("kernel", "")).startswith("gemm<"):
                 label = L.load().mml_gemm_last_kernel().decode() or None
             evs.append((c, a, b, label))
         torch.cuda.synchronize()
         for c, a, b, label in evs:
-            if c[0] is PY:
-                meta = c[3] if len(c) > 3 else {"kernel": getattr(c[1], "__name__", "python")}
-            else:
-                meta = c[2] if len(c) > 2 else {"kernel": c[0].__name__}
+            meta = call_meta(c) or {"kernel": getattr(c[1], "__name__", "python") if c[0] is PY else c[0].__name__}
             e = acc.setdefault(label or meta["kernel"], {"ms": 0.0, "launches": 0, "flops": 0.0, "bytes": 0.0,
                                                          "hbm_bytes": 0.0})
             e["ms"] += a.elapsed_time(b)
@@ -435,10 +465,9 @@ class Plan:
             self._cast16_prologue()
             return
         calls = head_op.train_calls(self, use_dprob=False)
-        is_side = lambda c: isinstance(c[-1], dict) and c[-1].get("side")  # noqa: E731
-        self.head_train = [c for c in calls if not is_side(c)]
+        self.head_train = [c for c in calls if not call_meta(c).get("side")]
         # (belongs to head_train, not to the backward every path shares: run_backward_from_dprob has its own head call)
-        self.head_side = [c for c in calls if is_side(c)]
+        self.head_side = [c for c in calls if call_meta(c).get("side")]
         self.head_bwd = head_op.train_calls(self, use_dprob=True, claim=False)
         for op in reversed(self.ops):
             for v in op.outputs():
@@ -450,7 +479,7 @@ class Plan:
                     v.deriv_applied = True
             mine = []
             for c in op.bwd_calls(self):
-                meta = c[-1] if isinstance(c[-1], dict) else {}
+                meta = call_meta(c)
                 if meta.get("side"):
                     self.bwd_side.append(c)
                     mine.append(c)
@@ -461,7 +490,7 @@ class Plan:
             # a side call reads dL/d(this op's outputs) and forward values only: it may start once the chain has issued
             # everything up to and including this op's own entries (TrainStep's early fork of the side stream)
             for c in mine:
-                c[-1]["ready"] = len(self.bwd)
+                call_meta(c)["ready"] = len(self.bwd)
         self._amax_prologue()
         self._cast16_prologue()
         if os.environ.get("MMLREC_MERGE_COPIES", "1") != "0":
@@ -473,8 +502,8 @@ class Plan:
                     # space (ready = k: the first k entries have been issued -> everything up to the merged entry that
                     # holds old entry k - 1)
                     for c in list(self.bwd_side) + list(self.head_side):
-                        m = c[-1] if isinstance(c[-1], dict) else None
-                        if m is not None and m.get("ready"):
+                        m = call_meta(c)
+                        if m.get("ready"):
                             m["ready"] = where[min(m["ready"], len(where)) - 1] + 1
         # (Measured on MI355X: issuing every weight-gradient partial-product GEMM before the first reduction -- the
         # phased wgrad entry point allows it -- makes the step SLOWER, 2.35 ms vs 2.19 ms: the GEMMs then run next to
@@ -541,7 +570,7 @@ class Plan:
                 meta = dict(kernel="copy2d_batch_kernel",
                             bytes=sum(8.0 * r[4] * r[5] for r in run))
                 for c in meta_run:  # (the scheduling tags of the merged calls: they were neighbours of ONE list)
-                    m = c[-1] if isinstance(c[-1], dict) else {}
+                    m = call_meta(c)
                     for k in ("side", "tail", "rank", "ready"):
                         if k in m:
                             meta[k] = max(meta.get(k, m[k]), m[k]) if k == "ready" else m[k]
@@ -614,11 +643,11 @@ class Plan:
         first_gemm = next((i for i, c in enumerate(self.fwd) if c[0] in (lib.mml_gemm_grouped_fwd, lib.mml_pep_gate_fwd)),
                           len(self.fwd))
         host = next((i for i, c in enumerate(self.fwd[:first_gemm]) if c[0] is lib.mml_amax_batch and
-                     isinstance(c[-1], dict) and "need" in c[-1]), None)
+                     "need" in call_meta(c)), None)
         if self.amax_wlist and host is not None and os.environ.get("MMLREC_AMAX_MERGE", "1") != "0":
             c = self.fwd[host]
-            merged = self.amax_call(c[-1]["need"] + self.amax_wlist,
-                                    **{k: v for k, v in c[-1].items() if k not in ("kernel", "bytes", "need")})
+            merged = self.amax_call(call_meta(c)["need"] + self.amax_wlist,
+                                    **{k: v for k, v in call_meta(c).items() if k not in ("kernel", "bytes", "need")})
             self.fwd = self.fwd[:host] + [merged] + cut + self.fwd[host + 1:]
         else:
             if self.amax_wlist:
@@ -680,8 +709,8 @@ class Plan:
         targets = [d.dW for d in descs] + [d.dbias for d in descs if d.dbias]
         if len(set(targets)) != len(targets) or any(d.accumulate for d in descs):
             return False
-        flops = sum(self.bwd_side[i][2].get("flops", 0.0) for i in idx)
-        hbm = sum(self.bwd_side[i][2].get("hbm_bytes", 0.0) for i in idx)
+        flops = sum(call_meta(self.bwd_side[i]).get("flops", 0.0) for i in idx)
+        hbm = sum(call_meta(self.bwd_side[i]).get("hbm_bytes", 0.0) for i in idx)
         merged, reduces = [], []
         for ch in chunks:
             arr = (L.GemmWgradDesc * len(ch))()
@@ -786,8 +815,8 @@ class Plan:
         del self.fwd[fi]
         del self.bwd[di]
         for c in list(self.bwd_side) + list(self.head_side):  # (`ready` counts entries of the backward chain)
-            m = c[-1] if isinstance(c[-1], dict) else None
-            if m is not None and m.get("ready", 0) > di:
+            m = call_meta(c)
+            if m.get("ready", 0) > di:
                 m["ready"] -= 1
         self.head_train = [fused]
         self.head_side = [red]
@@ -843,8 +872,8 @@ class Plan:
                 it.workspace, it.workspace_bytes = ws, nbytes
             self.keep.append(items)
             calls.append((lib.mml_rows_reduce_batch, (items, len(ch)),
-                          dict(kernel="slab_reduce", bytes=sum(c[2].get("bytes", 0.0) for c in ch), side=True, rank=1,
-                               ready=max(c[2].get("ready", 0) for c in ch))))
+                          dict(kernel="slab_reduce", bytes=sum(call_meta(c).get("bytes", 0.0) for c in ch), side=True, rank=1,
+                               ready=max(call_meta(c).get("ready", 0) for c in ch))))
         self.head_side = [c for c in self.head_side if not is_red(c)]
         self.bwd_side = calls + [c for c in self.bwd_side if not is_red(c)]
         return True
@@ -867,7 +896,7 @@ class Plan:
             return -(-steps // sl) * -(-tiles * sl // 512) + 8
 
         groups = [[self.bwd_side[i][1][0][k] for k in range(self.bwd_side[i][1][1])] for i in idx]
-        metas = [self.bwd_side[i][2] for i in idx]
+        metas = [call_meta(self.bwd_side[i]) for i in idx]
         out, om = [groups[0]], [dict(metas[0])]
         for g, m in zip(groups[1:], metas[1:]):
             cur = out[-1]
@@ -1074,8 +1103,8 @@ class GatherOp(Op):
             g = self.out
             # the magnitude of d(dnn_input) from the launch that wrote it: the one writer raised g.gamax (a slot of the
             # pool the step's opening mml_amax_reset zeroes) with the exact maximum over the [B, F * E] region read here
-            if (fused and self.nd == 0 and getattr(g, "gamax_exact", False) and g.gamax is not None and
-                    g.written == 1 and g.gamax_writers == 1 and g.n == F * E):
+            if (fused and self.nd == 0 and getattr(g, "gamax_exact", False) and g.written == 1 and
+                    plan.raised_grad_slot(g) is not None and g.n == F * E):
                 slot = g.gamax
                 flags |= L.SCATTER_DET_AMAX_SUPPLIED
             # the totals stay in acc64 for the ONE marked streaming launch of the dense table optimizer
@@ -1258,8 +1287,6 @@ class LinearGroupOp(Op):
                                  f"tile-aligned extents (got {q['x'].n} -> {out.n} at batch {plan.B})")
             if out.act not in (L.ACT_NONE, L.ACT_RELU):
                 raise NotImplementedError("bf16-storage layer group: relu / linear activations")
-            if plan.training and out.act == L.ACT_RELU and out.mask is None:
-                out.mask = torch.zeros(plan.B, (out.n + 31) // 32, dtype=torch.int32, device=plan.device)
             out.producer16 = True
             probs.append(dict(srcs=[(q["x"].buf, plan.weight16(q["W"], False))], C=out.buf,
                               bias=q["b"].data if q.get("b") else None, act=out.act,
@@ -1277,11 +1304,9 @@ class LinearGroupOp(Op):
             calls.append((lib.mml_g16_tn, (descs, len(ch)), meta))
         return calls
 
-    def _bwd16(self, plan):
-        lib = L.load()
-        calls = []
-        live = [q for q in self.p if q["out"].grad is not None]
-        # the incoming gradients as bf16 operands: written that way by their producer (Plan.grad_of), else cast here
+    def _casts16(self, plan, live):
+        """The incoming gradients as bf16 operands (q["dC16"]): written that way by their producer (Plan.grad_of), else cast
+        here, in ONE launch."""
         casts = []
         for q in live:
             g = q["out"].grad
@@ -1292,22 +1317,22 @@ class LinearGroupOp(Op):
                     raise L.MMLError("bf16-storage layer group: the activation derivative must be applied upstream")
                 q["dC16"] = plan.empty(plan.B, q["out"].n, dtype=torch.bfloat16)
                 casts.append((g, q["dC16"], False))
-        if casts:
-            arr = ops.make_cast16_descs(casts)
-            plan.keep.append(arr)
-            calls.append((lib.mml_cast16_batch, (arr, len(casts)),
-                          dict(kernel="cast16_kernel", bytes=6.0 * sum(g.numel() for g, _, _ in casts))))
-        # weight / bias gradients (side list: only the optimizer reads them)
+        if not casts:
+            return []
+        arr = ops.make_cast16_descs(casts)
+        plan.keep.append(arr)
+        return [(L.load().mml_cast16_batch, (arr, len(casts)),
+                 dict(kernel="cast16_kernel", bytes=6.0 * sum(g.numel() for g, _, _ in casts)))]
+
+    def _wgrad16_calls(self, plan, live):
+        """Weight / bias gradients of the bf16-storage path (side list: only the optimizer reads them)."""
+        lib = L.load()
         wg = []
         for q in live:
-            W, b = q["W"], q.get("b")
-            if not W.needs_grad:
-                continue
-            acc = _claim(W)
-            if b is not None and b.needs_grad and _claim(b) != acc:
-                raise L.MMLError("weight and bias of one layer must be written in the same order")
-            wg.append(dict(dC=q["dC16"], A=q["x"].buf, dW=W.grad, dbias=b.grad if (b and b.needs_grad) else None,
-                           accumulate=acc))
+            if q["W"].needs_grad:
+                acc, dbias = self._claim_wb(q)
+                wg.append(dict(dC=q["dC16"], A=q["x"].buf, dW=q["W"].grad, dbias=dbias, accumulate=acc))
+        calls = []
         for i in range(0, len(wg), L.G16_MAX_GROUP):
             ch = wg[i:i + L.G16_MAX_GROUP]
             descs = ops.make_g16_wgrad_descs(ch)
@@ -1323,13 +1348,12 @@ class LinearGroupOp(Op):
             calls.append((lib.mml_g16_wgrad, (descs, len(ch), ws.data_ptr(), ws.numel(), 1), meta))
             calls.append((lib.mml_g16_wgrad, (descs, len(ch), ws.data_ptr(), ws.numel(), 2),
                           dict(kernel="g16_reduce_kernel", bytes=float(nbytes), side=True, rank=1)))
-        # input gradients: one problem per distinct input value, its layers as the sources
-        by_x = {}
-        for q in live:
-            if q["x"].needs_grad:
-                by_x.setdefault(id(q["x"]), (q["x"], []))[1].append(q)
+        return calls
+
+    def _dgrad16_calls(self, plan, live):
+        """Input gradients of the bf16-storage path: one problem per distinct input value, its layers as the sources."""
         dg = []
-        for x, qs in by_x.values():
+        for x, qs in self._by_input(live):
             if len(qs) > L.MAX_SRC:
                 raise NotImplementedError("bf16-storage layer group: more than MAX_SRC layers on one input")
             plan.grad_of(x)
@@ -1343,6 +1367,7 @@ class LinearGroupOp(Op):
                             mask_in=x.mask if fuse else None), x, qs))
             if fuse:
                 x.deriv_applied = True
+        calls = []
         for i in range(0, len(dg), L.G16_MAX_GROUP):
             ch = dg[i:i + L.G16_MAX_GROUP]
             descs = ops.make_g16_tn_descs([c[0] for c in ch])
@@ -1352,8 +1377,45 @@ class LinearGroupOp(Op):
                         hbm_bytes=_distinct_bytes([x.grad for _, x, _ in ch] + [x.mask for _, x, _ in ch] +
                                                   [q["dC16"] for _, _, qs in ch for q in qs]) +
                         2.0 * sum(q["W"].data.numel() for _, _, qs in ch for q in qs))
-            calls.append((lib.mml_g16_tn, (descs, len(ch)), meta))
+            calls.append((L.load().mml_g16_tn, (descs, len(ch)), meta))
         return calls
+
+    # ---- what the fp32 and the bf16-storage path share -----------------------------------------------------------
+    def _relu_masks(self, plan):
+        """Training plans: a ReLU output also leaves its sign bits (1 bit per element) for the dgrad that will apply
+        relu' to its gradient -- 32x less to re-read than the activations themselves."""
+        for q in self.p:
+            out = q["out"]
+            if plan.training and out.act == L.ACT_RELU and out.mask is None:
+                out.mask = torch.zeros(plan.B, (out.n + 31) // 32, dtype=torch.int32, device=plan.device)
+
+    def _live(self):
+        """The problems whose output received a gradient."""
+        return [q for q in self.p if q["out"].grad is not None]
+
+    @staticmethod
+    def _by_input(live):
+        """[(x, the live problems that read x)] per distinct input value that takes a gradient, in order of appearance."""
+        by_x = {}
+        for q in live:
+            if q["x"].needs_grad:
+                by_x.setdefault(id(q["x"]), (q["x"], []))[1].append(q)
+        return list(by_x.values())
+
+    @staticmethod
+    def _claim_wb(q):
+        """Claim the weight and the bias gradient of problem q: (accumulate flag, bias gradient buffer or None)."""
+        W, b = q["W"], q.get("b")
+        acc = _claim(W)
+        if b is not None and b.needs_grad and _claim(b) != acc:
+            raise L.MMLError("weight and bias of one layer must be written in the same order")
+        return acc, (b.grad if (b and b.needs_grad) else None)
+
+    @staticmethod
+    def _planes_all_or_none(wp):
+        """Pre-cut weight planes [(planes, kexp)] for all problems / sources of a launch or for none: the kernels take
+        the planes form per launch."""
+        return wp if all(pl is not None for pl, _ in wp) else [(None, None)] * len(wp)
 
     def inputs(self):
         return [q["x"] for q in self.p] + [q["mul"] for q in self.p
@@ -1362,18 +1424,10 @@ class LinearGroupOp(Op):
     def outputs(self):
         return [q["out"] for q in self.p] + [q["prod"] for q in self.p if q.get("mul") is not None]
 
-    def fwd_calls(self, plan):
-        if plan.bf16 and any(q["x"].is16 for q in self.p):
-            self.use16 = True
-            return self._fwd16(plan)
-        # training plans: a ReLU output also leaves its sign bits (1 bit per element) for the dgrad that will apply
-        # relu' to its gradient -- 32x less to re-read than the activations themselves
-        for q in self.p:
-            out = q["out"]
-            if plan.training and out.act == L.ACT_RELU and out.mask is None:
-                out.mask = torch.zeros(plan.B, (out.n + 31) // 32, dtype=torch.int32, device=plan.device)
-        # reduction length not a multiple of 16: run the GEMM on the zero-padded operand pair (the value's own padded
-        # rows, a padded copy of the weight refreshed every step) instead of dropping to the register-staged kernel
+    def _pad_calls(self, plan):
+        """Reduction length not a multiple of 16: run the GEMM on the zero-padded operand pair (the value's own padded
+        rows q["Ap"], a padded copy of the weight q["Wp"] refreshed every step by the copy returned here) instead of
+        dropping to the register-staged kernel."""
         pads = []
         for q in self.p:
             kp = _kpad_of(q)
@@ -1381,7 +1435,14 @@ class LinearGroupOp(Op):
                 q["Ap"] = _padded_view(q["x"].buf, kp)
                 q["Wp"] = plan.zeros(q["W"].data.shape[0], kp)
                 pads.append((q["W"].data, q["Wp"]))
-        pre = [_copy2d_batch_call(plan, pads)] if pads else []
+        return [_copy2d_batch_call(plan, pads)] if pads else []
+
+    def fwd_calls(self, plan):
+        self._relu_masks(plan)
+        if plan.bf16 and any(q["x"].is16 for q in self.p):
+            self.use16 = True
+            return self._fwd16(plan)
+        pre = self._pad_calls(plan)
         # operand magnitudes: the input's (its producer's, or measured here), the weight's (start of the step), and the
         # output's is produced by this launch for the GEMMs that read it
         need = []
@@ -1394,10 +1455,7 @@ class LinearGroupOp(Op):
                 q["prod"].amax = plan.new_amax()
         if need:
             pre.append(plan.amax_call(need))
-        # pre-cut weights: all problems of the launch or none (the kernel takes the planes form per launch)
-        wp = [plan.weight_planes(q, ops.PLANES_ROWS, padded="Wp" in q) for q in self.p]
-        if any(pl is None for pl, _ in wp):
-            wp = [(None, None)] * len(self.p)
+        wp = self._planes_all_or_none([plan.weight_planes(q, ops.PLANES_ROWS, padded="Wp" in q) for q in self.p])
         descs = ops.make_fwd_descs([dict(A=q.get("Ap", q["x"].buf), W=q.get("Wp", q["W"].data),
                                          bias=q["b"].data if q.get("b") else None,
                                          C=q["out"].buf, act=q["out"].act, w_kn=q.get("w_kn", 0),
@@ -1422,11 +1480,9 @@ class LinearGroupOp(Op):
         return pre + [(L.load().mml_gemm_grouped_fwd, (descs, len(self.p)), meta)]
 
     def bwd_calls(self, plan):
+        live = self._live()
         if self.use16:
-            return self._bwd16(plan)
-        lib = L.load()
-        calls = []
-        live = [q for q in self.p if q["out"].grad is not None]
+            return self._casts16(plan, live) + self._wgrad16_calls(plan, live) + self._dgrad16_calls(plan, live)
         # magnitudes of the incoming gradients (every writer of out.grad has been recorded by now): raised by the GEMM
         # that wrote them, else measured here, on the main chain, before the input-gradient and weight-gradient launches
         need = []
@@ -1434,184 +1490,193 @@ class LinearGroupOp(Op):
             q["amax_dc"] = plan.grad_amax(q["out"], need)
             if q.get("amax_w") is None:
                 q["amax_w"] = plan.weight_amax(q["W"], q.get("Wp", q["W"].data), need)
-        if need:
-            calls.append(plan.amax_call(need))
-        # weight / bias gradients
-        wg = []
-        for q in live:
-            W, b = q["W"], q.get("b")
-            if not W.needs_grad:
-                continue
-            acc = _claim(W)
-            if b is not None and b.needs_grad:
-                if _claim(b) != acc:
-                    raise L.MMLError("weight and bias of one layer must be written in the same order")
-            if "Ap" in q and not acc:
-                q["dWp"] = plan.empty(W.data.shape[0], q["Ap"].shape[1])
-                wg.append(dict(dC=q["out"].grad, A=q["Ap"], dW=q["dWp"], dbias=b.grad if (b and b.needs_grad) else None,
-                               accumulate=0, w_kn=0, unpad=(q["dWp"], W.grad), amax_dc=q["amax_dc"],
-                               amax_a=q.get("amax_a")))
-                continue
-            wg.append(dict(dC=q["out"].grad, A=q["x"].buf, dW=W.grad, dbias=b.grad if (b and b.needs_grad) else None,
-                           accumulate=acc, w_kn=q.get("w_kn", 0), amax_dc=q["amax_dc"], amax_a=q.get("amax_a")))
-        if wg:
-            descs = ops.make_wgrad_descs(wg)
-            nbytes = lib.mml_gemm_grouped_wgrad_workspace_bytes(descs, len(wg))
-            # own workspace: all partial-product launches of the step run before the first reduction (see Plan)
-            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=plan.device)
-            plan.keep += [descs, ws]
-            meta = dict(kernel=_gemm_symbol(False, False, [q["dW"].shape[1] for q in wg], 2, kreds=[plan.B],
-                                            tensors=[q["dC"] for q in wg] + [q["A"] for q in wg],
-                                            nrc_extents=[d for q in wg for d in q["dW"].shape]),
-                        flops=sum(2.0 * plan.B * q["dW"].numel() for q in wg), side=True, rank=0,
-                        hbm_bytes=_distinct_bytes([q["dC"] for q in wg] + [q["A"] for q in wg] + [q["dW"] for q in wg]))
-            calls.append((lib.mml_gemm_grouped_wgrad_phase, (descs, len(wg), ws.data_ptr(), ws.numel(), 1), meta))
-            calls.append((lib.mml_gemm_grouped_wgrad_phase, (descs, len(wg), ws.data_ptr(), ws.numel(), 2),
-                          dict(kernel="slab_reduce", bytes=float(nbytes), side=True, rank=1)))
-            unpad = [q["unpad"] for q in wg if "unpad" in q]  # padded weight gradients -> the parameters' [N, K]
-            if unpad:
-                c = _copy2d_batch_call(plan, unpad)
-                c[2]["side"] = True
-                calls.append(c)
+        calls = [plan.amax_call(need)] if need else []
+        calls += self._wgrad_calls(plan, live)
         # input gradients: one dgrad problem per distinct input value
-        by_x = {}
-        for q in live:
-            if q["x"].needs_grad:
-                by_x.setdefault(id(q["x"]), (q["x"], []))[1].append(q)
         waves = []  # chunk k of every input goes into launch k: chunks of ONE input must not run concurrently
         post = []   # sums of split input gradients, after the launches
         gate_wave = {}  # K7: id(factor value) -> last launch that writes its gradient
-        for x, qs in by_x.values():
-            chunks = [qs[i:i + L.MAX_SRC] for i in range(0, len(qs), L.MAX_SRC)]
-            gate = getattr(x, "gate", None)
-            if gate is not None:
-                # K7: x = h (.) g was written by the epilogue of the GEMM that produced g; its gradient is not stored,
-                # this launch writes the gradients of the two factors (gate mode)
-                if len(chunks) != 1 or len(x.consumers) != 1 or x.kpad:
-                    raise L.MMLError("a fused gate product must feed exactly one Linear group (<= MAX_SRC layers)")
-                h, g = gate
-                gd = dict(h=h.buf, g=g.buf)
-                # h shared by several products and able to take its gradient in parts (MulBatchOp(fwd_fused)): this
-                # problem writes a buffer of its own -- no accumulation, no order between the sharing problems
-                parts = getattr(h, "grad_parts", None)
-                # (at most seven: the summing launch takes eight terms per target -- parts + the plain gradient buffer a
-                # further reader would add to)
-                use_part = (parts is not None and h.act == L.ACT_NONE and len(parts) < 7 and
-                            h.buf.stride(0) == h.n and os.environ.get("MMLREC_GRAD_PARTS", "1") != "0")
-                for key, v, nc in (("h", h, 1), ("g", g, 0)):
-                    if key == "h" and use_part:
-                        part = plan.empty(plan.B, h.n)
-                        parts.append(part)
-                        gd.update(dh=part, act_h=L.ACT_NONE, acc_h=0, amax_dh=None)
-                        continue
-                    gv = plan.grad_of(v)
-                    acc = _claim(v)
-                    fold = (not acc and v.act != L.ACT_NONE and not v.deriv_applied and len(v.consumers) == nc)
-                    if fold:
-                        v.deriv_applied = True
-                    slot = None
-                    if plan.amax_pool is not None:
-                        if v.gamax is None:
-                            v.gamax = plan.new_amax()
-                        if v.gamax_writers == v.written - 1:
-                            v.gamax_writers += 1
-                            slot = v.gamax
-                    gd.update({"d" + key: gv, "act_" + key: v.act if fold else L.ACT_NONE, "acc_" + key: acc,
-                               "amax_d" + key: slot})
-                ch = chunks[0]
-                gp = [plan.weight_planes(q, ops.PLANES_COLS, ch) for q in ch]
-                if any(pl is None for pl, _ in gp):
-                    gp = [(None, None)] * len(ch)
-                # products that share a factor (the gated input feeds every task's first product) write the SAME
-                # gradient buffer, the first overwriting, the others adding: they must not run in one launch
-                wi = max(-1 if use_part else gate_wave.get(id(h), -1), gate_wave.get(id(g), -1)) + 1
-                gate_wave[id(g)] = wi
-                if not use_part:
-                    gate_wave[id(h)] = wi
-                while len(waves) <= wi:
-                    waves.append([])
-                waves[wi].append(dict(dA=gd["dh"], gate=gd, Y=None, act=L.ACT_NONE, mask=None, accumulate=0,
-                                     srcs=[(q["out"].grad, q["W"].data, q.get("w_kn", 0), q["amax_dc"], q["amax_w"]) +
-                                           ((pl, kx) if pl is not None else ()) for q, (pl, kx) in zip(ch, gp)]))
+        for x, qs in self._by_input(live):
+            if getattr(x, "gate", None) is not None:
+                self._dgrad_gate(plan, x, qs, waves, gate_wave)
                 continue
             plan.grad_of(x)
-            fuse = len(chunks) == 1 and len(x.consumers) == 1 and x.act != L.ACT_NONE
-            # columns of the input gradient somebody reads (Val.grad_cols): a narrower launch over the same buffers
-            gc = x.grad_cols if (0 < x.grad_cols < x.n and x.grad_cols % 16 == 0 and x.act == L.ACT_NONE and
-                                 all(isinstance(c, LinearGroupOp) for c in x.consumers) and
-                                 not any(q.get("w_kn", 0) for q in qs) and
-                                 os.environ.get("MMLREC_GRAD_COLS", "1") != "0") else 0
-            cut = (lambda t: t[:, :gc]) if gc else (lambda t: t)
-            # Small batches: an input fed by many layers (dnn_input: every expert and gate) is ONE problem with a long
-            # reduction -- 128 tiles of 72 k-steps at B = 4 096 on AE-30, 41 us on a chip with 256 CUs.  Its sources are
-            # dealt to up to four problems of the same launch (partial sums into scratch, one add afterwards): 4x the
-            # tiles, a quarter of the steps.  Only without an activation derivative in the epilogue (input layers).
-            ktot = sum(q["out"].n for q in qs)
-            if (plan.B <= 8192 and len(chunks) == 1 and len(qs) >= 2 and x.act == L.ACT_NONE and ktot >= 512 and
-                    os.environ.get("MMLREC_SPLIT_DGRAD", "1") != "0"):
-                nparts = min(4, len(qs))
-                parts = [[] for _ in range(nparts)]
-                for q in sorted(qs, key=lambda q_: -q_["out"].n):  # longest first into the lightest part
-                    min(parts, key=lambda p_: sum(r["out"].n for r in p_)).append(q)
-                acc = _claim(x)
-                padded = x.kpad and all("Wp" in q for q in qs)
-                g0 = cut(_padded_view(x.grad, x.kpad) if padded else x.grad)
-                pitch = x.grad.stride(0)
-                targets = [g0]
-                for _ in parts[1:]:
-                    t_ = plan.zeros(plan.B, pitch)
-                    targets.append(t_.as_strided(g0.shape, (pitch, 1)))
-                while len(waves) < 1:
-                    waves.append([])
-                for part, dst in zip(parts, targets):
-                    waves[0].append(dict(dA=dst, Y=None, act=L.ACT_NONE, mask=None, accumulate=acc if dst is g0 else 0,
-                                         srcs=[(q["out"].grad, cut(q["Wp"] if padded else q["W"].data), q.get("w_kn", 0),
-                                                q["amax_dc"], q["amax_w"]) for q in part]))
-                arr = ops._ptr_array([x.grad] + [t_ for t_ in targets[1:]])
-                plan.keep.append(arr)
-                post.append((lib.mml_ew_add_n, (arr, len(targets), x.grad.data_ptr(), plan.B * pitch),
-                             dict(kernel="ew_add_n_kernel", bytes=4.0 * plan.B * pitch * (len(targets) + 1))))
+            if self._splits(plan, x, qs):
+                post.append(self._dgrad_split(plan, x, qs, waves))
+            else:
+                self._dgrad_chunked(plan, x, qs, waves)
+        return calls + self._dgrad_calls(plan, waves) + post
+
+    def _wgrad_calls(self, plan, live):
+        """Weight / bias gradients: the partial-product launch, its reduction, and the copies that un-pad the gradients of
+        zero-padded weights -- all on the side list (only the optimizer reads them)."""
+        lib = L.load()
+        wg = []
+        for q in live:
+            W = q["W"]
+            if not W.needs_grad:
                 continue
-            for ci, ch in enumerate(chunks):
-                acc = _claim(x)
-                while len(waves) <= ci:
-                    waves.append([])
-                padded = x.kpad and all("Wp" in q for q in ch)  # every source reads the zero-padded weight copy
-                # this launch raises the magnitude slot of x.grad with what it stores (after derivative / accumulation)
-                if x.gamax is None and plan.amax_pool is not None:
-                    x.gamax = plan.new_amax()
-                if x.gamax is not None and x.gamax_writers == x.written - 1:
-                    x.gamax_writers += 1
-                    out_slot = x.gamax
-                else:
-                    out_slot = None
-                # the weights that feed this input gradient, cut as one group (common exponent)
-                gp = [plan.weight_planes(q, ops.PLANES_COLS, ch, padded=bool(padded)) for q in ch]
-                if any(pl is None for pl, _ in gp):
-                    gp = [(None, None)] * len(ch)
-                # a launch of the shape csrc/gemm_os.hip serves (mml_gemm_os_try_dgrad: its conditions) stores exactly
-                # x.grad's [B, n] region and raises the slot with the exact maximum of what it stored: GatherOp's
-                # deterministic scatter may take its fixed-point unit from it (tests/test_scatter_det_fused_gpu.py)
-                exact = (out_slot is not None and len(chunks) == 1 and not fuse and not padded and not gc and
-                         not x.kpad and plan.B >= 16384 and 192 <= x.n <= 256 and x.n % 4 == 0 and len(ch) >= 2 and
-                         all(pl is not None for pl, _ in gp) and not any(q.get("w_kn", 0) for q in ch) and
-                         all(q["out"].n % 16 == 0 for q in ch) and sum(q["out"].n for q in ch) >= 256 and
-                         x.grad.dtype == torch.float32 and x.grad.stride(0) % 4 == 0 and
-                         os.environ.get("MMLREC_GEMM_OS", "1")[:1] != "0")
-                waves[ci].append(dict(dA=cut(_padded_view(x.grad, x.kpad) if padded else x.grad),
-                                      Y=x.buf if fuse else None, act=x.act if fuse else L.ACT_NONE,
-                                      mask=x.mask if (fuse and x.act == L.ACT_RELU) else None,
-                                      accumulate=acc, amax_out=out_slot, exact_amax_of=x if exact else None,
-                                      srcs=[(q["out"].grad, cut(q["Wp"] if padded else q["W"].data), q.get("w_kn", 0),
-                                             q["amax_dc"], q["amax_w"]) + ((pl, kx) if pl is not None else ())
-                                            for q, (pl, kx) in zip(ch, gp)]))
-            if fuse:
-                x.deriv_applied = True
+            acc, dbias = self._claim_wb(q)
+            if "Ap" in q and not acc:
+                q["dWp"] = plan.empty(W.data.shape[0], q["Ap"].shape[1])
+                wg.append(dict(dC=q["out"].grad, A=q["Ap"], dW=q["dWp"], dbias=dbias,
+                               accumulate=0, w_kn=0, unpad=(q["dWp"], W.grad), amax_dc=q["amax_dc"],
+                               amax_a=q.get("amax_a")))
+                continue
+            wg.append(dict(dC=q["out"].grad, A=q["x"].buf, dW=W.grad, dbias=dbias,
+                           accumulate=acc, w_kn=q.get("w_kn", 0), amax_dc=q["amax_dc"], amax_a=q.get("amax_a")))
+        if not wg:
+            return []
+        descs = ops.make_wgrad_descs(wg)
+        nbytes = lib.mml_gemm_grouped_wgrad_workspace_bytes(descs, len(wg))
+        # own workspace: all partial-product launches of the step run before the first reduction (see Plan)
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=plan.device)
+        plan.keep += [descs, ws]
+        meta = dict(kernel=_gemm_symbol(False, False, [q["dW"].shape[1] for q in wg], 2, kreds=[plan.B],
+                                        tensors=[q["dC"] for q in wg] + [q["A"] for q in wg],
+                                        nrc_extents=[d for q in wg for d in q["dW"].shape]),
+                    flops=sum(2.0 * plan.B * q["dW"].numel() for q in wg), side=True, rank=0,
+                    hbm_bytes=_distinct_bytes([q["dC"] for q in wg] + [q["A"] for q in wg] + [q["dW"] for q in wg]))
+        calls = [(lib.mml_gemm_grouped_wgrad_phase, (descs, len(wg), ws.data_ptr(), ws.numel(), 1), meta),
+                 (lib.mml_gemm_grouped_wgrad_phase, (descs, len(wg), ws.data_ptr(), ws.numel(), 2),
+                  dict(kernel="slab_reduce", bytes=float(nbytes), side=True, rank=1))]
+        unpad = [q["unpad"] for q in wg if "unpad" in q]  # padded weight gradients -> the parameters' [N, K]
+        if unpad:
+            c = _copy2d_batch_call(plan, unpad)
+            call_meta(c)["side"] = True
+            calls.append(c)
+        return calls
+
+    @staticmethod
+    def _wave(waves, i):
+        while len(waves) <= i:
+            waves.append([])
+        return waves[i]
+
+    def _dgrad_gate(self, plan, x, qs, waves, gate_wave):
+        """K7: x = h (.) g was written by the epilogue of the GEMM that produced g; its gradient is not stored, this
+        problem writes the gradients of the two factors (gate mode)."""
+        if len(qs) > L.MAX_SRC or len(x.consumers) != 1 or x.kpad:
+            raise L.MMLError("a fused gate product must feed exactly one Linear group (<= MAX_SRC layers)")
+        h, g = x.gate
+        gd = dict(h=h.buf, g=g.buf)
+        # h shared by several products and able to take its gradient in parts (MulBatchOp(fwd_fused)): this
+        # problem writes a buffer of its own -- no accumulation, no order between the sharing problems
+        parts = getattr(h, "grad_parts", None)
+        # (at most seven: the summing launch takes eight terms per target -- parts + the plain gradient buffer a
+        # further reader would add to)
+        use_part = (parts is not None and h.act == L.ACT_NONE and len(parts) < 7 and
+                    h.buf.stride(0) == h.n and os.environ.get("MMLREC_GRAD_PARTS", "1") != "0")
+        for key, v, nc in (("h", h, 1), ("g", g, 0)):
+            if key == "h" and use_part:
+                part = plan.empty(plan.B, h.n)
+                parts.append(part)
+                gd.update(dh=part, act_h=L.ACT_NONE, acc_h=0, amax_dh=None)
+                continue
+            gv = plan.grad_of(v)
+            acc = _claim(v)
+            fold = (not acc and v.act != L.ACT_NONE and not v.deriv_applied and len(v.consumers) == nc)
+            if fold:
+                v.deriv_applied = True
+            gd.update({"d" + key: gv, "act_" + key: v.act if fold else L.ACT_NONE, "acc_" + key: acc,
+                       "amax_d" + key: plan.grad_slot(v)})
+        gp = self._planes_all_or_none([plan.weight_planes(q, ops.PLANES_COLS, qs) for q in qs])
+        # products that share a factor (the gated input feeds every task's first product) write the SAME
+        # gradient buffer, the first overwriting, the others adding: they must not run in one launch
+        wi = max(-1 if use_part else gate_wave.get(id(h), -1), gate_wave.get(id(g), -1)) + 1
+        gate_wave[id(g)] = wi
+        if not use_part:
+            gate_wave[id(h)] = wi
+        self._wave(waves, wi).append(dict(
+            dA=gd["dh"], gate=gd, Y=None, act=L.ACT_NONE, mask=None, accumulate=0,
+            srcs=[(q["out"].grad, q["W"].data, q.get("w_kn", 0), q["amax_dc"], q["amax_w"]) +
+                  ((pl, kx) if pl is not None else ()) for q, (pl, kx) in zip(qs, gp)]))
+
+    @staticmethod
+    def _grad_cols(x, qs):
+        """Columns of the input gradient somebody reads (Val.grad_cols), or 0 for all of them: a narrower launch over the
+        same buffers."""
+        return x.grad_cols if (0 < x.grad_cols < x.n and x.grad_cols % 16 == 0 and x.act == L.ACT_NONE and
+                               all(isinstance(c, LinearGroupOp) for c in x.consumers) and
+                               not any(q.get("w_kn", 0) for q in qs) and
+                               os.environ.get("MMLREC_GRAD_COLS", "1") != "0") else 0
+
+    @staticmethod
+    def _splits(plan, x, qs):
+        """Small batches: an input fed by many layers (dnn_input: every expert and gate) is ONE problem with a long
+        reduction -- 128 tiles of 72 k-steps at B = 4 096 on AE-30, 41 us on a chip with 256 CUs.  Its sources are
+        dealt to up to four problems of the same launch (partial sums into scratch, one add afterwards): 4x the
+        tiles, a quarter of the steps.  Only without an activation derivative in the epilogue (input layers)."""
+        return (plan.B <= 8192 and 2 <= len(qs) <= L.MAX_SRC and x.act == L.ACT_NONE and
+                sum(q["out"].n for q in qs) >= 512 and os.environ.get("MMLREC_SPLIT_DGRAD", "1") != "0")
+
+    def _dgrad_split(self, plan, x, qs, waves):
+        """The split problem (_splits): up to four problems of the first launch; returns the call that sums the parts."""
+        gc = self._grad_cols(x, qs)
+        cut = (lambda t: t[:, :gc]) if gc else (lambda t: t)
+        nparts = min(4, len(qs))
+        parts = [[] for _ in range(nparts)]
+        for q in sorted(qs, key=lambda q_: -q_["out"].n):  # longest first into the lightest part
+            min(parts, key=lambda p_: sum(r["out"].n for r in p_)).append(q)
+        acc = _claim(x)
+        padded = x.kpad and all("Wp" in q for q in qs)
+        g0 = cut(_padded_view(x.grad, x.kpad) if padded else x.grad)
+        pitch = x.grad.stride(0)
+        targets = [g0]
+        for _ in parts[1:]:
+            t_ = plan.zeros(plan.B, pitch)
+            targets.append(t_.as_strided(g0.shape, (pitch, 1)))
+        for part, dst in zip(parts, targets):
+            self._wave(waves, 0).append(dict(
+                dA=dst, Y=None, act=L.ACT_NONE, mask=None, accumulate=acc if dst is g0 else 0,
+                srcs=[(q["out"].grad, cut(q["Wp"] if padded else q["W"].data), q.get("w_kn", 0),
+                       q["amax_dc"], q["amax_w"]) for q in part]))
+        arr = ops._ptr_array([x.grad] + [t_ for t_ in targets[1:]])
+        plan.keep.append(arr)
+        return (L.load().mml_ew_add_n, (arr, len(targets), x.grad.data_ptr(), plan.B * pitch),
+                dict(kernel="ew_add_n_kernel", bytes=4.0 * plan.B * pitch * (len(targets) + 1)))
+
+    def _dgrad_chunked(self, plan, x, qs, waves):
+        """The plain problem: the layers that read x in chunks of MAX_SRC sources, chunk k in launch k."""
+        chunks = [qs[i:i + L.MAX_SRC] for i in range(0, len(qs), L.MAX_SRC)]
+        fuse = len(chunks) == 1 and len(x.consumers) == 1 and x.act != L.ACT_NONE
+        gc = self._grad_cols(x, qs)
+        cut = (lambda t: t[:, :gc]) if gc else (lambda t: t)
+        for ci, ch in enumerate(chunks):
+            acc = _claim(x)
+            padded = x.kpad and all("Wp" in q for q in ch)  # every source reads the zero-padded weight copy
+            # this launch raises the magnitude slot of x.grad with what it stores (after derivative / accumulation)
+            out_slot = plan.grad_slot(x)
+            # the weights that feed this input gradient, cut as one group (common exponent)
+            gp = self._planes_all_or_none([plan.weight_planes(q, ops.PLANES_COLS, ch, padded=bool(padded)) for q in ch])
+            # a launch that raises the slot and stores exactly x.grad's [B, n] region: if the output-stationary kernel
+            # serves it (_dgrad_calls asks the library), the slot holds the exact maximum of what was stored
+            exact = out_slot is not None and not x.kpad and not gc
+            self._wave(waves, ci).append(dict(
+                dA=cut(_padded_view(x.grad, x.kpad) if padded else x.grad),
+                Y=x.buf if fuse else None, act=x.act if fuse else L.ACT_NONE,
+                mask=x.mask if (fuse and x.act == L.ACT_RELU) else None,
+                accumulate=acc, amax_out=out_slot, exact_amax_of=x if exact else None,
+                srcs=[(q["out"].grad, cut(q["Wp"] if padded else q["W"].data), q.get("w_kn", 0),
+                       q["amax_dc"], q["amax_w"]) + ((pl, kx) if pl is not None else ())
+                      for q, (pl, kx) in zip(ch, gp)]))
+        if fuse:
+            x.deriv_applied = True
+
+    @staticmethod
+    def _dgrad_calls(plan, waves):
+        """One mml_gemm_grouped_dgrad call per wave of input-gradient problems."""
+        lib = L.load()
+        calls = []
         for dg in waves:
             descs = ops.make_dgrad_descs(dg)
             plan.keep.append(descs)
-            if len(dg) == 1 and dg[0].get("exact_amax_of") is not None:  # (that kernel takes one problem per launch)
-                dg[0]["exact_amax_of"].gamax_exact = True
+            # csrc/gemm_os.hip (one problem per launch) raises the slot with the exact maximum of what it stored:
+            # GatherOp's deterministic scatter may take its fixed-point unit from it
+            # (tests/test_scatter_det_fused_gpu.py).  Whether that kernel runs is the library's decision.
+            x = dg[0].get("exact_amax_of") if len(dg) == 1 else None
+            if x is not None and lib.mml_gemm_os_serves(descs, len(dg)):
+                x.gamax_exact = True
             kn = dg[0]["srcs"][0][2]
             meta = dict(kernel=_gemm_symbol(True, bool(kn), [q["dA"].shape[1] for q in dg], 1,
                                             kreds=[sr[0].shape[1] for q in dg for sr in q["srcs"]],
@@ -1622,7 +1687,7 @@ class LinearGroupOp(Op):
                         hbm_bytes=_distinct_bytes([q["dA"] for q in dg] + [q.get("mask") for q in dg] +
                                                   [t_ for q in dg for sr in q["srcs"] for t_ in sr[:2]]))
             calls.append((lib.mml_gemm_grouped_dgrad, (descs, len(dg)), meta))
-        return calls + post
+        return calls
 
 
 class GateGroupOp(Op):
@@ -1692,14 +1757,10 @@ class GateGroupOp(Op):
         grp = ops.make_gate_group([e.buf for e in self.experts], gl, plan.B, self.H, d_experts=dE, e_relu=e_relu)
         # magnitudes of what the kernel stores: one slot for every expert gradient, one for every gate-input gradient
         # (this op is the only writer of each of them: checked above)
-        s_de, s_dg = plan.new_amax(), plan.new_amax()
+        s_de = plan.shared_grad_slot(self.experts)
+        s_dg = plan.shared_grad_slot([g["G"] for g in self.gates if g["mix"].grad is not None])
         if s_de is not None:
             grp.amax_dE, grp.amax_dG = s_de.data_ptr(), s_dg.data_ptr()
-            for e in self.experts:
-                e.gamax, e.gamax_writers = s_de, e.written
-            for g in self.gates:
-                if g["mix"].grad is not None:
-                    g["G"].gamax, g["G"].gamax_writers = s_dg, g["G"].written
         nws = int(lib.mml_gate_mix_bwd_workspace_bytes(C.byref(grp)))
         # (deferred reduction: the partial sums must survive until the side list runs -- a buffer of this op's own, not the
         # shared scratch every other call overwrites)
@@ -1719,7 +1780,19 @@ class GateGroupOp(Op):
                  dict(kernel="gate_bwd_kernel", bytes=byts))]
 
 
-_DEFER = None  # set by trainer.TrainStep around the recording of its plan (one stream: True)
+_DEFER = None  # inside deferred_reductions(on): `on`
+
+
+@contextlib.contextmanager
+def deferred_reductions(on):
+    """While a plan is recorded inside this block, GateGroupOp / HeadOp defer their reductions iff `on`
+    (trainer.TrainStep: a step that runs as ONE list); MMLREC_DEFER_REDUCE still overrides (_defer_reduce)."""
+    global _DEFER
+    prev, _DEFER = _DEFER, on
+    try:
+        yield
+    finally:
+        _DEFER = prev
 
 
 def _defer_reduce():
@@ -1783,10 +1856,8 @@ class HeadOp(Op):
                         if _claim(G):
                             raise L.MMLError("gated head: the gate's gradient has another writer")
                         G.deriv_applied = True   # (the kernel multiplies act'(gate) in)
-                        if plan.amax_pool is not None:  # ONE slot for all gates' gradients
-                            if getattr(self, "_amax_dG", None) is None:
-                                self._amax_dG = plan.new_amax()
-                            G.gamax, G.gamax_writers = self._amax_dG, 1
+                        # ONE slot for all gates' gradients
+                        self._amax_dG = plan.shared_grad_slot([G], getattr(self, "_amax_dG", None))
                 if sole:
                     q["dH"] = plan.grad_of(Hin)
                     q["h_relu"] = int(Hin.act == L.ACT_RELU)
@@ -1795,10 +1866,8 @@ class HeadOp(Op):
                     if claim:
                         _claim(Hin)
                         Hin.deriv_applied = True
-                        if Hin.written == 1 and plan.amax_pool is not None:  # the kernel raises ONE slot for all dH
-                            if getattr(self, "_amax_dH", None) is None:
-                                self._amax_dH = plan.new_amax()
-                            Hin.gamax, Hin.gamax_writers = self._amax_dH, 1
+                        if Hin.written == 1:  # the kernel raises ONE slot for all dH
+                            self._amax_dH = plan.shared_grad_slot([Hin], getattr(self, "_amax_dH", None))
                 else:
                     tmp = h.setdefault("_dH_tmp", plan.empty(plan.B, Hin.n))
                     q["dH"], q["h_relu"] = tmp, 0
@@ -2071,15 +2140,9 @@ class PReluBatchOp(Op):
             acc = _claim(z)
             if id(a) not in acc_da:  # (later items of the slope: the launch sums them behind the first)
                 acc_da[id(a)] = _claim(a)
-            slot = None  # magnitude of the gradient as stored (tracked like a dgrad GEMM's amax_out)
-            if plan.amax_pool is not None:
-                if z.gamax is None:
-                    z.gamax = plan.new_amax()
-                if z.gamax_writers == z.written - 1:
-                    z.gamax_writers += 1
-                    slot = z.gamax
+            # (amax: magnitude of the gradient as stored, tracked like a dgrad GEMM's amax_out)
             rows.append(dict(dy=y.grad, z=z.buf, dz=g, alpha=a.data, dalpha=a.grad, acc_dz=acc,
-                             acc_dalpha=acc_da[id(a)], amax=slot))
+                             acc_dalpha=acc_da[id(a)], amax=plan.grad_slot(z)))
         calls, seen = [], set()
         for ch in ops.prelu_chunks(rows):
             arr = ops.make_prelu_bwd_descs(ch, seen)
@@ -2337,60 +2400,14 @@ class SplitOp(Op):
         return []
 
 
-class MulOp(Op):
-    """out = a * b on whole contiguous [B,n] buffers (PepNet gating, model/pepnet.py:77, :140)."""
-
-    def __init__(self, a, b, out):
-        self.a, self.b, self.out = a, b, out
-        self.flat = self._flat_numel((a, b, out))
-
-    @staticmethod
-    def _flat_numel(vals):
-        """The flat kernels run over whole buffers: contiguous [B, n], or rows of one common zero-padded pitch."""
-        if all(v.buf.is_contiguous() for v in vals):
-            return vals[0].buf.numel()
-        st = vals[0].buf.stride(0)
-        if all(v.kpad == st and v.buf.stride(0) == st and v.n == vals[0].n for v in vals):
-            return vals[0].buf.shape[0] * st
-        raise L.MMLError("MulOp needs contiguous buffers (or one common zero-padded pitch)")
-
-    def inputs(self):
-        return [self.a, self.b]
-
-    def outputs(self):
-        return [self.out]
-
-    def fwd_calls(self, plan):
-        return [(L.load().mml_ew_mul, (self.a.buf.data_ptr(), self.b.buf.data_ptr(), self.out.buf.data_ptr(),
-                                       self.flat), dict(kernel="ew_mul_kernel", bytes=12.0 * self.flat))]
-
-    def bwd_calls(self, plan):
-        if self.out.grad is None:
-            return []
-        if self.out.grad.stride(0) != self.out.buf.stride(0):
-            raise L.MMLError("MulOp: value / gradient pitch mismatch")
-        da = db = None
-        acc_a = acc_b = 0
-        if self.a.needs_grad:
-            da = plan.grad_of(self.a)
-            acc_a = _claim(self.a)
-        if self.b.needs_grad:
-            db = plan.grad_of(self.b)
-            acc_b = _claim(self.b)
-        if da is None and db is None:
-            return []
-        # an operand that is an activation's output and feeds nothing else: fold act' into the gradient written here
-        # (Plan.finish would otherwise add a separate read-modify-write pass over it)
-        acts = []
-        for v, g, acc in ((self.a, da, acc_a), (self.b, db, acc_b)):
-            fold = (g is not None and not acc and v.act != L.ACT_NONE and not v.deriv_applied and
-                    len(v.consumers) == 1)
-            acts.append(v.act if fold else L.ACT_NONE)
-            if fold:
-                v.deriv_applied = True
-        return [(L.load().mml_ew_mul_bwd_act, (self.out.grad.data_ptr(), self.a.buf.data_ptr(), self.b.buf.data_ptr(),
-                                               L.ptr(da), L.ptr(db), acc_a, acc_b, self.flat, acts[0], acts[1]),
-                 dict(kernel="ew_mul_bwd_kernel", bytes=4.0 * self.flat * (3 + (da is not None) + (db is not None))))]
+def _flat_numel(vals):
+    """The flat kernels run over whole buffers: contiguous [B, n], or rows of one common zero-padded pitch."""
+    if all(v.buf.is_contiguous() for v in vals):
+        return vals[0].buf.numel()
+    st = vals[0].buf.stride(0)
+    if all(v.kpad == st and v.buf.stride(0) == st and v.n == vals[0].n for v in vals):
+        return vals[0].buf.shape[0] * st
+    raise L.MMLError("a flat product needs contiguous buffers (or one common zero-padded pitch)")
 
 
 class MulBatchOp(Op):
@@ -2402,7 +2419,7 @@ class MulBatchOp(Op):
 
     def __init__(self, items, fwd_fused=False):
         self.items = items
-        self.flat = [MulOp._flat_numel(it) for it in items]
+        self.flat = [_flat_numel(it) for it in items]
         # True: the products themselves leave the epilogue of the GEMM that produces b (LinearGroupOp problems with mul /
         # prod and prod_bwd = "ext": K7 forward); this op only contributes the backward
         self.fwd_fused = bool(fwd_fused)
@@ -2468,13 +2485,9 @@ class MulBatchOp(Op):
             fold = (not acc and v.act != L.ACT_NONE and not v.deriv_applied and len(v.consumers) == 1)
             if fold:
                 v.deriv_applied = True
-            slot = None  # magnitude of the gradient as stored (tracked like a dgrad GEMM's amax_out)
-            if plan.amax_pool is not None and g.stride(0) == v.n:
-                if v.gamax is None:
-                    v.gamax = plan.new_amax()
-                if v.gamax_writers == v.written - 1:
-                    v.gamax_writers += 1
-                    slot = v.gamax
+            # magnitude of the gradient as stored (tracked like a dgrad GEMM's amax_out): this flat launch can raise it
+            # only when it covers no padding columns
+            slot = plan.grad_slot(v) if g.stride(0) == v.n else None
             rows.append((g, n, terms, acc, v.act if fold else L.ACT_NONE, v.buf, slot))
             nbytes += 4.0 * n * (2 * len(terms) + 1 + (1 if (acc or fold) else 0))
         if not rows:
@@ -2497,31 +2510,6 @@ class CopyColsOp(Op):
             return [_copy2d_batch_call(plan, [(self.src, self.dst)], amax=[self.amax_out])]
         return [(L.load().mml_copy2d, (self.src.data_ptr(), ops._ld(self.src), self.dst.data_ptr(), ops._ld(self.dst),
                                        plan.B, self.src.shape[1], 0))]
-
-
-class PMulOp(Op):
-    """Derived parameter out = a * b (STAR: specific * shared weight, model/utils.py:215)."""
-
-    def __init__(self, a, b, out):
-        self.a, self.b, self.out = a, b, out
-
-    def fwd_calls(self, plan):
-        return [(L.load().mml_ew_mul, (self.a.data.data_ptr(), self.b.data.data_ptr(), self.out.data.data_ptr(),
-                                       self.out.data.numel()))]
-
-    def bwd_calls(self, plan):
-        if not self.out.written:
-            return []
-        da = self.a.grad if self.a.needs_grad else None
-        db = self.b.grad if self.b.needs_grad else None
-        if da is None and db is None:
-            return []
-        acc_a = _claim(self.a) if da is not None else 0
-        acc_b = _claim(self.b) if db is not None else 0
-        # consumes a weight gradient -> belongs behind the wgrad GEMMs on the side list
-        return [(L.load().mml_ew_mul_bwd, (self.out.grad.data_ptr(), self.a.data.data_ptr(), self.b.data.data_ptr(),
-                                           L.ptr(da), L.ptr(db), acc_a, acc_b, self.out.data.numel()),
-                 dict(kernel="ew_mul_bwd_kernel", side=True))]
 
 
 class SumProdBatchOp(Op):

@@ -65,8 +65,8 @@ class Segments:
                 item[1](*item[2])
             elif graph is not None:
                 if profiling.enabled:
-                    with profiling.range("hip_graph[%d calls: %s ...]" % (len(item), (item[0][2] if len(item[0]) > 2 and
-                                         isinstance(item[0][2], dict) else {}).get("kernel", getattr(item[0][0], "__name__", "inline")))):
+                    with profiling.range("hip_graph[%d calls: %s ...]" % (
+                            len(item), E.call_meta(item[0]).get("kernel", getattr(item[0][0], "__name__", "inline")))):
                         graph.replay()
                 else:
                     graph.replay()
@@ -97,8 +97,7 @@ def fork_conflicts(side_calls, mid_calls, shared_scratch=()):
                     out.add(a)
             # (buffers a call reads or writes through its descriptors and names in its meta: the 64-bit totals and the
             # magnitude slot the deterministic scatter hands to the table optimizer)
-            if isinstance(c[-1], dict):
-                out.update(int(p) for p in c[-1].get("ptrs", ()))
+            out.update(int(p) for p in E.call_meta(c).get("ptrs", ()))
         return out
     a, b = ptrs(side_calls), ptrs(mid_calls)
     scratch = {int(x) for x in shared_scratch if x}
@@ -208,17 +207,13 @@ class TrainStep:
         marked = (self.opt.table_update == "dense_exact" and not split and
                   (par is None or par.mode in ("row_sharded", "replicated")) and
                   os.environ.get("MMLREC_GRAD_MARKS", "1") != "0" and not os.environ.get("MMLREC_SCATTER_OLD"))
-        from . import engine as _E
         # one stream (and no split table update, whose early pass forks anyway): the reductions of the head / gate kernels'
         # partial sums are deferred behind the backward chain and merged into ONE launch (Plan.merge_row_reduces)
         one_list = not overlap and not split and os.environ.get("MMLREC_MERGE_REDUCES", "1") != "0"
-        _E._DEFER = one_list
-        try:
+        with E.deferred_reductions(one_list):
             self.plan = model._record(B, True, False, self.store, sparse_rows=None if (lazy or split) else rows,
                                       lazy=lazy or split, mark_rows=rows if (split and par is None) else None,
                                       grad_marks=marked)
-        finally:
-            _E._DEFER = None
         if one_list:
             # the top of the network -- last tower layer, heads + BCE, the towers' input gradient -- as one launch where
             # the recorded lists hold that pattern (csrc/tower_head.hip; before the reductions are merged: it brings its own)
@@ -290,7 +285,7 @@ class TrainStep:
         self.front = Segments(([] if self.split_dense else self.opt_split["pre"]) + p.fwd[n_lead:] + p.head_train +
                               (p.bwd[:k] if k else p.bwd), self.use_graph)
         self.front_b = Segments(p.bwd[k:], self.use_graph, min_calls=1) if k else None
-        side_a = [c for c in p.bwd_side if c[-1].get("ready", 1 << 30) <= k] if k else []
+        side_a = [c for c in p.bwd_side if E.call_meta(c).get("ready", 1 << 30) <= k] if k else []
         self.side_a = Segments(side_a, self.use_graph, min_calls=1) if k else None
         self.ev_fork_a = torch.cuda.Event() if k else None
         self.early_fork = k
@@ -347,7 +342,7 @@ class TrainStep:
 
     @staticmethod
     def _cost(c):
-        meta = c[-1] if isinstance(c[-1], dict) else {}
+        meta = E.call_meta(c)
         return 4e-6 + meta.get("flops", 0.0) / 5e14 + meta.get("bytes", 0.0) / 4e12
 
     def _early_fork(self, p, B):
@@ -356,7 +351,7 @@ class TrainStep:
         n > 0 = that index, "auto" = where the side calls that are ready by then take about as long as the rest of the
         chain -- but only when the tail has no dense table stream of the same length to put them beside."""
         env = os.environ.get("MMLREC_EARLY_WGRAD", "0")
-        ready = [c[-1].get("ready") for c in p.bwd_side]
+        ready = [E.call_meta(c).get("ready") for c in p.bwd_side]
         if env == "0" or not p.bwd_side or any(r is None for r in ready) or any(c[0] is E.PY for c in p.bwd):
             return 0
         if ready != sorted(ready):  # (program order: a later side call is never ready before an earlier one)

@@ -130,3 +130,64 @@ def test_os_dgrad_is_repeatable_on_a_full_chip(env):
         assert name == "gemm_os_kernel"
         assert torch.equal(dA, ref), (rep, int((dA != ref).sum()))
         assert float(torch.max(am.view(torch.float32))) == float(torch.max(amt.view(torch.float32))), rep
+
+
+# ---- mml_gemm_os_serves: the library's own answer to "does gemm_os_kernel run this launch?" ---------------------------
+def _recut(torch, ops, src, layout, group_slots, kexp):
+    """The source with planes cut anew (same magnitudes) into a buffer / exponent word of its own."""
+    dC, W, kn, sd, sw = src[:5]
+    planes = torch.zeros(tuple(W.shape), dtype=torch.int32, device=W.device)
+    ops.planes_cut([(W, planes, layout, group_slots, kexp)])
+    return (dC, W, kn, sd, sw, planes, kexp)
+
+
+def _os_case(torch, L, ops, mp, lib, what):
+    """The problems of one case: the smallest launch the kernel takes -- M = 16384, K = 192, two sources of N = 128, planes
+    cut with one exponent -- with ONE of its conditions broken."""
+    M, K, Ns = 16384, 192, [128, 128]
+    if what == "short batch":
+        M -= 128
+    elif what == "narrow gradient":
+        K = 188
+    elif what == "one source":
+        Ns = [256]
+    elif what == "short reduction":
+        Ns = [128, 112]
+    prob, _ = launch(torch, L, ops, M, K, Ns, seed=21)
+    dev = torch.device("cuda:0")
+    prob = dict(prob, dA=torch.empty(M, K, device=dev), accumulate=0)
+    wslots = [s[4] for s in prob["srcs"]]
+    if what == "[K, N] weights":   # (read along a row: the MML_PLANES_ROWS image, as STAR's layers hand them over)
+        prob["srcs"] = [_recut(torch, ops, (s[0], s[1].t().contiguous(), 1, s[3], s[4]), ops.PLANES_ROWS, wslots, s[6])
+                        for s in prob["srcs"]]
+    elif what == "no planes":
+        prob["srcs"] = [s[:5] for s in prob["srcs"]]
+    elif what == "two exponent words":
+        other = torch.zeros(1, dtype=torch.int32, device=dev)
+        prob["srcs"][1] = _recut(torch, ops, prob["srcs"][1], ops.PLANES_COLS, wslots, other)
+    elif what == "relu epilogue":
+        prob.update(Y=torch.randn(M, K, device=dev), act=L.ACT_RELU)
+    probs = [prob]
+    if what == "two problems":
+        second, _ = launch(torch, L, ops, M, K, Ns, seed=22)
+        probs.append(dict(second, dA=torch.empty(M, K, device=dev), accumulate=0))
+    if what == "MMLREC_GEMM_OS=0":
+        mp.setenv("MMLREC_GEMM_OS", "0")
+    if what == "gemm mode 0":
+        lib.mml_gemm_set_mode(0)   # (the env fixture's teardown restores the mode)
+    return probs
+
+
+@pytest.mark.parametrize("what", ["served", "short batch", "narrow gradient", "one source", "short reduction",
+                                  "[K, N] weights", "no planes", "two exponent words", "relu epilogue", "two problems",
+                                  "MMLREC_GEMM_OS=0", "gemm mode 0"])
+def test_os_serves_is_the_dispatch_of_grouped_dgrad(env, what):
+    torch, L, ops, lib, mp = env
+    probs = _os_case(torch, L, ops, mp, lib, what)
+    arr = ops.make_dgrad_descs(probs)
+    says = lib.mml_gemm_os_serves(arr, len(probs))
+    L.check(lib.mml_gemm_grouped_dgrad(arr, len(probs), ops._stream()), "mml_gemm_grouped_dgrad")
+    torch.cuda.synchronize()
+    name = lib.mml_gemm_last_kernel().decode()
+    assert says in (0, 1) and (says == 1) == (name == "gemm_os_kernel"), (what, says, name)
+    assert says == (1 if what == "served" else 0), (what, says, name)

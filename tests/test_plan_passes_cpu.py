@@ -228,3 +228,68 @@ def test_fork_conflicts_sees_shared_scratch_and_common_pointers():
     assert trainer.fork_conflicts(side, mid2) == [0x7f0000100000]                                     # a common pointer
     assert trainer.fork_conflicts([(f, (64, 1, True))], [(f, (64, 1))]) == []                         # small integers are sizes
     assert trainer.fork_conflicts([(f, (0x10000, 1 << 24))], [(f, (0x10000, 1 << 24))]) == []         # ... a batch of 65 536 rows too
+
+
+# ---- the gradient-magnitude slot protocol (Plan.grad_slot / shared_grad_slot / grad_amax) -----------------------------
+@pytest.fixture()
+def slot_plan():
+    import torch
+    import mmlrec_amd  # noqa: F401
+    from mmlrec_amd import engine as E
+    plan = E.Plan(torch.device("cpu"), 4, True)
+    plan.amax_pool = torch.zeros(8)  # (a CPU plan has no pool of its own)
+    return E, plan, E.Val(torch.zeros(4, 8), name="v")
+
+
+def same_slot(a, b):
+    return a is not None and b is not None and a.data_ptr() == b.data_ptr()
+
+
+def test_grad_slot_one_writer(slot_plan):
+    E, plan, v = slot_plan
+    E._claim(v)
+    slot = plan.grad_slot(v)
+    assert slot is not None
+    need = []
+    assert same_slot(plan.grad_amax(v, need), slot) and need == []
+    assert plan.amax_next == 1
+
+
+def test_grad_slot_two_writers_both_raise(slot_plan):
+    E, plan, v = slot_plan
+    assert E._claim(v) == 0
+    first = plan.grad_slot(v)
+    assert E._claim(v) == 1
+    second = plan.grad_slot(v)
+    assert same_slot(first, second)
+    need = []
+    assert same_slot(plan.grad_amax(v, need), first) and need == []
+    assert plan.amax_next == 1
+
+
+def test_grad_slot_foreign_writer_in_between(slot_plan):
+    E, plan, v = slot_plan
+    E._claim(v)
+    first = plan.grad_slot(v)
+    assert first is not None
+    E._claim(v)  # a writer that raises no slot
+    E._claim(v)
+    assert plan.grad_slot(v) is None  # (the count fell behind: nobody may vouch for the slot any more)
+    need = []
+    fresh = plan.grad_amax(v, need)
+    assert fresh is not None and not same_slot(fresh, first)
+    assert len(need) == 1 and need[0][0] is v.grad and same_slot(need[0][1], fresh)
+
+
+def test_shared_grad_slot(slot_plan):
+    E, plan, v = slot_plan
+    import torch
+    w = E.Val(torch.zeros(4, 8), name="w")
+    for x in (v, w):
+        E._claim(x)
+    slot = plan.shared_grad_slot([v, w])
+    assert same_slot(plan.shared_grad_slot([v], slot), slot) and plan.amax_next == 1
+    need = []
+    assert same_slot(plan.grad_amax(v, need), slot) and same_slot(plan.grad_amax(w, need), slot) and need == []
+    plan.amax_pool = None
+    assert plan.grad_slot(v) is None and plan.shared_grad_slot([v]) is None
