@@ -978,6 +978,48 @@ int mml_prelu_batch_fwd(const mml_prelu_desc* d, int32_t n, mml_stream_t stream)
 int64_t mml_prelu_workspace_bytes(int32_t n);
 int mml_prelu_batch_bwd(const mml_prelu_bwd_desc* d, int32_t n, void* workspace, int64_t workspace_bytes,
                         mml_stream_t stream);
+/* PCGrad gradient surgery (model/optimizer.py:10-138) over T per-objective gradients g_0 .. g_{T-1}, each the flattened
+ * gradient of ALL parameters.  Every projected gradient stays in the span of the originals, pc_i = sum_k c_ik g_k, so:
+ *   mml_pcgrad_gram    : ONE pass over the banks -> the T x T Gram matrix G[k][j] = <g_k, g_j> (double, symmetric)
+ *   mml_pcgrad_weights : the projection loop (:50-55) as a recursion on the coefficients, in double: for i ascending,
+ *                        c_i = e_i; for j in order[i*T ..]: d = sum_k c_i[k] G[k][j]; d < 0: c_i[j] -= d / G[j][j]
+ *                        (G[j][j] == 0 can only meet d == 0: no division).  w[k] = (1/T) sum_i c_ik (mean weights),
+ *                        w[T + k] = sum_i c_ik (sum weights), fp32; fired[i*T + j] = 1 where a projection happened, else 0.
+ *   mml_pcgrad_combine : out = sum_k w'[k] bank_k per element, fp32, acc = 0 then acc = fma(w'[k], bank_k, acc) with k
+ *                        ascending; w' = the mean weights where EVERY bank of the segment is non-NULL (:58), the sum
+ *                        weights otherwise (:65); a NULL bank contributes nothing.  out may be one of the banks.
+ * A segment is one parameter tensor: bank[t] = objective t's gradient [rows, cols] with row pitch ld (shared by the banks
+ * and out), or NULL = the objective has no gradient there (zeros).  row_marks (optional, one byte per row): rows whose
+ * byte is 0 hold zeros in every bank -- they are not read, and combine does not write them.  `s` is a HOST array of any
+ * length n >= 1.  16-byte accesses where ld % 4 == 0 and every pointer of the segment is 16-byte aligned, single elements
+ * otherwise.  gram takes the fp32 products in double (exact) and adds them in a fixed order -- lane, wave, workgroup
+ * partials in the workspace (mml_pcgrad_workspace_bytes), one ordered final sum -- with no float atomics: two launches on
+ * the same inputs give the same bits.  `order` ([T*T] int32, row i = the order in which g_i meets the g_j), gram, w
+ * and fired are DEVICE pointers.
+ * MML_ERR_ARG: T < 1, T > MML_PCGRAD_MAX_TASKS, n < 1, a null array, rows < 0, cols < 1, ld < cols, a segment whose banks
+ * are all NULL, a null out (combine), a workspace that is null or too small.  (The entries of `order` are device data
+ * and are not checked: an entry outside [0, T) is skipped by the kernel.) */
+#define MML_PCGRAD_MAX_TASKS 8
+typedef struct mml_pcgrad_seg {
+  const float* bank[MML_PCGRAD_MAX_TASKS];
+  float* out;
+  int64_t rows;
+  int64_t ld;
+  int32_t cols;
+  int32_t pad_;
+  const uint8_t* row_marks;
+} mml_pcgrad_seg;
+int64_t mml_pcgrad_workspace_bytes(const mml_pcgrad_seg* s, int32_t n, int32_t T);
+int mml_pcgrad_gram(const mml_pcgrad_seg* s, int32_t n, int32_t T, double* gram, void* workspace,
+                    int64_t workspace_bytes, mml_stream_t stream);
+int mml_pcgrad_weights(const double* gram, const int32_t* order, int32_t T, float* w, int32_t* fired,
+                       mml_stream_t stream);
+int mml_pcgrad_combine(const mml_pcgrad_seg* s, int32_t n, int32_t T, const float* w, mml_stream_t stream);
+/* One objective's gradient leaves the buffers the backward writes: out = bank[0] over the rows of every segment (the
+ * marked rows where row_marks is given; the other banks are ignored), and with clear != 0 those rows of bank[0] are
+ * zeroed behind the copy -- the table accumulators the scatter adds into start the next objective's pass at zero.
+ * MML_ERR_ARG as for mml_pcgrad_combine with T = 1, and for out == bank[0]. */
+int mml_pcgrad_stash(const mml_pcgrad_seg* s, int32_t n, int32_t clear, mml_stream_t stream);
 /* DomainBatchNorm (model/utils.py:553-636; STAR applies it after its first star layer when forward() is given a domain
  * mask, model/star.py:50-51).  gamma / beta are unregistered there, frozen at (1, 0).  Training mode normalises with
  * the statistics of the WHOLE batch for every domain (= mml_bn_fwd with gamma 1 / beta 0; the caller issues that) and

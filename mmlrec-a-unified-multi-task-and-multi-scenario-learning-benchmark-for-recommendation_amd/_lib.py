@@ -165,6 +165,14 @@ class PreluBwdDesc(C.Structure):
                 ("accumulate_dalpha", i32), ("amax_out", fp)]
 
 
+PCGRAD_MAX_TASKS = 8
+
+
+class PcgradSeg(C.Structure):
+    _fields_ = [("bank", fp * PCGRAD_MAX_TASKS), ("out", fp), ("rows", i64), ("ld", i64), ("cols", i32), ("pad_", i32),
+                ("row_marks", fp)]
+
+
 class SumProdDesc(C.Structure):
     _fields_ = [("out", fp), ("x", fp * 8), ("y", fp * 8), ("n", i64), ("n_terms", i32), ("accumulate", i32),
                 ("deriv_of", fp), ("act", i32), ("pad_", i32), ("amax_out", fp)]
@@ -263,6 +271,11 @@ _SIGS = {
     "mml_prelu_batch_fwd": (C.c_int, [_PP(PreluDesc), i32, fp]),
     "mml_prelu_workspace_bytes": (i64, [i32]),
     "mml_prelu_batch_bwd": (C.c_int, [_PP(PreluBwdDesc), i32, fp, i64, fp]),
+    "mml_pcgrad_workspace_bytes": (i64, [_PP(PcgradSeg), i32, i32]),
+    "mml_pcgrad_gram": (C.c_int, [_PP(PcgradSeg), i32, i32, fp, fp, i64, fp]),
+    "mml_pcgrad_weights": (C.c_int, [fp, fp, i32, fp, fp, fp]),
+    "mml_pcgrad_combine": (C.c_int, [_PP(PcgradSeg), i32, i32, fp, fp]),
+    "mml_pcgrad_stash": (C.c_int, [_PP(PcgradSeg), i32, i32, fp]),
     "mml_auc_segments": (C.c_int, [fp, i64, fp, i64, i64, i32, i32, fp, fp]),
     "mml_bn_workspace_bytes": (C.c_int64, [i64, i32]),
     "mml_bn_fwd": (C.c_int, [fp, i64, fp, fp, fp, fp, fp, fp, fp, fp, i64, i64, i32, i32, i32, C.c_float, C.c_float, fp,

@@ -94,7 +94,7 @@ def _claim(x):
 
 
 class Plan:
-    def __init__(self, device, B, training):
+    def __init__(self, device, B, training, use_amax=None):
         self.device, self.B, self.training = device, int(B), bool(training)
         self.ops = []
         self.fwd, self.head_infer, self.head_train, self.head_bwd, self.bwd = [], [], [], [], []
@@ -131,6 +131,11 @@ class Plan:
         # below.  MMLREC_AMAX=0 / 1 forces.
         env = os.environ.get("MMLREC_AMAX", "")
         self.use_amax = (env != "0") and (env == "1" or self.B >= 32768)
+        if use_amax is False:
+            # (a PCGrad per-task plan replays its backward once per objective: the gradient slots only ever rise within a
+            # step, so a later pass would cut its operands with an earlier pass's magnitudes)
+            self.use_amax = False
+        self.pcgrad_T = 0  # > 0: the plan of a PCGrad per-task step (trainer.PCGradSchedule) over that many objectives
         # bf16-STORAGE path (round 5, include/mmlrec.h K3'; BASELINE.json configs[1]): under the opt-in reduced-precision
         # GEMM mode 1 (operands rounded to bf16) the values and gradients that only GEMMs read are STORED as bf16 and the
         # layer groups that read them run csrc/gemm16.hip -- same products, half the activation traffic, no conversion in
@@ -1109,8 +1114,9 @@ class GatherOp(Op):
                 flags |= L.SCATTER_DET_AMAX_SUPPLIED
             # the totals stay in acc64 for the ONE marked streaming launch of the dense table optimizer
             self.det_deferred = None
+            # (never in a PCGrad per-task plan: its banks take the fp32 rows of every pass)
             if (fused and type(self) is GatherOp and self.grad_marks is not None and sr is None and
-                    len(self.tables) <= L.MAX_OPT_TENSORS and
+                    not getattr(plan, "pcgrad_T", 0) and len(self.tables) <= L.MAX_OPT_TENSORS and
                     sum(t.data.numel() for t in self.tables) >= (1 << 24)):
                 flags |= L.SCATTER_DET_DEFER_TOTALS
                 self.det_deferred = dict(slot=slot, shift=int(lib.mml_scatter_det_shift(plan.B)))
@@ -3054,3 +3060,82 @@ class Optimizer:
             s1, s2 = self.state[n]
             ops.opt_catchup_dense(self.store.pvals[n].data, s1, s2 if self.kind == "adam" else None, self.last[n], hyper)
         self.dirty = False
+
+
+# ---- PCGrad per-task step (reference model/optimizer.py:10-138; trainer.PCGradSchedule) --------------------------------
+def _op_edges(op):
+    """[(output Vals, input Vals, PVals)] of an op, one entry per independent problem of a grouped launch: the edges the
+    reference's autograd graph would have."""
+    if isinstance(op, GatherOp):
+        return [([op.out], [], list(op.tables))]
+    if isinstance(op, LinearGroupOp):
+        edges = []
+        for q in op.p:
+            mul = q.get("mul")
+            edges.append(([q["out"]] + ([q["prod"]] if mul is not None else []),
+                          [q["x"]] + ([mul] if mul is not None else []),
+                          [q["W"]] + ([q["b"]] if q.get("b") is not None else [])))
+        return edges
+    if isinstance(op, GateGroupOp):
+        return [([g["mix"]], [op.experts[i] for i in g["expert"]] + [g["G"]], [g["Wg"]]) for g in op.gates]
+    if isinstance(op, BNOp):
+        return [([op.y], [op.z], [op.gamma, op.beta])]
+    if isinstance(op, DropoutOp):
+        return [([op.y], [op.x], [])]
+    if isinstance(op, PReluBatchOp):
+        return [([y], [z], [a]) for z, y, a in op.items]
+    raise NotImplementedError(f"PCGrad per_task: no gradient-reach rule for {type(op).__name__}")
+
+
+def pcgrad_reach(plan):
+    """Per objective: the ids of the PVals (parameters, tables) that objective has a gradient for -- what the reference
+    reads off `p.grad is None` after objective t's backward (model/optimizer.py:130-137) -- derived from the recorded ops
+    by walking back from the heads' inputs.
+    Objective t is loss(y_pred[:, t], y[:, t]) with y_pred = torch.cat(task_outs, -1) (reference model/mmoe.py:108,
+    model/basemodel.py:294-296): the backward of the column slice hands the concatenation a gradient for EVERY head's
+    output (zeros for the others), so autograd gives every parameter that any head reaches a gradient -- of zeros -- under
+    every objective, never None.  The fixtures of tests/golden/make_golden_pcgrad.py record exactly that (has/<param> is 1
+    throughout), and with it the merge takes the MEAN everywhere (model/optimizer.py:58): the sets below are the union over
+    the heads.  A parameter no head reaches has no gradient under any objective and is in no set."""
+    head = plan.head_op
+    if type(head) is not HeadOp:
+        raise NotImplementedError(f"PCGrad per_task: {type(head).__name__}")
+    edges = [e for op in plan.ops for e in _op_edges(op)]
+    union = set()
+    for h in head.heads:
+        vals = {id(h["Hin"])} | ({id(h["gate"])} if h.get("gate") is not None else set())
+        pvs = {id(h[k]) for k in ("w", "bias", "bias2") if h.get(k) is not None}
+        for outs, ins, params in reversed(edges):
+            if any(id(o) in vals for o in outs):
+                vals.update(id(v) for v in ins)
+                pvs.update(id(p) for p in params)
+        union |= pvs
+    return [set(union) for _ in head.heads]
+
+
+def pcgrad_segments(plan, store, reach, dense_bank, table_banks, marks_of):
+    """The mml_pcgrad_seg list of a plan: runs of arena-adjacent MLP parameters that the same objectives reach (one flat
+    segment each), then every table with its row marks.  dense_bank [T, arena]; table_banks[name] [T, V, E]; marks_of: id of
+    a table's PVal -> its slice of the scatter's byte map (absent: every row is read)."""
+    T = len(reach)
+    arena = store.arena
+    dense = sorted(((pv.grad.data_ptr() - arena.data_ptr()) // 4, pv) for pv in store.pvals.values()
+                   if not pv.is_table and pv.grad is not None and pv.written)
+    segs, run = [], None
+    for off, pv in dense:
+        has = tuple(id(pv) in reach[t] for t in range(T))
+        if not any(has):
+            continue
+        if run is not None and run[1] == off and run[2] == has:
+            run[1] = off + pv.grad.numel()
+        else:
+            run = [off, off + pv.grad.numel(), has]
+            segs.append(run)
+    out = [dict(banks=[dense_bank[t, a:b] if has[t] else None for t in range(T)], out=arena[a:b]) for a, b, has in segs]
+    for n in store.table_names:
+        pv = store.pvals[n]
+        if not pv.written or not any(id(pv) in reach[t] for t in range(T)):
+            continue
+        out.append(dict(banks=[table_banks[n][t] if id(pv) in reach[t] else None for t in range(T)], out=pv.grad,
+                        marks=marks_of.get(id(pv))))
+    return out

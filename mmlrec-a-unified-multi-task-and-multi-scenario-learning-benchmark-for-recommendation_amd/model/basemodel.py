@@ -269,8 +269,9 @@ class BaseModel(nn.Module):
             self._caches["plans"][key] = plan
         return plan
 
-    def _record(self, B, training, masked, store, sparse_rows=None, lazy=False, mark_rows=None, grad_marks=False):
-        plan = E.Plan(store.device, B, training)
+    def _record(self, B, training, masked, store, sparse_rows=None, lazy=False, mark_rows=None, grad_marks=False,
+                pcgrad=False):
+        plan = E.Plan(store.device, B, training, use_amax=False if pcgrad else None)
         plan.bn_training = bool(self.training)
         plan.dropout_on = bool(self.training)
         plan.dropout_seed = int(getattr(self, "dropout_seed", 0))
@@ -300,6 +301,13 @@ class BaseModel(nn.Module):
             store.ensure_table_grads()
         if masked:
             plan.mask = plan.zeros(B, max(self.num_domains, 1))
+        if pcgrad:
+            # PCGrad per-task step: head t reads column t of a per-head mask the schedule rewrites before every
+            # objective's pass (1 in that objective's column, 0 elsewhere: a zero seed for the other heads)
+            if masked or not training:
+                raise L.MMLError("a PCGrad per-task plan is an unmasked training plan")
+            plan.pcgrad_T = T
+            plan.mask = plan.zeros(B, T)
         store.reset_written()
         E_dim = self.embedding_size
         nd = sum(f.dimension for f in de)
@@ -379,7 +387,9 @@ class BaseModel(nn.Module):
 
     def _finish_record(self, plan, store, x0):
         head = self._build_graph(plan, store, x0)
-        head.mask_cols = self._head_mask_cols()
+        head.mask_cols = list(range(self.num_tasks)) if plan.pcgrad_T else self._head_mask_cols()
+        if plan.pcgrad_T and len(head.heads) != self.num_tasks:
+            raise NotImplementedError("PCGrad per_task: one head per task")
         if len(head.heads) == self.num_tasks:  # head t is task t's PredictionLayer
             for t, h in enumerate(head.heads):
                 h.setdefault("kind", self._head_kind(t))
@@ -521,12 +531,33 @@ class BaseModel(nn.Module):
             self.optim_name = optimizer
         else:
             raise NotImplementedError("pass the optimizer by name: the update runs in the fused HIP optimizer kernels")
-        if self.model_config.get("model_name") == "pcg":
-            raise NotImplementedError("PCGrad is outside the MI355X hot path")
+        if self._pcgrad_objectives() == "per_task":
+            # the reference's class has no place for the regulariser among per-task objectives (it is part of neither
+            # list entry): no rule is invented here
+            mc = self.model_config
+            if (any(float(mc.get(k, 0) or 0) != 0 for k in ("l2_reg_embedding", "l2_reg_dnn", "l2_reg_linear")) or
+                    any(l1 > 0 or l2 > 0 for _, l1, l2 in getattr(self, "regularization_weight", []))):
+                raise ValueError("pcgrad_objectives='per_task' with a regulariser (l2_reg_embedding / l2_reg_dnn / "
+                                 "l2_reg_linear): PCGrad has no rule for it among per-task objectives; set them to 0")
         self.loss_func = self._get_loss_func(loss)
         self.metrics = self._get_metrics(metrics)
         self._caches["steps"] = {}
         self._optimizer = None
+
+    def _pcgrad_objectives(self):
+        """optim_config["pcgrad_objectives"] of a `pcg` model (reference model/optimizer.py:10-138, model/basemodel.py:309-310,
+        :564-565): "total" (default) -- the reference's literal behaviour, pc_backward(total_loss) iterates a one-element
+        tensor, ONE objective, no projection can fire: the MMoE step -- or "per_task" -- the list of per-task loss terms
+        the class's docstring asks for (trainer.PCGradSchedule).  None for every other model, where a non-default value is
+        an error."""
+        v = (getattr(self, "optim_config", None) or {}).get("pcgrad_objectives", "total")
+        if v not in ("total", "per_task"):
+            raise ValueError("optim_config['pcgrad_objectives'] must be 'total' or 'per_task'")
+        if self.model_config.get("model_name") != "pcg":
+            if v != "total":
+                raise ValueError("optim_config['pcgrad_objectives'] is read for model_name 'pcg' only")
+            return None
+        return v
 
     def _get_loss_func(self, loss):
         """One loss name per task (reference :586-603): binary_crossentropy, mse (F.mse_loss) or mae (F.l1_loss), each summed

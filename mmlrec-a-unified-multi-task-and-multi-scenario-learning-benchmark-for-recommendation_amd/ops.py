@@ -878,6 +878,77 @@ def prelu_bwd(items):
         seen.update(d.dalpha for d in arr)
 
 
+def make_pcgrad_segs(segs, T, need_out=False):
+    """segs: dicts `banks` (T entries: objective t's gradient of one parameter tensor -- float32, 1-D or 2-D with unit
+    inner stride, one shape and row pitch for all -- or None = no gradient), optional `out` (same layout; may be one of
+    the banks) and `marks` (uint8, one byte per row).  Returns the mml_pcgrad_seg array (include/mmlrec.h)."""
+    arr = (L.PcgradSeg * max(len(segs), 1))()
+    for d, sg in zip(arr, segs):
+        banks = list(sg["banks"])
+        if len(banks) != T:
+            raise L.MMLError(f"pcgrad: a segment has {len(banks)} banks for T = {T}")
+        have = [b for b in banks if b is not None] + ([sg["out"]] if sg.get("out") is not None else [])
+        if not have:
+            raise L.MMLError("pcgrad: a segment whose banks are all None")
+        _need_gpu(*have)
+        ref = have[0]
+        for b in have:
+            if (b.dtype != torch.float32 or b.dim() not in (1, 2) or b.shape != ref.shape or b.stride() != ref.stride() or
+                    (b.shape[-1] > 1 and b.stride(-1) != 1)):
+                raise L.MMLError("pcgrad: banks and out of a segment must be float32 views of one shape and pitch")
+        rows, cols = (1, ref.shape[0]) if ref.dim() == 1 else ref.shape
+        for k, b in enumerate(banks):
+            d.bank[k] = b.data_ptr() if b is not None else None
+        d.out = L.ptr(sg.get("out"))
+        d.rows, d.cols, d.ld = rows, cols, (cols if ref.dim() == 1 else _ld(ref))
+        marks = sg.get("marks")
+        if marks is not None and (marks.dtype != torch.uint8 or marks.numel() < rows or not marks.is_contiguous()):
+            raise L.MMLError("pcgrad: marks must be a contiguous uint8 tensor with one byte per row")
+        d.row_marks = L.ptr(marks)
+        if need_out and sg.get("out") is None:
+            raise L.MMLError("pcgrad combine: a segment without `out`")
+    return arr
+
+
+def pcgrad_gram(segs, T, gram=None):
+    """The T x T Gram matrix (float64, device) of the per-objective gradients over every segment: one pass, fixed-order
+    sums (mml_pcgrad_gram)."""
+    arr = make_pcgrad_segs(segs, T)
+    dev = next(b for b in segs[0]["banks"] if b is not None).device
+    if gram is None:
+        gram = torch.empty((T, T), dtype=torch.float64, device=dev)
+    nbytes = int(L.load().mml_pcgrad_workspace_bytes(arr, len(segs), T))
+    ws = workspace(nbytes, dev)
+    L.check(L.load().mml_pcgrad_gram(arr, len(segs), T, gram.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+            "mml_pcgrad_gram")
+    return gram
+
+
+def pcgrad_weights(gram, order, w=None, fired=None):
+    """gram [T, T] float64, order [T, T] int32 (row i: the order in which g_i meets the g_j), both on the device ->
+    (w [2 T] float32: mean weights then sum weights, fired [T, T] int32) (mml_pcgrad_weights)."""
+    _need_gpu(gram, order)
+    T = gram.shape[0]
+    if gram.dtype != torch.float64 or order.dtype != torch.int32 or order.numel() != T * T or gram.numel() != T * T \
+            or not gram.is_contiguous() or not order.is_contiguous():
+        raise L.MMLError("pcgrad_weights: gram [T, T] float64 and order [T, T] int32, contiguous")
+    if w is None:
+        w = torch.empty(2 * T, dtype=torch.float32, device=gram.device)
+    if fired is None:
+        fired = torch.empty((T, T), dtype=torch.int32, device=gram.device)
+    L.check(L.load().mml_pcgrad_weights(gram.data_ptr(), order.data_ptr(), T, w.data_ptr(), fired.data_ptr(), _stream()),
+            "mml_pcgrad_weights")
+    return w, fired
+
+
+def pcgrad_combine(segs, T, w):
+    """out = sum_k w'[k] bank_k for every segment: the mean weights where every bank is there, the sum weights otherwise
+    (mml_pcgrad_combine)."""
+    _need_gpu(w)
+    arr = make_pcgrad_segs(segs, T, need_out=True)
+    L.check(L.load().mml_pcgrad_combine(arr, len(segs), T, w.data_ptr(), _stream()), "mml_pcgrad_combine")
+
+
 def act_bwd(y, dy, dst, act):
     L.check(L.load().mml_act_bwd(y.data_ptr(), dy.data_ptr(), dst.data_ptr(), y.numel(), act, _stream()), "mml_act_bwd")
 

@@ -697,6 +697,8 @@ def shard_model(model, dist, batch_per_rank=4096, group=None, mode="row_sharded"
     # that are per-sample sums.  Two model features are not: ESCM's IPW loss normalises by batch-wide sums (N = sum y0,
     # L1, S: mml_escm_combine sees the local shard only) and BatchNorm / DomainBatchNorm use batch statistics (per-rank
     # statistics would silently train a different model, and the running statistics would diverge across ranks).
+    if getattr(model, "_pcgrad_objectives", None) is not None and model._pcgrad_objectives() == "per_task":
+        raise NotImplementedError("shard_model: the PCGrad per-task step (pcgrad_objectives='per_task') runs on one GPU only")
     if getattr(model, "_pooled_cols", None) is not None and model._pooled_cols():
         raise NotImplementedError("shard_model: multi-valued (pooled) features run on one GPU only")
     if type(model).__name__ == "ESCM":

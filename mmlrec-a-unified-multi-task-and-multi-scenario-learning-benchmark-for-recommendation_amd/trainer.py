@@ -155,9 +155,159 @@ def resolve_overlap(overlap):
     return bool(overlap)
 
 
+def draw_pcgrad_orders(T):
+    """The orders in which PCGrad projects: the reference shuffles ONE list of the T gradients in place before every g_i
+    (model/optimizer.py:50-51: `random.shuffle(grads)` inside the loop over pc_grad), so the shuffles accumulate from one i
+    to the next, and the list starts in task order at every step (_pack_grad builds it anew).  Same calls to Python's
+    `random` in the same sequence: under random.seed(s) these are the reference's orders.  Returns T rows of T indices."""
+    import random
+    lst = list(range(T))
+    rows = []
+    for _ in range(T):
+        random.shuffle(lst)
+        rows.append(list(lst))
+    return rows
+
+
+class PCGradSchedule:
+    """The step of a `pcg` model with optim_config["pcgrad_objectives"] = "per_task" (reference model/optimizer.py:10-138,
+    fed the list of per-task loss terms): ONE forward, then per objective t
+        mask <- 1 in head t's column, 0 elsewhere; labels the heads read <- y * mask   (a zero seed, a zero loss term and
+                                                                                         a zero prediction for the others)
+        heads + loss, backward chain, table scatter, weight gradients                  (the plan's own lists, replayed)
+        predictions and loss term added to the step's totals
+        the MLP arena -> bank t; the table rows the scatter marked -> bank t, and cleared  (mml_pcgrad_stash)
+    then mml_pcgrad_gram / _weights / _combine over the banks -- the merged gradient lands in the ordinary gradient
+    buffers -- and the unchanged optimizer calls.  One stream, one call list (one HIP graph).  `order` (the step's projection
+    orders) is a plan-owned device buffer TrainStep.run() fills before launching."""
+
+    def __init__(self, model, plan, store, opt, opt_split):
+        from . import _lib as L
+        from . import ops
+        lib = L.load()
+        T, B, dev = plan.pcgrad_T, plan.B, plan.device
+        if T > L.PCGRAD_MAX_TASKS:
+            raise NotImplementedError(f"PCGrad per_task: {T} tasks (at most {L.PCGRAD_MAX_TASKS})")
+        if any(c[0] is E.PY for lst in (plan.fwd, plan.head_train, plan.bwd, plan.bwd_tail, plan.bwd_side) for c in lst):
+            raise NotImplementedError("PCGrad per_task: a plan with Python-issued entries (multi-GPU)")
+        self.T = T
+        gop = plan.ops[0] if plan.ops else None
+        gm = getattr(gop, "grad_marks", None)
+        if gm is None and opt.table_update != "dense_exact":
+            raise NotImplementedError(f"PCGrad per_task with table_update={opt.table_update!r} needs the scatter's row marks "
+                                      "(embedding size 4, 8 or 16, one table per field): use table_update='dense_exact'")
+        dd = getattr(gop, "det_deferred", None)
+        if dd is not None:
+            raise L.MMLError("PCGrad per_task: the deterministic scatter must fold its totals itself (fp32 rows for the banks)")
+        reach = E.pcgrad_reach(plan)
+        marks_of = {}
+        if gm is not None:
+            _, base = store.ensure_grad_marks(gop.tables)
+            for f, t in enumerate(gop.tables):
+                marks_of[id(t)] = gm[base[f]:base[f] + t.data.shape[0]]
+        tabs = [store.pvals[n] for n in store.table_names if store.pvals[n].written]
+        # memory: T banks of the MLP arena + T banks of every table's gradient rows (only marked rows are ever touched)
+        self.dense_bank = torch.empty((T, store.arena.numel()), dtype=torch.float32, device=dev)
+        self.table_banks = {n: torch.empty((T,) + tuple(store.pvals[n].data.shape), dtype=torch.float32, device=dev)
+                            for n in store.table_names if store.pvals[n].written}
+        self.segs = E.pcgrad_segments(plan, store, reach, self.dense_bank, self.table_banks, marks_of)
+        self.gram = torch.zeros((T, T), dtype=torch.float64, device=dev)
+        self.w = torch.zeros(2 * T, dtype=torch.float32, device=dev)
+        self.fired = torch.zeros((T, T), dtype=torch.int32, device=dev)
+        self.order = torch.zeros((T, T), dtype=torch.int32, device=dev)
+        self.order_host = [torch.zeros((T, T), dtype=torch.int32).pin_memory() for _ in range(2)]
+        self.order_ev = [None, None]
+        self.orders = None  # the orders of the latest step (host list)
+        # the heads keep reading the label buffer the plan was recorded with; the batch is loaded into a buffer of its own
+        self.y_heads = plan.y
+        plan.y = plan.zeros(B, T)
+        ones, zeros = plan.zeros(B, 1) + 1.0, plan.zeros(B, 1)
+        plan.keep += [ones, zeros]
+        self.prob_sum, self.loss_sum = plan.zeros(B, T), plan.zeros(1, 1)
+
+        def copies(items):  # [(src, dst, accumulate)] -> one mml_copy2d_batch launch
+            arr = (L.Copy2dDesc * len(items))()
+            for d, (src, dst, acc) in zip(arr, items):
+                d.src, d.lds, d.dst, d.ldd = src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0)
+                d.rows, d.cols, d.accumulate = src.shape[0], src.shape[1], int(acc)
+            plan.keep.append(arr)
+            return (lib.mml_copy2d_batch, (arr, len(items)),
+                    dict(kernel="copy2d_batch_kernel", bytes=8.0 * sum(a.numel() for a, _, _ in items)))
+
+        table_segs = [[dict(banks=[pv.grad], out=self.table_banks[pv.name][t], marks=marks_of.get(id(pv))) for pv in tabs]
+                      for t in range(T)]
+        loss2d = plan.loss.view(1, 1)
+        self.passes = []
+        for t in range(T):
+            cols = [(ones, plan.mask[:, t:t + 1], 0)]
+            if T > 1:
+                prev = (t - 1) % T  # (pass 0: the column the previous step's last pass left set)
+                cols.append((zeros, plan.mask[:, prev:prev + 1], 0))
+            calls = [copies(cols),
+                     (lib.mml_ew_mul, (plan.y.data_ptr(), plan.mask.data_ptr(), self.y_heads.data_ptr(), B * T),
+                      dict(kernel="ew_mul_kernel", bytes=12.0 * B * T))]
+            calls += plan.head_train + plan.bwd + plan.bwd_tail + list(getattr(plan, "head_side", [])) + plan.bwd_side
+            calls.append(copies([(plan.prob, self.prob_sum, t > 0), (loss2d, self.loss_sum, t > 0)]))
+            a = ops.make_pcgrad_segs([dict(banks=[store.arena], out=self.dense_bank[t])], 1, need_out=True)
+            plan.keep.append(a)
+            calls.append((lib.mml_pcgrad_stash, (a, 1, 0),
+                          dict(kernel="pcgrad_stash_kernel", bytes=8.0 * store.arena.numel())))
+            if tabs:
+                b = ops.make_pcgrad_segs(table_segs[t], 1, need_out=True)
+                plan.keep.append(b)
+                calls.append((lib.mml_pcgrad_stash, (b, len(tabs), 1),
+                              dict(kernel="pcgrad_stash_kernel", bytes=12.0 * B * len(tabs) * tabs[0].data.shape[1])))
+            self.passes.append(calls)
+        arr = ops.make_pcgrad_segs(self.segs, T, need_out=True)
+        n = len(self.segs)
+        nws = int(lib.mml_pcgrad_workspace_bytes(arr, n, T))
+        ws = torch.empty(max(nws, 256), dtype=torch.uint8, device=dev)
+        plan.keep += [arr, ws, self.dense_bank, self.table_banks, self.gram, self.w, self.fired, self.order]
+        elems = float(sum(int(sg["out"].numel()) if sg.get("marks") is None else
+                          min(int(sg["out"].numel()), B * int(sg["out"].shape[1])) for sg in self.segs))
+        self.surgery = [
+            copies([(self.prob_sum, plan.prob, 0), (self.loss_sum, loss2d, 0)]),
+            (lib.mml_pcgrad_gram, (arr, n, T, self.gram.data_ptr(), ws.data_ptr(), ws.numel()),
+             dict(kernel="pcgrad_gram_kernel", bytes=4.0 * T * elems)),
+            (lib.mml_pcgrad_weights, (self.gram.data_ptr(), self.order.data_ptr(), T, self.w.data_ptr(),
+                                      self.fired.data_ptr()), dict(kernel="pcgrad_weights_kernel", bytes=8.0 * T * T)),
+            (lib.mml_pcgrad_combine, (arr, n, T, self.w.data_ptr()),
+             dict(kernel="pcgrad_combine_kernel", bytes=4.0 * (T + 1) * elems)),
+        ]
+        # the marked dense update clears the scatter's marks itself; the row-wise updates do not read them
+        self.unmark = []
+        if gm is not None and opt.table_update != "dense_exact":
+            z = torch.zeros((gm.numel() // 32, 8), dtype=torch.float32, device=dev)  # (the map is padded to 32 bytes per table)
+            plan.keep.append(z)
+            self.unmark = [(lib.mml_copy2d, (z.data_ptr(), 8, gm.data_ptr(), 8, z.shape[0], 8, 0),
+                            dict(kernel="copy2d_kernel", bytes=2.0 * gm.numel()))]
+        self.gradients = plan.fwd + [c for p_ in self.passes for c in p_] + self.surgery
+        self.calls = (opt_split["pre"] + self.gradients + self.unmark + opt_split["tables"] + opt_split["mlp"])
+
+    def upload_orders(self, step_no):
+        """Draw this step's orders on the host and queue their upload in front of the step (two pinned buffers in turn: the
+        host may run one step ahead of the device)."""
+        k = step_no % 2
+        if self.order_ev[k] is not None:
+            self.order_ev[k].synchronize()
+        self.orders = draw_pcgrad_orders(self.T)
+        self.order_host[k].copy_(torch.tensor(self.orders, dtype=torch.int32))
+        self.order.copy_(self.order_host[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream())
+        self.order_ev[k] = ev
+
+
 class TrainStep:
     def __init__(self, model, B, use_graph=True, allreduce=None, overlap=None, split_dense=True):
         overlap = resolve_overlap(overlap)
+        # PCGrad per-task step (PCGradSchedule): a schedule of its own -- one stream, no split table update, no inner fork
+        pcg = getattr(model, "_pcgrad_objectives", lambda: None)() == "per_task"
+        if pcg:
+            if getattr(model, "_parallel", None) is not None or allreduce is not None:
+                raise NotImplementedError("the PCGrad per-task step runs on one GPU")
+            overlap = False
+        self.pcgrad = None
         self.model = model
         self.store = model._store()
         self.opt = model.optimizer()
@@ -171,7 +321,9 @@ class TrainStep:
         if (self.opt.table_update == "lazy_exact" and getattr(self.opt, "auto", False) and par is not None and
                 par.mode == "table_wise" and self.opt.steps_done == 0 and self.opt.last is None):
             self.opt.table_update = "dense_exact"  # ('auto' picked lazy_exact before the tables were sharded table-wise)
-        lazy = self.opt.table_update == "lazy_exact"
+        # (a PCGrad per-task step lists the rows of a sparse_rows update in an index pre-pass too: its scatter runs once per
+        # objective and only accumulates and marks)
+        lazy = self.opt.table_update == "lazy_exact" or (pcg and self.opt.table_update == "sparse_rows")
         if lazy and par is not None and par.mode == "table_wise":
             raise NotImplementedError("lazy_exact table updates on the table-wise sharded path (use row_sharded)")
         # Split dense table update (engine.Optimizer.can_split_dense): the reference-exact dense optimizer as
@@ -183,7 +335,7 @@ class TrainStep:
         # not mark (grad_marks below: 24 instead of 28 bytes per Adam parameter, no extra launch or stream) the two
         # are level at B = 4 096 too (0.767 / 0.769 ms on one box), so the split form only runs on request
         # (split_dense="force").
-        split = (split_dense == "force" and self.opt.table_update == "dense_exact" and
+        split = (split_dense == "force" and self.opt.table_update == "dense_exact" and not pcg and
                  (par is None or par.mode == "replicated") and
                  not model._pooled_cols() and  # (the pooled gather marks no rows: the single-launch schedule)
                  not self.opt._table_reg(self.opt._reg_map()) and model.embedding_size <= 16 and
@@ -204,7 +356,7 @@ class TrainStep:
         # the GLOBAL batch, listed by the index pre-pass
         # Single-launch dense update: the scatter marks the rows it adds to, the optimizer reads the gradient of those
         # rows only (mml_opt_tensor.grad_marks): 24 instead of 28 bytes per Adam parameter, no extra launch.
-        marked = (self.opt.table_update == "dense_exact" and not split and
+        marked = ((self.opt.table_update == "dense_exact" or pcg) and not split and
                   (par is None or par.mode in ("row_sharded", "replicated")) and
                   os.environ.get("MMLREC_GRAD_MARKS", "1") != "0" and not os.environ.get("MMLREC_SCATTER_OLD"))
         # one stream (and no split table update, whose early pass forks anyway): the reductions of the head / gate kernels'
@@ -213,7 +365,7 @@ class TrainStep:
         with E.deferred_reductions(one_list):
             self.plan = model._record(B, True, False, self.store, sparse_rows=None if (lazy or split) else rows,
                                       lazy=lazy or split, mark_rows=rows if (split and par is None) else None,
-                                      grad_marks=marked)
+                                      grad_marks=marked, **(dict(pcgrad=True) if pcg else {}))
         if one_list:
             # the top of the network -- last tower layer, heads + BCE, the towers' input gradient -- as one launch where
             # the recorded lists hold that pattern (csrc/tower_head.hip; before the reductions are merged: it brings its own)
@@ -231,6 +383,8 @@ class TrainStep:
         if not overlap and os.environ.get("MMLREC_MERGE_WGRAD", "1") != "0":
             self.plan.merge_wgrad16()  # (the bf16-storage path's launches: csrc/gemm16.hip)
         self.opt_split = self.opt.calls_split(self.plan, split_dense=split)
+        if pcg and self.opt.table_update == "sparse_rows":
+            self.opt_split["pre"] = self.opt_split["pre"] + self.opt._unique_pre_calls(self.plan)
         self.split_dense = bool(self.opt_split["early"])
         self.opt_calls = (self.opt_split["pre"] + self.opt_split["early"] + self.opt_split["mlp"] +
                           self.opt_split["tables"])
@@ -295,7 +449,11 @@ class TrainStep:
         # one stream: the whole step is ONE call list (one HIP graph when it holds no Python-issued entry) -- every graph
         # seam is ~16 us of idle stream, a tenth of a small-batch step
         self.whole = None
-        if not self.overlap and not self.split_dense:
+        if pcg:
+            self.pcgrad = PCGradSchedule(model, p, self.store, self.opt, self.opt_split)
+            self.whole = Segments(self.pcgrad.calls, self.use_graph)
+            self.fork_refused = []
+        elif not self.overlap and not self.split_dense:
             # The weight gradients on a second stream INSIDE the step's one graph (a fork / join of graph nodes: no seam):
             # beside the table scatter and the table optimizer.  Same-box interleaved pairs (tools/lab/ab_env.sh
             # MMLREC_INNER_FORK=0 / 2, B = 65 536): AE-30 1.4773 / 1.4818 / 1.4860 / 1.4952 / 1.4772 -> 1.4635 / 1.4683 /
@@ -479,6 +637,8 @@ class TrainStep:
                 if seg is not None:
                     seg.capture()
             torch.cuda.synchronize()
+        if self.pcgrad is not None:
+            self.pcgrad.upload_orders(self.calls)
         if self.whole is not None:
             self.whole.run()
             self._done()
@@ -507,6 +667,15 @@ class TrainStep:
         else:
             self._forked(self.sideq.run, self.tail.run)
         self._done()
+
+    def run_gradients(self):
+        """PCGrad per-task step only, for tests and diagnostics: everything of run() in front of the optimizer, eagerly.
+        The merged gradient is left in the ordinary gradient buffers (table accumulators included, which a step expects
+        to find all zero): do not call run() on this model afterwards."""
+        if self.pcgrad is None:
+            raise RuntimeError("run_gradients: not a PCGrad per-task step")
+        self.pcgrad.upload_orders(self.calls)
+        E.Plan._run(self.pcgrad.gradients)
 
     def _done(self):
         profiling.pop()

@@ -83,7 +83,7 @@ def build_model(name, device, vocab_scale=1.0, seed=0, **model_kw):
     cfg["model_config"].update(model_kw)
     emb = cfg["model_config"]["emb"]
     cols = [SparseFeat(n, v, embedding_dim=emb) for n, v in zip(names, vocab)] + [DenseFeat(n, 1) for n in dense]
-    cls = {"sharedbottom": SharedBottom, "mmoe": MMOE, "ple": PLE, "star": STAR, "pepnet": PepNet, "mlp": MLP,
+    cls = {"sharedbottom": SharedBottom, "mmoe": MMOE, "pcg": MMOE, "ple": PLE, "star": STAR, "pepnet": PepNet, "mlp": MLP,
            "esmm": ESMM, "escm": ESCM, "apg": APG, "cross_stitch": CrossStitch, "hmoe": HMOE, "aitm": AITM, "snr_trans": SNR_trans,
            "mssm": MSSM}[
         cfg["model_config"]["model_name"]]
