@@ -87,6 +87,11 @@ def call_meta(c):
     return c[-1] if isinstance(c[-1], dict) else {}
 
 
+def has_py(calls):
+    """Whether a call list holds a Python-issued entry (such a list is no single HIP graph: trainer.Segments cuts there)."""
+    return any(c[0] is PY for c in calls)
+
+
 def _claim(x):
     acc = 1 if x.written else 0
     x.written += 1
@@ -1238,16 +1243,24 @@ def _padded_view(buf, kp):
     return buf.as_strided((buf.shape[0], kp), (buf.stride(0), 1), buf.storage_offset())
 
 
-def _copy2d_batch_call(plan, pairs, amax=None):
-    """One launch copying src[:, :cols] -> dst[:, :cols] for every (src, dst) pair (cols = the narrower of the two);
-    amax: per pair a magnitude slot the copy raises with max |x| of what it stores, or None."""
+def copy2d_descs(pairs, amax=None, accumulate=None):
+    """The Copy2dDesc block of mml_copy2d_batch: src[:, :cols] -> dst[:, :cols] for every (src, dst) pair (cols = the narrower
+    of the two).  amax: per pair a magnitude slot the copy raises with max |x| of what it stores, or None; accumulate: per
+    pair whether the copy adds to dst instead of overwriting it (None = no pair does)."""
     arr = (L.Copy2dDesc * len(pairs))()
     for k, (d, (src, dst)) in enumerate(zip(arr, pairs)):
         d.src, d.lds, d.dst, d.ldd = src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0)
-        d.rows, d.cols, d.accumulate = src.shape[0], min(src.shape[1], dst.shape[1]), 0
+        d.rows, d.cols = src.shape[0], min(src.shape[1], dst.shape[1])
+        d.accumulate = int(bool(accumulate[k])) if accumulate is not None else 0
         if amax is not None and amax[k] is not None:
             d.amax_out = amax[k].data_ptr()
-            plan.keep.append(amax[k])
+    return arr
+
+
+def _copy2d_batch_call(plan, pairs, amax=None, accumulate=None):
+    """One launch of copy2d_descs(pairs, amax, accumulate); the plan keeps the block and the magnitude slots alive."""
+    arr = copy2d_descs(pairs, amax, accumulate)
+    plan.keep += [a for a in (amax or ()) if a is not None]
     plan.keep.append(arr)
     return (L.load().mml_copy2d_batch, (arr, len(pairs)),
             dict(kernel="copy2d_batch_kernel", bytes=8.0 * sum(min(a.numel(), b.numel()) for a, b in pairs)))
@@ -2707,6 +2720,15 @@ class ParamStore:
             off += (v + 31) // 32 * 32
         return self.grad_marks, base
 
+    def grad_marks_by_table(self, gop):
+        """{id(table): its rows' slice of the mark map} for the tables of a gather whose scatter marks rows; {} for one
+        that does not (or for no gather at all)."""
+        gm = getattr(gop, "grad_marks", None)
+        if gm is None:
+            return {}
+        _, base = self.ensure_grad_marks(gop.tables)
+        return {id(t): gm[base[f]:base[f] + t.data.shape[0]] for f, t in enumerate(gop.tables)}
+
     def ensure_det(self, tables):
         """Buffers of the deterministic scatter for `tables` (a gather's field order): int64 [V, E] totals per table (kept
         all zero between steps by the scatter's second launch, or by the table optimizer that takes the totals over), a
@@ -2881,13 +2903,8 @@ class Optimizer:
                     seen_of = dict(zip(st.rows_names, st.rows.seen))
                 # marked gradients (the scatter of this plan marked every row it added to): the streaming launch does not
                 # read the gradient of unmarked rows -- 24 instead of 28 bytes per Adam parameter
-                marks_of = {}
                 gop = plan.ops[0] if plan.ops else None
-                gm = getattr(gop, "grad_marks", None)
-                if gm is not None and not split_dense:
-                    _, base = st.ensure_grad_marks(gop.tables)
-                    for f, t in enumerate(gop.tables):
-                        marks_of[id(t)] = gm[base[f]:base[f] + t.data.shape[0]]
+                marks_of = {} if split_dense else st.grad_marks_by_table(gop)
                 # Round 6, built and measured, NOT the default: every table in ONE marked streaming launch (workgroups dealt
                 # in proportion to the tables' sizes, csrc/optim_ew.hip) instead of the streaming launch of the huge tables
                 # + a flat launch of the small ones (AE-30: 26 tables, 31-34 us).  Two call lists over ONE model replayed in

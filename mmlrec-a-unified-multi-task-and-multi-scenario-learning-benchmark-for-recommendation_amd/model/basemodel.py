@@ -635,8 +635,9 @@ class BaseModel(nn.Module):
         overlap = resolve_overlap(overlap)  # (None: the default schedule -- one stream since round 5)
         key = (int(B), bool(self.training))  # BatchNorm follows the MODULE's mode: a step is recorded for one of them
         st = self._caches["steps"].get(key)
-        if (st is None or st.store is not self._store() or st.overlap != bool(overlap) or
-                st.want_split != bool(split_dense)):
+        # (the REQUEST is compared, not what the step made of it: TrainStep may lower overlap, and "force" is not True)
+        if (st is None or st.store is not self._store() or st.want_overlap != overlap or
+                st.want_split != split_dense):
             st = TrainStep(self, B, self.use_hip_graph if use_graph is None else use_graph, allreduce, overlap,
                            split_dense)
             self._caches["steps"][key] = st

@@ -11,14 +11,74 @@ Default (round 5): ONE HIP stream, the whole step one HIP graph (resolve_overlap
 Multi-GPU steps (parallel.py) contain Python-issued entries (collectives, the row-sharded exchange with its run-time
 sizes).  Those run eagerly; the runs of C-ABI calls between them -- static shapes, static pointers -- are still captured
 and replayed as HIP graphs (`Segments`).
+
+How a step is put together: StepKnobs.from_env reads every MMLREC_* switch once per TrainStep; whole_step_calls (one
+list, with or without a fork / join inside it) and segmented_step (the two-stream lists, early fork and split dense table
+update included) are pure functions of call lists; OneList, TwoStreams and PCGradSchedule replay what they return and
+own their streams and events.  TrainStep picks the schedule and keeps the lists readable under their names.
 """
+import dataclasses
 import os
+import typing
 
 import torch
 
 from . import engine as E
 from .ops import concurrent_stream as ops_concurrent_stream
 from . import profiling
+
+
+@dataclasses.dataclass(frozen=True)
+class StepKnobs:
+    """Every environment switch the trainer reads, read ONCE per TrainStep (from_env; never at import: tests and lab scripts
+    set the variables between constructions)."""
+    streams: int = 1             # MMLREC_STREAMS=2: two streams where the caller leaves overlap=None (resolve_overlap)
+    grad_marks: bool = True      # MMLREC_GRAD_MARKS=0 or MMLREC_SCATTER_OLD: the dense update reads every row's gradient
+    merge_reduces: bool = True   # MMLREC_MERGE_REDUCES=0: the head / gate reductions stay where they were recorded
+    merge_wgrad: bool = True     # MMLREC_MERGE_WGRAD=0: one weight-gradient launch per layer
+    # CU partition of the forked tail (lab knob MMLREC_CU_TAIL = n: table scatter + table optimizer on compute units
+    # [0, n), weight-gradient GEMMs + MLP optimizer on [n, all)); MMLREC_CU_EARLY = n: the early table pass on [0, n)
+    cu_tail: int = 0
+    cu_early: int = 0
+    # The weight gradients on a second stream INSIDE the step's one graph (a fork / join of graph nodes: no seam): beside
+    # the table scatter and the table optimizer.  Same-box interleaved pairs (tools/lab/ab_env.sh MMLREC_INNER_FORK=0 / 2,
+    # B = 65 536): AE-30 1.4773 / 1.4818 / 1.4860 / 1.4952 / 1.4772 -> 1.4635 / 1.4683 / 1.4851 / 1.4623 / 1.4731 ms,
+    # AE-30d 1.613 -> 1.582, PLE 1.535 -> 1.509, PepNet 2.028 -> 2.006; at B = 4 096 it loses (0.670 -> 0.679 ms), so
+    # large batches only.  MMLREC_INNER_FORK: 0 off, 1 joined in front of the table optimizer (beside the scatter only:
+    # level), 2 joined behind it (the default form), 3 forked behind the scatter; unset (None) = by batch size.
+    # Round 6: the fork makes the step's graph a multi-branch graph, the kind whose launch segfaulted sporadically in
+    # this runtime (hip::Graph::UpdateStreams, see TwoStreams: dependent on how many streams the process created).
+    # Soaked (tools/lab/fork_soak.sh, profiles/r06_fork_soak.txt): 0 crashes in 32 fresh processes with the fork forced
+    # on for EVERY batch size (22 runs of the suite's graph tests -- every model of the zoo, its own streams, the original
+    # repro's shape -- and 10 of bench.py), so it stays the default for large batches; it never applies to a step that
+    # holds a collective (Python-issued entries between fork and join), i.e. to no multi-GPU step.
+    inner_fork: typing.Optional[int] = None
+    fork_mlp: bool = False       # MMLREC_FORK_MLP=1: the MLP optimizer behind the weight gradients on the fork's branch
+    early_wgrad: str = "0"       # MMLREC_EARLY_WGRAD: "0" off, "auto", or an index into plan.bwd (_early_fork)
+    early_wgrad_debug: bool = False  # MMLREC_EARLY_WGRAD_DEBUG: _early_fork prints its estimate
+
+    @staticmethod
+    def streams_from_env(env=None):
+        """MMLREC_STREAMS alone (resolve_overlap: on the per-batch path of fit(), which needs no other knob)."""
+        return 2 if (os.environ if env is None else env).get("MMLREC_STREAMS", "1") == "2" else 1
+
+    @classmethod
+    def from_env(cls, env=None):
+        env = os.environ if env is None else env
+        fork = env.get("MMLREC_INNER_FORK")
+        return cls(streams=cls.streams_from_env(env),
+                   grad_marks=env.get("MMLREC_GRAD_MARKS", "1") != "0" and not env.get("MMLREC_SCATTER_OLD"),
+                   merge_reduces=env.get("MMLREC_MERGE_REDUCES", "1") != "0",
+                   merge_wgrad=env.get("MMLREC_MERGE_WGRAD", "1") != "0",
+                   cu_tail=int(env.get("MMLREC_CU_TAIL", "0")), cu_early=int(env.get("MMLREC_CU_EARLY", "0")),
+                   inner_fork=int(fork) if fork is not None else None,
+                   fork_mlp=env.get("MMLREC_FORK_MLP", "0") == "1",
+                   early_wgrad=env.get("MMLREC_EARLY_WGRAD", "0"),
+                   early_wgrad_debug=bool(env.get("MMLREC_EARLY_WGRAD_DEBUG")))
+
+    def fork_placement(self, B):
+        """Where the one-list step forks (whole_step_calls): the knob, else 2 from a batch of 16 384 on and 0 below."""
+        return self.inner_fork if self.inner_fork is not None else (2 if int(B) >= 16384 else 0)
 
 
 class Segments:
@@ -84,7 +144,7 @@ def fork_conflicts(side_calls, mid_calls, shared_scratch=()):
     EITHER branch -- the other branch, or the chain that follows, may overwrite it -- and (b) a pointer argument both
     branches carry (each branch must own what it names; descriptors hold further pointers the lists do not show: the
     operands of the weight-gradient GEMMs are written by the chain BEFORE the fork and only read after it).  Returns the
-    offending pointers (empty = no conflict seen); TrainStep refuses to fork on any (tests/test_plan_passes_cpu.py)."""
+    offending pointers (empty = no conflict seen); whole_step_calls refuses to fork on any (tests/test_plan_passes_cpu.py)."""
     def ptrs(calls):
         out = set()
         for c in calls:
@@ -106,8 +166,8 @@ def fork_conflicts(side_calls, mid_calls, shared_scratch=()):
 
 class InnerFork:
     """A fork / join INSIDE one call list (one HIP graph): `fork` sends `calls` to a second stream behind everything
-    issued so far, `join` makes the current stream wait for them.  Knob MMLREC_INNER_FORK (TrainStep): no graph seam,
-    unlike the two-stream schedule of overlap=True -- but a multi-branch graph (see TrainStep.run's note on
+    issued so far, `join` makes the current stream wait for them.  Knob MMLREC_INNER_FORK (StepKnobs): no graph seam,
+    unlike the two-stream schedule of overlap=True -- but a multi-branch graph (see TwoStreams' note on
     hip::Graph::UpdateStreams and the soak of round 6)."""
 
     def __init__(self, device, calls):
@@ -151,7 +211,7 @@ def resolve_overlap(overlap):
     PepNet / Amazon-8 (2.238 against 2.200), level on KuaiRec-32: everything it co-schedules is HBM-bound together, and
     every graph seam costs ~16 us of idle stream.  Two streams stay available: overlap=True, or MMLREC_STREAMS=2."""
     if overlap is None:
-        return os.environ.get("MMLREC_STREAMS", "1") == "2"
+        return StepKnobs.streams_from_env() == 2
     return bool(overlap)
 
 
@@ -169,7 +229,20 @@ def draw_pcgrad_orders(T):
     return rows
 
 
-class PCGradSchedule:
+class OneList:
+    """One stream: the whole step replayed as one Segments (whole_step_calls)."""
+
+    def __init__(self, whole):
+        self.whole = whole
+
+    def segments(self):
+        return [self.whole]
+
+    def run(self, step_no):
+        self.whole.run()
+
+
+class PCGradSchedule(OneList):
     """The step of a `pcg` model with optim_config["pcgrad_objectives"] = "per_task" (reference model/optimizer.py:10-138,
     fed the list of per-task loss terms): ONE forward, then per objective t
         mask <- 1 in head t's column, 0 elsewhere; labels the heads read <- y * mask   (a zero seed, a zero loss term and
@@ -178,17 +251,17 @@ class PCGradSchedule:
         predictions and loss term added to the step's totals
         the MLP arena -> bank t; the table rows the scatter marked -> bank t, and cleared  (mml_pcgrad_stash)
     then mml_pcgrad_gram / _weights / _combine over the banks -- the merged gradient lands in the ordinary gradient
-    buffers -- and the unchanged optimizer calls.  One stream, one call list (one HIP graph).  `order` (the step's projection
-    orders) is a plan-owned device buffer TrainStep.run() fills before launching."""
+    buffers -- and the unchanged optimizer calls.  One stream, one call list (`whole`: one HIP graph).  `order` (the step's
+    projection orders) is a plan-owned device buffer run() fills before launching."""
 
-    def __init__(self, model, plan, store, opt, opt_split):
+    def __init__(self, plan, store, opt, opt_split, use_graph):
         from . import _lib as L
         from . import ops
         lib = L.load()
         T, B, dev = plan.pcgrad_T, plan.B, plan.device
         if T > L.PCGRAD_MAX_TASKS:
             raise NotImplementedError(f"PCGrad per_task: {T} tasks (at most {L.PCGRAD_MAX_TASKS})")
-        if any(c[0] is E.PY for lst in (plan.fwd, plan.head_train, plan.bwd, plan.bwd_tail, plan.bwd_side) for c in lst):
+        if E.has_py(plan.fwd + plan.head_train + plan.bwd + plan.bwd_tail + plan.bwd_side):
             raise NotImplementedError("PCGrad per_task: a plan with Python-issued entries (multi-GPU)")
         self.T = T
         gop = plan.ops[0] if plan.ops else None
@@ -200,11 +273,7 @@ class PCGradSchedule:
         if dd is not None:
             raise L.MMLError("PCGrad per_task: the deterministic scatter must fold its totals itself (fp32 rows for the banks)")
         reach = E.pcgrad_reach(plan)
-        marks_of = {}
-        if gm is not None:
-            _, base = store.ensure_grad_marks(gop.tables)
-            for f, t in enumerate(gop.tables):
-                marks_of[id(t)] = gm[base[f]:base[f] + t.data.shape[0]]
+        marks_of = store.grad_marks_by_table(gop)
         tabs = [store.pvals[n] for n in store.table_names if store.pvals[n].written]
         # memory: T banks of the MLP arena + T banks of every table's gradient rows (only marked rows are ever touched)
         self.dense_bank = torch.empty((T, store.arena.numel()), dtype=torch.float32, device=dev)
@@ -225,29 +294,23 @@ class PCGradSchedule:
         plan.keep += [ones, zeros]
         self.prob_sum, self.loss_sum = plan.zeros(B, T), plan.zeros(1, 1)
 
-        def copies(items):  # [(src, dst, accumulate)] -> one mml_copy2d_batch launch
-            arr = (L.Copy2dDesc * len(items))()
-            for d, (src, dst, acc) in zip(arr, items):
-                d.src, d.lds, d.dst, d.ldd = src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0)
-                d.rows, d.cols, d.accumulate = src.shape[0], src.shape[1], int(acc)
-            plan.keep.append(arr)
-            return (lib.mml_copy2d_batch, (arr, len(items)),
-                    dict(kernel="copy2d_batch_kernel", bytes=8.0 * sum(a.numel() for a, _, _ in items)))
+        def copies(pairs, accumulate=False):  # one mml_copy2d_batch launch (every src has its dst's shape)
+            return E._copy2d_batch_call(plan, pairs, accumulate=[accumulate] * len(pairs))
 
         table_segs = [[dict(banks=[pv.grad], out=self.table_banks[pv.name][t], marks=marks_of.get(id(pv))) for pv in tabs]
                       for t in range(T)]
         loss2d = plan.loss.view(1, 1)
         self.passes = []
         for t in range(T):
-            cols = [(ones, plan.mask[:, t:t + 1], 0)]
+            cols = [(ones, plan.mask[:, t:t + 1])]
             if T > 1:
                 prev = (t - 1) % T  # (pass 0: the column the previous step's last pass left set)
-                cols.append((zeros, plan.mask[:, prev:prev + 1], 0))
+                cols.append((zeros, plan.mask[:, prev:prev + 1]))
             calls = [copies(cols),
                      (lib.mml_ew_mul, (plan.y.data_ptr(), plan.mask.data_ptr(), self.y_heads.data_ptr(), B * T),
                       dict(kernel="ew_mul_kernel", bytes=12.0 * B * T))]
             calls += plan.head_train + plan.bwd + plan.bwd_tail + list(getattr(plan, "head_side", [])) + plan.bwd_side
-            calls.append(copies([(plan.prob, self.prob_sum, t > 0), (loss2d, self.loss_sum, t > 0)]))
+            calls.append(copies([(plan.prob, self.prob_sum), (loss2d, self.loss_sum)], accumulate=t > 0))
             a = ops.make_pcgrad_segs([dict(banks=[store.arena], out=self.dense_bank[t])], 1, need_out=True)
             plan.keep.append(a)
             calls.append((lib.mml_pcgrad_stash, (a, 1, 0),
@@ -266,7 +329,7 @@ class PCGradSchedule:
         elems = float(sum(int(sg["out"].numel()) if sg.get("marks") is None else
                           min(int(sg["out"].numel()), B * int(sg["out"].shape[1])) for sg in self.segs))
         self.surgery = [
-            copies([(self.prob_sum, plan.prob, 0), (self.loss_sum, loss2d, 0)]),
+            copies([(self.prob_sum, plan.prob), (self.loss_sum, loss2d)]),
             (lib.mml_pcgrad_gram, (arr, n, T, self.gram.data_ptr(), ws.data_ptr(), ws.numel()),
              dict(kernel="pcgrad_gram_kernel", bytes=4.0 * T * elems)),
             (lib.mml_pcgrad_weights, (self.gram.data_ptr(), self.order.data_ptr(), T, self.w.data_ptr(),
@@ -283,6 +346,11 @@ class PCGradSchedule:
                             dict(kernel="copy2d_kernel", bytes=2.0 * gm.numel()))]
         self.gradients = plan.fwd + [c for p_ in self.passes for c in p_] + self.surgery
         self.calls = (opt_split["pre"] + self.gradients + self.unmark + opt_split["tables"] + opt_split["mlp"])
+        OneList.__init__(self, Segments(self.calls, use_graph))
+
+    def run(self, step_no):
+        self.upload_orders(step_no)
+        self.whole.run()
 
     def upload_orders(self, step_no):
         """Draw this step's orders on the host and queue their upload in front of the step (two pinned buffers in turn: the
@@ -298,26 +366,276 @@ class PCGradSchedule:
         self.order_ev[k] = ev
 
 
+def whole_step_calls(p, opt, ar, placement=0, fork_mlp=False, shared_scratch=(), make_fork=None):
+    """The whole step as ONE call list (one HIP graph when it holds no Python-issued entry -- every graph seam is ~16 us of
+    idle stream, a tenth of a small-batch step) -> (calls, fork_refused).  p: the plan's lists; opt: the optimizer's
+    pre / early / mlp / tables lists; ar: [the all-reduce entry] or [].  Unforked:
+        pre + fwd + head_train + bwd + bwd_tail + tables + head_side + bwd_side + ar + mlp
+    Forked (placement 1, 2 or 3), the side calls head_side + bwd_side run on the fork's branch and the list reads
+        1: ... bwd + [fork] + bwd_tail + [join] + tables + ar + mlp        (beside the scatter only)
+        2: ... bwd + [fork] + bwd_tail + tables + [join] + ar + mlp        (the default form)
+        3: ... bwd + bwd_tail + [fork] + tables + [join] + ar + mlp        (forked behind the scatter)
+    fork_mlp without an all-reduce: the MLP optimizer goes behind the weight gradients on their branch (it needs nothing of
+    the other one).  The fork is taken iff there are side calls, neither they nor bwd_tail + tables hold a Python-issued
+    entry (fork and join must land in ONE graph) and fork_conflicts sees no shared buffer; fork_refused is what it saw (a
+    step whose branches share a buffer simply runs unforked).  make_fork(side calls) -> (fork entry, join entry)."""
+    head_side = list(getattr(p, "head_side", []))
+    mlp_side = bool(fork_mlp) and not ar
+    side = head_side + p.bwd_side + (opt["mlp"] if mlp_side else [])
+    mid = p.bwd_tail + opt["tables"]
+    lead = opt["pre"] + p.fwd + p.head_train + p.bwd
+    refused = []
+    if placement in (1, 2, 3) and side and not E.has_py(side) and not E.has_py(mid):
+        refused = fork_conflicts(side, mid, shared_scratch)
+        if not refused:
+            fork, join = make_fork(side)
+            mid = ([fork] + p.bwd_tail + [join] + opt["tables"]) if placement == 1 else \
+                ([fork] + p.bwd_tail + opt["tables"] + [join]) if placement == 2 else \
+                (p.bwd_tail + [fork] + opt["tables"] + [join])
+            return lead + mid + ar + ([] if mlp_side else opt["mlp"]), refused
+    return lead + mid + head_side + p.bwd_side + ar + opt["mlp"], refused
+
+
+def early_stream_wait(overlap, split_dense, wait_entry):
+    """-> (whether the early table pass runs on a stream of its own, what `tail` holds in front of the table update).  The
+    pass gets its stream only in a two-stream step whose dense update is split; the touched-row update then waits for it."""
+    own = bool(overlap and split_dense)
+    return own, ([wait_entry] if own else [])
+
+
+SEGMENT_NAMES = ("pre", "early", "front", "front_b", "side_a", "sideq", "tail")
+
+
+def segmented_step(p, opt, ar, wait, split, marks_rows, k, use_graph):
+    """The step cut for two streams -> {name: Segments or None} over SEGMENT_NAMES.  split: the dense table update runs as
+    an early pass over the untouched rows + a touched-row update; marks_rows: the gather that opens `fwd` lists the batch's
+    rows itself (gather + compaction: two entries); k: the early fork's index into bwd (0 = none); wait: [the entry that
+    waits for the early pass] when that pass has a stream of its own, else [].
+    Without an early pass the counter bump / lazy pre-pass simply lead the front graph; with one, `pre` is everything the
+    early pass waits for: the counter, and the row list -- from the index pre-pass, or from the marking gather +
+    compaction that open the forward (behind the magnitude reset / weight pass: plan.n_pre entries)."""
+    n_lead = ((2 if marks_rows else 0) + getattr(p, "n_pre", 0)) if split else 0
+    side_a = [c for c in p.bwd_side if E.call_meta(c).get("ready", 1 << 30) <= k] if k else []
+    head_side = list(getattr(p, "head_side", []))
+    return dict(
+        pre=Segments((opt["pre"] + p.fwd[:n_lead]) if split else [], use_graph),
+        early=Segments(opt["early"], use_graph, min_calls=1),
+        front=Segments(([] if split else opt["pre"]) + p.fwd[n_lead:] + p.head_train + (p.bwd[:k] if k else p.bwd), use_graph),
+        front_b=Segments(p.bwd[k:], use_graph, min_calls=1) if k else None,
+        side_a=Segments(side_a, use_graph, min_calls=1) if k else None,
+        sideq=Segments(head_side + p.bwd_side[len(side_a):] + ar + opt["mlp"], use_graph),
+        # (the touched-row update clears the `seen` bits the early pass is still reading: it waits for that pass)
+        tail=Segments(p.bwd_tail + wait + opt["tables"], use_graph))
+
+
+def _cost(c):
+    meta = E.call_meta(c)
+    return 4e-6 + meta.get("flops", 0.0) / 5e14 + meta.get("bytes", 0.0) / 4e12
+
+
+def _early_fork(knobs, p, tables, B):
+    """Index into plan.bwd at which the side stream forks early (0 = only at the end of the chain).
+    MMLREC_EARLY_WGRAD: unset or 0 = off (the default: measured a loss or level on every workload),
+    n > 0 = that index, "auto" = where the side calls that are ready by then take about as long as the rest of the
+    chain -- but only when the tail (`tables`: the table optimizer's calls) has no dense table stream of the same length
+    to put them beside.
+    When no long table stream waits in the tail to hide the weight-gradient GEMMs behind (row-wise table updates, small
+    tables), the GEMMs whose operands the backward chain has already produced start beside the REST of the chain instead
+    -- worth it where that rest holds HBM-bound launches (PepNet's gate products, the gate / head row kernels) that leave
+    the matrix pipe idle.  One more graph seam on each stream."""
+    env = knobs.early_wgrad
+    ready = [E.call_meta(c).get("ready") for c in p.bwd_side]
+    if env == "0" or not p.bwd_side or any(r is None for r in ready) or E.has_py(p.bwd):
+        return 0
+    if ready != sorted(ready):  # (program order: a later side call is never ready before an earlier one)
+        return 0
+    if env != "auto":
+        return max(0, min(int(env), len(p.bwd) - 1))
+    side_t = sum(_cost(c) for c in p.bwd_side)
+    table_t = sum(_cost(c) for c in tables)
+    if knobs.early_wgrad_debug:
+        import sys
+        print("early fork: side %.0f us, tables %.0f us, chain %.0f us, ready %s of %d" % (
+            side_t * 1e6, table_t * 1e6, sum(_cost(c) for c in p.bwd) * 1e6, ready, len(p.bwd)), file=sys.stderr)
+    if B < 16384 or table_t > 0.5 * side_t:
+        return 0
+    best, best_k = 0.0, 0
+    for k in sorted(set(ready)):
+        if k <= 0 or k >= len(p.bwd):
+            continue
+        a = sum(_cost(c) for c, r in zip(p.bwd_side, ready) if r <= k)
+        rest = sum(_cost(c) for c in p.bwd[k:])
+        if min(a, rest) > best:
+            best, best_k = min(a, rest), k
+    return best_k if best > 40e-6 else 0
+
+
+class TwoStreams:
+    """The lists of segmented_step replayed: pre, [early on a stream of its own], front, [side_a beside front_b], then tail
+    on the main stream beside sideq on the side stream (overlap), or tail and sideq in a row (the split dense update on one
+    stream).
+    With two streams the step is THREE single-stream graph sequences (front, side, tail) forked and joined with events
+    at replay time, not one graph with two branches: hipGraphLaunch of a multi-branch graph walks past the end of the
+    exec's parallel-stream vector when one of those streams shares a hardware queue with the launch stream
+    (hip::Graph::UpdateStreams, ROCm 7.0 runtime bundled with torch 2.10) -- a sporadic segfault that depends on how many
+    streams the process has created.  Single-branch graphs never enter that loop."""
+
+    def __init__(self, device, segs, overlap, early_stream, knobs, single_gpu):
+        self.segs = segs  # (TrainStep's: pre, early, front, front_b, side_a, sideq, tail)
+        self.overlap = overlap
+        self.side = ops_concurrent_stream(device) if overlap else None
+        self.tail_stream = None
+        if overlap and knobs.cu_tail > 0 and single_gpu:
+            from . import ops
+            ncu = torch.cuda.get_device_properties(device).multi_processor_count
+            self.tail_stream = ops.cu_range_stream(device, 0, knobs.cu_tail)
+            self.side = ops.cu_range_stream(device, knobs.cu_tail, ncu)
+            self.ev_tail = torch.cuda.Event()
+        # (a high-priority stream, or more hardware queues (GPU_MAX_HW_QUEUES=8), for the early pass made a B = 4 096
+        # step twice as slow: 0.82 -> 1.6 ms; the default priority it is)
+        self.side2 = torch.cuda.Stream(device=device) if early_stream else None
+        if early_stream and knobs.cu_early > 0:
+            from . import ops
+            self.side2 = ops.cu_range_stream(device, 0, knobs.cu_early)
+        # fork / join events live as long as the step
+        self.ev_fork = torch.cuda.Event() if overlap else None
+        self.ev_join = torch.cuda.Event() if overlap else None
+        self.ev_pre = torch.cuda.Event() if early_stream else None
+        self.ev_early = torch.cuda.Event() if early_stream else None
+        self.ev_fork_a = torch.cuda.Event() if segs["front_b"] is not None else None
+
+    def segments(self):
+        return [self.segs[n] for n in SEGMENT_NAMES if self.segs[n] is not None]
+
+    def wait_early(self):
+        torch.cuda.current_stream().wait_event(self.ev_early)
+
+    def _forked(self, side, tail):
+        main = torch.cuda.current_stream()
+        self.ev_fork.record(main)
+        self.side.wait_event(self.ev_fork)
+        with torch.cuda.stream(self.side):
+            side()
+            self.ev_join.record(self.side)
+        if self.tail_stream is not None:
+            self.tail_stream.wait_event(self.ev_fork)
+            with torch.cuda.stream(self.tail_stream):
+                tail()
+                self.ev_tail.record(self.tail_stream)
+            main.wait_event(self.ev_tail)
+        else:
+            tail()
+        main.wait_event(self.ev_join)
+
+    def run(self, step_no):
+        s = self.segs
+        s["pre"].run()
+        if self.side2 is not None:  # untouched table rows: their own stream, beside everything up to the row update
+            main = torch.cuda.current_stream()
+            self.ev_pre.record(main)
+            self.side2.wait_event(self.ev_pre)
+            with torch.cuda.stream(self.side2):
+                s["early"].run()
+                self.ev_early.record(self.side2)
+        else:
+            s["early"].run()
+        s["front"].run()
+        if s["front_b"] is not None:  # early fork: ready weight-gradient GEMMs beside the rest of the backward chain
+            main = torch.cuda.current_stream()
+            self.ev_fork_a.record(main)
+            self.side.wait_event(self.ev_fork_a)
+            with torch.cuda.stream(self.side):
+                s["side_a"].run()
+            s["front_b"].run()
+        if not self.overlap:
+            s["tail"].run()
+            s["sideq"].run()
+        else:
+            self._forked(s["sideq"].run, s["tail"].run)
+
+
 class TrainStep:
+    """Records the plan of one batch size, asks the optimizer for its lists, builds ONE schedule (PCGradSchedule, OneList
+    or TwoStreams) and replays it.  want_overlap / want_split are what the caller asked for (BaseModel.train_step_runner
+    caches by them), overlap / split_dense what the step does."""
+
     def __init__(self, model, B, use_graph=True, allreduce=None, overlap=None, split_dense=True):
-        overlap = resolve_overlap(overlap)
+        knobs = self.knobs = StepKnobs.from_env()
+        self.want_overlap = overlap = resolve_overlap(overlap)
+        self.want_split = split_dense
         # PCGrad per-task step (PCGradSchedule): a schedule of its own -- one stream, no split table update, no inner fork
         pcg = getattr(model, "_pcgrad_objectives", lambda: None)() == "per_task"
+        par = getattr(model, "_parallel", None)
         if pcg:
-            if getattr(model, "_parallel", None) is not None or allreduce is not None:
+            if par is not None or allreduce is not None:
                 raise NotImplementedError("the PCGrad per-task step runs on one GPU")
             overlap = False
-        self.pcgrad = None
         self.model = model
         self.store = model._store()
         self.opt = model.optimizer()
-        self.want_split = bool(split_dense)
-        rows = None
-        par = getattr(model, "_parallel", None)
         self.par = par
         if allreduce is None and par is not None:
             from .parallel import make_allreduce
             allreduce = make_allreduce(par)
+        self.allreduce = allreduce  # callable(flat dense-gradient arena) or None
+        self.use_graph = bool(use_graph)
+        split = self._record(model, B, pcg, overlap, split_dense, knobs)
+        p = self.plan
+        # every weight-gradient GEMM of the step in one launch: at small batches (a layer's launch does not fill the chip)
+        # and whenever no table stream runs beside them (same-box A/B at B = 65 536: lazy_exact 1.677 -> 1.628 ms, but
+        # dense_exact 1.94 -> 1.98: next to the dense table update the per-layer order shares the chip better)
+        # Round 5, ONE stream (no table update beside the weight gradients): merged at every batch -- the per-layer
+        # launches of a large batch do not all fill the chip either (AE-30's tower layers: 2 tiles x 64 slabs = 128
+        # workgroups for 512 slots), and one reduction over 17 slabs replaces three over 25 / 64 / 64.
+        self.wgrad_merged = (int(B) <= 8192 or self.opt.table_update != "dense_exact" or not overlap) and \
+            knobs.merge_wgrad and p.merge_wgrad()
+        if not overlap and knobs.merge_wgrad:
+            p.merge_wgrad16()  # (the bf16-storage path's launches: csrc/gemm16.hip)
+        opt = self.opt_split = self.opt.calls_split(p, split_dense=split)
+        if pcg and self.opt.table_update == "sparse_rows":
+            opt["pre"] = opt["pre"] + self.opt._unique_pre_calls(p)
+        self.split_dense = bool(opt["early"])
+        self.opt_calls = opt["pre"] + opt["early"] + opt["mlp"] + opt["tables"]
+        # Two streams pay when there is a long table stream to put beside the weight-gradient GEMMs.  The row-wise table
+        # updates have none, and at small batches the fork / join (two more graph seams, ~16 us each) costs more than
+        # the overlap returns -- same-box A/B, lazy_exact on AE-30: 0.374 forked vs 0.338 ms serial at B = 4 096, level
+        # at 16 384, 1.655 vs 1.682 at 65 536 (dense_exact: forked wins at every batch).
+        if overlap and self.opt.table_update != "dense_exact" and int(B) <= 8192 and par is None and allreduce is None:
+            overlap = False
+        self.overlap = bool(overlap)
+        ar = [(E.PY, self._allreduce, (), dict(kernel="all_reduce(mlp grads)"))] if allreduce is not None else []
+        early_stream, wait = early_stream_wait(self.overlap, self.split_dense,
+                                               (E.PY, self._wait_early, (), dict(kernel="wait(early table pass)")))
+        k = _early_fork(knobs, p, opt["tables"], int(B)) if self.overlap and not self.split_dense else 0
+        self.early_fork = k
+        segs = segmented_step(p, opt, ar, wait, self.split_dense,
+                              getattr(p.ops[0], "mark_rows", None) is not None, k, self.use_graph)
+        # (built, and dumped by tools/plan_dump.py, for every step; replayed by TwoStreams only)
+        self.pre, self.early, self.front, self.front_b = segs["pre"], segs["early"], segs["front"], segs["front_b"]
+        self.side_a, self.sideq, self.tail = segs["side_a"], segs["sideq"], segs["tail"]
+        self.whole = self.pcgrad = self.inner_fork = None
+        self.fork_refused = []
+        if pcg:
+            self.schedule = self.pcgrad = PCGradSchedule(p, self.store, self.opt, opt, self.use_graph)
+            self.whole = self.pcgrad.whole
+        elif not self.overlap and not self.split_dense:
+            from . import ops
+            calls, self.fork_refused = whole_step_calls(
+                p, opt, ar, knobs.fork_placement(B), knobs.fork_mlp, [w.data_ptr() for w in ops._workspaces.values()],
+                self._make_fork)
+            self.whole = Segments(calls, self.use_graph)
+            self.schedule = OneList(self.whole)
+        else:
+            self.schedule = TwoStreams(self.store.device, segs, self.overlap, early_stream, knobs, par is None)
+        self.calls = 0
+        self._nX = self._ny = None  # staging buffers of a prefetched batch
+        self._has_next = False
+
+    def _record(self, model, B, pcg, overlap, split_dense, knobs):
+        """What to record, and the recording: sets plan, tower_head_fused and grad_marks; returns whether the dense table
+        update is split."""
+        par = self.par
+        rows = None
         if (self.opt.table_update == "lazy_exact" and getattr(self.opt, "auto", False) and par is not None and
                 par.mode == "table_wise" and self.opt.steps_done == 0 and self.opt.last is None):
             self.opt.table_update = "dense_exact"  # ('auto' picked lazy_exact before the tables were sharded table-wise)
@@ -358,181 +676,26 @@ class TrainStep:
         # rows only (mml_opt_tensor.grad_marks): 24 instead of 28 bytes per Adam parameter, no extra launch.
         marked = ((self.opt.table_update == "dense_exact" or pcg) and not split and
                   (par is None or par.mode in ("row_sharded", "replicated")) and
-                  os.environ.get("MMLREC_GRAD_MARKS", "1") != "0" and not os.environ.get("MMLREC_SCATTER_OLD"))
+                  knobs.grad_marks)
         # one stream (and no split table update, whose early pass forks anyway): the reductions of the head / gate kernels'
         # partial sums are deferred behind the backward chain and merged into ONE launch (Plan.merge_row_reduces)
-        one_list = not overlap and not split and os.environ.get("MMLREC_MERGE_REDUCES", "1") != "0"
+        one_list = not overlap and not split and knobs.merge_reduces
         with E.deferred_reductions(one_list):
             self.plan = model._record(B, True, False, self.store, sparse_rows=None if (lazy or split) else rows,
                                       lazy=lazy or split, mark_rows=rows if (split and par is None) else None,
                                       grad_marks=marked, **(dict(pcgrad=True) if pcg else {}))
+        self.tower_head_fused = False
         if one_list:
             # the top of the network -- last tower layer, heads + BCE, the towers' input gradient -- as one launch where
             # the recorded lists hold that pattern (csrc/tower_head.hip; before the reductions are merged: it brings its own)
             self.tower_head_fused = self.plan.fuse_tower_head()
             self.plan.merge_row_reduces()
         self.grad_marks = getattr(self.plan.ops[0], "grad_marks", None) is not None
-        # every weight-gradient GEMM of the step in one launch: at small batches (a layer's launch does not fill the chip)
-        # and whenever no table stream runs beside them (same-box A/B at B = 65 536: lazy_exact 1.677 -> 1.628 ms, but
-        # dense_exact 1.94 -> 1.98: next to the dense table update the per-layer order shares the chip better)
-        # Round 5, ONE stream (no table update beside the weight gradients): merged at every batch -- the per-layer
-        # launches of a large batch do not all fill the chip either (AE-30's tower layers: 2 tiles x 64 slabs = 128
-        # workgroups for 512 slots), and one reduction over 17 slabs replaces three over 25 / 64 / 64.
-        self.wgrad_merged = (int(B) <= 8192 or self.opt.table_update != "dense_exact" or not overlap) and \
-            os.environ.get("MMLREC_MERGE_WGRAD", "1") != "0" and self.plan.merge_wgrad()
-        if not overlap and os.environ.get("MMLREC_MERGE_WGRAD", "1") != "0":
-            self.plan.merge_wgrad16()  # (the bf16-storage path's launches: csrc/gemm16.hip)
-        self.opt_split = self.opt.calls_split(self.plan, split_dense=split)
-        if pcg and self.opt.table_update == "sparse_rows":
-            self.opt_split["pre"] = self.opt_split["pre"] + self.opt._unique_pre_calls(self.plan)
-        self.split_dense = bool(self.opt_split["early"])
-        self.opt_calls = (self.opt_split["pre"] + self.opt_split["early"] + self.opt_split["mlp"] +
-                          self.opt_split["tables"])
-        self.allreduce = allreduce  # callable(flat dense-gradient arena) or None
-        self.use_graph = bool(use_graph)
-        # Two streams pay when there is a long table stream to put beside the weight-gradient GEMMs.  The row-wise table
-        # updates have none, and at small batches the fork / join (two more graph seams, ~16 us each) costs more than
-        # the overlap returns -- same-box A/B, lazy_exact on AE-30: 0.374 forked vs 0.338 ms serial at B = 4 096, level
-        # at 16 384, 1.655 vs 1.682 at 65 536 (dense_exact: forked wins at every batch).
-        if overlap and self.opt.table_update != "dense_exact" and int(B) <= 8192 and par is None and allreduce is None:
-            overlap = False
-        self.overlap = bool(overlap)
-        self.side = ops_concurrent_stream(self.store.device) if self.overlap else None
-        # CU partition of the forked tail (lab knob MMLREC_CU_TAIL = n: table scatter + table optimizer on compute
-        # units [0, n), weight-gradient GEMMs + MLP optimizer on [n, all))
-        self.tail_stream = None
-        n_tail = int(os.environ.get("MMLREC_CU_TAIL", "0"))
-        if self.overlap and n_tail > 0 and par is None:
-            from . import ops
-            ncu = torch.cuda.get_device_properties(self.store.device).multi_processor_count
-            self.tail_stream = ops.cu_range_stream(self.store.device, 0, n_tail)
-            self.side = ops.cu_range_stream(self.store.device, n_tail, ncu)
-            self.ev_tail = torch.cuda.Event()
-        # (a high-priority stream, or more hardware queues (GPU_MAX_HW_QUEUES=8), for the early pass made a B = 4 096
-        # step twice as slow: 0.82 -> 1.6 ms; the default priority it is)
-        self.side2 = torch.cuda.Stream(device=self.store.device) if (self.overlap and self.split_dense) else None
-        n_early = int(os.environ.get("MMLREC_CU_EARLY", "0"))
-        if self.side2 is not None and n_early > 0:
-            from . import ops
-            self.side2 = ops.cu_range_stream(self.store.device, 0, n_early)
-        # fork / join events live as long as the step
-        self.ev_fork = torch.cuda.Event() if self.overlap else None
-        self.ev_join = torch.cuda.Event() if self.overlap else None
-        self.ev_pre = torch.cuda.Event() if self.side2 is not None else None
-        self.ev_early = torch.cuda.Event() if self.side2 is not None else None
-        p = self.plan
-        ar = [(E.PY, self._allreduce, (), dict(kernel="all_reduce(mlp grads)"))] if allreduce is not None else []
-        # the touched-row update clears the `seen` bits the early pass is still reading: it waits for that pass
-        wait = ([(E.PY, self._wait_early, (), dict(kernel="wait(early table pass)"))] if self.side2 is not None else [])
-        # (without an early pass the counter bump / lazy pre-pass simply lead the front graph; with one, `pre` is
-        # everything the early pass waits for: the counter, and the row list -- from the index pre-pass, or from the
-        # marking gather + compaction that open the forward)
-        n_lead = 2 if (self.split_dense and getattr(p.ops[0], "mark_rows", None) is not None) else 0
-        n_lead += getattr(p, "n_pre", 0) if self.split_dense else 0  # (the magnitude reset / weight pass open `fwd`)
-        self.pre = Segments((self.opt_split["pre"] + p.fwd[:n_lead]) if self.split_dense else [], self.use_graph)
-        self.early = Segments(self.opt_split["early"], self.use_graph, min_calls=1)
-        # Early fork of the side stream: when no long table stream waits in the tail to hide the weight-gradient GEMMs
-        # behind (row-wise table updates, small tables), the GEMMs whose operands the backward chain has already produced
-        # start beside the REST of the chain instead -- worth it where that rest holds HBM-bound launches (PepNet's gate
-        # products, the gate / head row kernels) that leave the matrix pipe idle.  One more graph seam on each stream.
-        k = self._early_fork(p, int(B)) if self.overlap and not self.split_dense else 0
-        self.front = Segments(([] if self.split_dense else self.opt_split["pre"]) + p.fwd[n_lead:] + p.head_train +
-                              (p.bwd[:k] if k else p.bwd), self.use_graph)
-        self.front_b = Segments(p.bwd[k:], self.use_graph, min_calls=1) if k else None
-        side_a = [c for c in p.bwd_side if E.call_meta(c).get("ready", 1 << 30) <= k] if k else []
-        self.side_a = Segments(side_a, self.use_graph, min_calls=1) if k else None
-        self.ev_fork_a = torch.cuda.Event() if k else None
-        self.early_fork = k
-        head_side = list(getattr(p, "head_side", []))
-        self.sideq = Segments(head_side + p.bwd_side[len(side_a):] + ar + self.opt_split["mlp"], self.use_graph)
-        self.tail = Segments(p.bwd_tail + wait + self.opt_split["tables"], self.use_graph)
-        # one stream: the whole step is ONE call list (one HIP graph when it holds no Python-issued entry) -- every graph
-        # seam is ~16 us of idle stream, a tenth of a small-batch step
-        self.whole = None
-        if pcg:
-            self.pcgrad = PCGradSchedule(model, p, self.store, self.opt, self.opt_split)
-            self.whole = Segments(self.pcgrad.calls, self.use_graph)
-            self.fork_refused = []
-        elif not self.overlap and not self.split_dense:
-            # The weight gradients on a second stream INSIDE the step's one graph (a fork / join of graph nodes: no seam):
-            # beside the table scatter and the table optimizer.  Same-box interleaved pairs (tools/lab/ab_env.sh
-            # MMLREC_INNER_FORK=0 / 2, B = 65 536): AE-30 1.4773 / 1.4818 / 1.4860 / 1.4952 / 1.4772 -> 1.4635 / 1.4683 /
-            # 1.4851 / 1.4623 / 1.4731 ms, AE-30d 1.613 -> 1.582, PLE 1.535 -> 1.509, PepNet 2.028 -> 2.006; at B = 4 096
-            # it loses (0.670 -> 0.679 ms), so large batches only.  MMLREC_INNER_FORK: 0 off, 1 joined in front of the table
-            # optimizer (beside the scatter only: level), 2 joined behind it (the default form).
-            # Round 6: the fork makes the step's graph a multi-branch graph, the kind whose launch segfaulted sporadically
-            # in this runtime (hip::Graph::UpdateStreams, see run() below: dependent on how many streams the process
-            # created).  Soaked (tools/lab/fork_soak.sh, profiles/r06_fork_soak.txt): 0 crashes in 32 fresh processes with
-            # the fork forced on for EVERY batch size (22 runs of the suite's graph tests -- every model of the zoo, its
-            # own streams, the original repro's shape -- and 10 of bench.py), so it stays the default for large batches;
-            # it never applies to a step that holds a collective (Python-issued entries between fork and join), i.e. to no
-            # multi-GPU step.  MMLREC_INNER_FORK=0 turns it off.
-            env_fork = os.environ.get("MMLREC_INNER_FORK")
-            inner = int(env_fork) if env_fork is not None else (2 if int(B) >= 16384 else 0)
-            side_calls = head_side + p.bwd_side
-            mid = (p.bwd_tail + self.opt_split["tables"])
-            self.fork_refused = []
-            mlp_side = os.environ.get("MMLREC_FORK_MLP", "0") == "1" and not ar
-            if mlp_side:  # the MLP optimizer behind the weight gradients on their branch (it needs nothing of the other one)
-                side_calls = side_calls + self.opt_split["mlp"]
-            if (inner in (1, 2, 3) and side_calls and not any(c[0] is E.PY for c in side_calls) and
-                    not any(c[0] is E.PY for c in mid)):  # (fork and join must land in ONE graph)
-                from . import ops as _ops
-                bad = fork_conflicts(side_calls, mid, [w.data_ptr() for w in _ops._workspaces.values()])
-                self.fork_refused = bad  # (a step whose branches share a buffer simply runs unforked)
-            if (inner in (1, 2, 3) and side_calls and not any(c[0] is E.PY for c in side_calls) and
-                    not any(c[0] is E.PY for c in mid) and not self.fork_refused):
-                self.inner_fork = InnerFork(self.store.device, side_calls)
-                fk = [(E.INLINE, self.inner_fork.fork, ())]
-                jn = [(E.INLINE, self.inner_fork.join, ())]
-                mid = (fk + p.bwd_tail + jn + self.opt_split["tables"]) if inner == 1 else \
-                    (fk + p.bwd_tail + self.opt_split["tables"] + jn) if inner == 2 else \
-                    (p.bwd_tail + fk + self.opt_split["tables"] + jn)   # (3: forked behind the scatter)
-                self.whole = Segments(self.opt_split["pre"] + p.fwd + p.head_train + p.bwd + mid + ar +
-                                      ([] if mlp_side else self.opt_split["mlp"]), self.use_graph)
-            else:
-                self.whole = Segments(self.opt_split["pre"] + p.fwd + p.head_train + p.bwd + p.bwd_tail +
-                                      self.opt_split["tables"] + head_side + p.bwd_side + ar + self.opt_split["mlp"],
-                                      self.use_graph)
-        self.calls = 0
-        self._nX = self._ny = None  # staging buffers of a prefetched batch
-        self._has_next = False
+        return split
 
-    @staticmethod
-    def _cost(c):
-        meta = E.call_meta(c)
-        return 4e-6 + meta.get("flops", 0.0) / 5e14 + meta.get("bytes", 0.0) / 4e12
-
-    def _early_fork(self, p, B):
-        """Index into plan.bwd at which the side stream forks early (0 = only at the end of the chain).
-        MMLREC_EARLY_WGRAD: unset or 0 = off (the default: measured a loss or level on every workload),
-        n > 0 = that index, "auto" = where the side calls that are ready by then take about as long as the rest of the
-        chain -- but only when the tail has no dense table stream of the same length to put them beside."""
-        env = os.environ.get("MMLREC_EARLY_WGRAD", "0")
-        ready = [E.call_meta(c).get("ready") for c in p.bwd_side]
-        if env == "0" or not p.bwd_side or any(r is None for r in ready) or any(c[0] is E.PY for c in p.bwd):
-            return 0
-        if ready != sorted(ready):  # (program order: a later side call is never ready before an earlier one)
-            return 0
-        if env != "auto":
-            return max(0, min(int(env), len(p.bwd) - 1))
-        side_t = sum(self._cost(c) for c in p.bwd_side)
-        table_t = sum(self._cost(c) for c in self.opt_split["tables"])
-        if os.environ.get("MMLREC_EARLY_WGRAD_DEBUG"):
-            import sys
-            print("early fork: side %.0f us, tables %.0f us, chain %.0f us, ready %s of %d" % (
-                side_t * 1e6, table_t * 1e6, sum(self._cost(c) for c in p.bwd) * 1e6, ready, len(p.bwd)), file=sys.stderr)
-        if B < 16384 or table_t > 0.5 * side_t:
-            return 0
-        best, best_k = 0.0, 0
-        for k in sorted(set(ready)):
-            if k <= 0 or k >= len(p.bwd):
-                continue
-            a = sum(self._cost(c) for c, r in zip(p.bwd_side, ready) if r <= k)
-            rest = sum(self._cost(c) for c in p.bwd[k:])
-            if min(a, rest) > best:
-                best, best_k = min(a, rest), k
-        return best_k if best > 40e-6 else 0
+    def _make_fork(self, side_calls):
+        self.inner_fork = InnerFork(self.store.device, side_calls)
+        return (E.INLINE, self.inner_fork.fork, ()), (E.INLINE, self.inner_fork.join, ())
 
     def prefetch(self, X=None, y=None, fence=None, fill=None):
         """Hand over the NEXT step's batch while this one is still in flight: it is copied into staging buffers (the
@@ -577,10 +740,7 @@ class TrainStep:
             p.X.copy_(X)
             p.y.copy_(y)
             return
-        arr = (L.Copy2dDesc * 2)()
-        for d, (src, dst) in zip(arr, ((X, p.X), (y, p.y))):
-            d.src, d.lds, d.dst, d.ldd = src.data_ptr(), src.stride(0), dst.data_ptr(), dst.stride(0)
-            d.rows, d.cols, d.accumulate = src.shape[0], src.shape[1], 0
+        arr = E.copy2d_descs(((X, p.X), (y, p.y)))
         L.check(L.load().mml_copy2d_batch(arr, 2, torch.cuda.current_stream().cuda_stream), "mml_copy2d_batch")
 
     def drop_prefetch(self):
@@ -593,35 +753,12 @@ class TrainStep:
         self.allreduce(self.store.arena)
 
     def _wait_early(self):
-        torch.cuda.current_stream().wait_event(self.ev_early)
-
-    def _forked(self, side, tail):
-        main = torch.cuda.current_stream()
-        self.ev_fork.record(main)
-        self.side.wait_event(self.ev_fork)
-        with torch.cuda.stream(self.side):
-            side()
-            self.ev_join.record(self.side)
-        if self.tail_stream is not None:
-            self.tail_stream.wait_event(self.ev_fork)
-            with torch.cuda.stream(self.tail_stream):
-                tail()
-                self.ev_tail.record(self.tail_stream)
-            main.wait_event(self.ev_tail)
-        else:
-            tail()
-        main.wait_event(self.ev_join)
+        self.schedule.wait_early()
 
     def run(self):
         """plan.X / plan.y must hold the batch. After the call plan.prob / plan.loss hold this step's outputs.
         The first call runs eagerly (HIP graph capture needs warmed-up state and does not execute what it records);
-        the second call captures, then every call replays.
-
-        With two streams the step is THREE single-stream graph sequences (front, side, tail) forked and joined with
-        events at replay time, not one graph with two branches: hipGraphLaunch of a multi-branch graph walks past the
-        end of the exec's parallel-stream vector when one of those streams shares a hardware queue with the launch
-        stream (hip::Graph::UpdateStreams, ROCm 7.0 runtime bundled with torch 2.10) -- a sporadic segfault that
-        depends on how many streams the process has created.  Single-branch graphs never enter that loop."""
+        the second call captures, then every call replays."""
         profiling.push("train_step")
         if self._has_next:  # the batch handed over by prefetch()
             main = torch.cuda.current_stream()
@@ -632,40 +769,10 @@ class TrainStep:
         if self.use_graph and self.calls == 1:
             torch.cuda.synchronize()
             _quiesce_collective_watchdog()
-            for seg in ((self.whole,) if self.whole is not None else
-                        (self.pre, self.early, self.front, self.front_b, self.side_a, self.sideq, self.tail)):
-                if seg is not None:
-                    seg.capture()
+            for seg in self.schedule.segments():
+                seg.capture()
             torch.cuda.synchronize()
-        if self.pcgrad is not None:
-            self.pcgrad.upload_orders(self.calls)
-        if self.whole is not None:
-            self.whole.run()
-            self._done()
-            return
-        self.pre.run()
-        if self.side2 is not None:  # untouched table rows: their own stream, beside everything up to the row update
-            main = torch.cuda.current_stream()
-            self.ev_pre.record(main)
-            self.side2.wait_event(self.ev_pre)
-            with torch.cuda.stream(self.side2):
-                self.early.run()
-                self.ev_early.record(self.side2)
-        else:
-            self.early.run()
-        self.front.run()
-        if self.front_b is not None:  # early fork: ready weight-gradient GEMMs beside the rest of the backward chain
-            main = torch.cuda.current_stream()
-            self.ev_fork_a.record(main)
-            self.side.wait_event(self.ev_fork_a)
-            with torch.cuda.stream(self.side):
-                self.side_a.run()
-            self.front_b.run()
-        if not self.overlap:
-            self.tail.run()
-            self.sideq.run()
-        else:
-            self._forked(self.sideq.run, self.tail.run)
+        self.schedule.run(self.calls)
         self._done()
 
     def run_gradients(self):

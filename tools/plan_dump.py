@@ -2,13 +2,16 @@
 """Canonical text of a recorded step: every call list of the plan and of the step runner, entry by entry.
 
     python tools/plan_dump.py --workload mmoe_ae30 --batch 65536 [--table-update dense_exact] [--scatter-mode atomic]
-                              [--gemm-mode N] [--streams 2] [--vocab-scale 0.2] [--infer] [--out FILE]
+                              [--gemm-mode N] [--streams 2] [--vocab-scale 0.2] [--split-dense force|off]
+                              [--pcgrad total|per_task] [--infer] [--out FILE]
 
 Two trees record the same step iff their dumps are equal: the before / after check of a change to engine.py or
 trainer.py (diff the two files).  Per entry: the function's name, its meta without pointers, its scalar arguments, and
 every ctypes descriptor walked field by field (fields that are zero are left out).  Device addresses differ from run to
 run, so each is replaced by an ordinal in order of first appearance (`@3`); a bare integer argument counts as an address
-from 2^32 on -- the rule of trainer.fork_conflicts.  Records plans on the GPU, runs no step."""
+from 2^32 on -- the rule of trainer.fork_conflicts.  Records plans on the GPU, runs no step.
+The first line names every option of THIS copy of the tool (pcgrad= and split_dense= since they exist), so a dump differs
+in that line from one an older copy wrote: make both sides of a comparison with one copy (it runs in older trees)."""
 import argparse
 import ctypes as C
 import os
@@ -104,7 +107,11 @@ def dump(args):
     kw = dict(table_update=args.table_update)
     if args.scatter_mode:
         kw["scatter_mode"] = args.scatter_mode
+    if args.pcgrad:  # (the workload's model as model_name "pcg": PCGrad over its tasks)
+        kw.update(seed=0, model_name="pcg")
     model, cfg, _, _ = W.build_model(args.workload, dev, vocab_scale=args.vocab_scale, **kw)
+    if args.pcgrad:
+        model.optim_config["pcgrad_objectives"] = args.pcgrad
     oc = cfg["optim_config"]
     model.compile(oc["optimizer"], oc["loss"], oc["metrics"])
     canon, out = Canon(), []
@@ -116,7 +123,8 @@ def dump(args):
             canon.calls("plan." + name, getattr(plan, name), out)
         return out
     model.train()
-    step = model.train_step_runner(args.batch, overlap=(args.streams == 2))
+    step = model.train_step_runner(args.batch, overlap=(args.streams == 2),
+                                   split_dense={"default": True, "force": "force", "off": False}[args.split_dense])
     for name in PLAN_LISTS:
         canon.calls("plan." + name, getattr(step.plan, name), out)
     for name in ("pre", "early", "mlp", "tables"):
@@ -142,6 +150,10 @@ def main():
     ap.add_argument("--gemm-mode", type=int, default=None, help="mml_gemm_set_mode before the model is built")
     ap.add_argument("--streams", type=int, default=1, choices=[1, 2])
     ap.add_argument("--vocab-scale", type=float, default=1.0)
+    ap.add_argument("--split-dense", default="default", choices=["default", "force", "off"],
+                    help="the split_dense request of train_step_runner: True, 'force' or False")
+    ap.add_argument("--pcgrad", default=None, choices=["total", "per_task"],
+                    help="build the workload as model_name='pcg' with these pcgrad_objectives")
     ap.add_argument("--infer", action="store_true", help="the forward-only plan instead of a training step")
     ap.add_argument("--out", default=None, help="write here instead of stdout")
     args = ap.parse_args()
