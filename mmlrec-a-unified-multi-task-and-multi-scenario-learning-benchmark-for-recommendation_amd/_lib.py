@@ -11,6 +11,11 @@ import torch  # noqa: F401,E402
 from . import build as _build
 
 MAX_FIELDS, MAX_GROUP, MAX_SRC, MAX_EXPERTS, MAX_GATES, MAX_HEADS, MAX_OPT_TENSORS = 64, 16, 8, 16, 8, 8, 32
+# mml_opt_step_dense's launch rule (csrc/optim_ew.hip), mirrored here ONCE for everything that predicts it: a call of at
+# least OPT_STREAM_MIN_PARAMS parameters streams (opt_dense_kernel) when it holds at most OPT_STREAM_MAX_TENSORS tensors
+# or every tensor carries gradient marks; everything else is one opt_flat_kernel launch, which refuses marks.  A table
+# counts as huge -- worth a streaming launch of its own group -- from OPT_HUGE_MIN_PARAMS parameters on.
+OPT_STREAM_MIN_PARAMS, OPT_HUGE_MIN_PARAMS, OPT_STREAM_MAX_TENSORS = 1 << 24, 1 << 22, 4
 MAX_POOLED, POOL_MAX_LEN = 16, 256
 POOL_COMBINERS = {"sum": 0, "mean": 1, "max": 2}
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SIGMOID2 = 0, 1, 2, 3
@@ -352,3 +357,17 @@ def check(rc, what=""):
 def ptr(t):
     """Device (or host) address of a torch tensor, or None."""
     return None if t is None else t.data_ptr()
+
+
+def opt_dense_streams(numel, ntensors, all_marked):
+    """Whether one mml_opt_step_dense call over `ntensors` tensors of `numel` parameters in all launches the streaming
+    kernel (the constants above); False = the flat kernel, which takes no marked tensor."""
+    return numel >= OPT_STREAM_MIN_PARAMS and (ntensors <= OPT_STREAM_MAX_TENSORS or all_marked)
+
+
+def opt_takes_det_totals(numels, all_marked, split=False):
+    """Whether the dense update of the tables of sizes `numels` can take over the deterministic scatter's deferred totals:
+    they are only read by ONE marked streaming launch over all of them.  The scatter asks before it defers
+    (engine.GatherOp.bwd_calls), the optimizer before it accepts (optimizer.dense_table_launches)."""
+    return (all_marked and not split and len(numels) <= MAX_OPT_TENSORS and
+            opt_dense_streams(sum(numels), len(numels), True))

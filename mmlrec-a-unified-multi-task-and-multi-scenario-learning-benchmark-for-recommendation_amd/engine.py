@@ -34,7 +34,7 @@ class PVal:
         self.needs_grad = needs_grad and grad is not None
         self.is_table = is_table
         self.written = 0  # build-time counter: first writer overwrites, later writers accumulate
-        # True: a trained parameter (ParamStore) that changes only in the optimizer -- its magnitude is measured ONCE at
+        # True: a trained parameter (optimizer.ParamStore) that changes only in the optimizer -- its magnitude is measured ONCE at
         # the start of a step.  False: a tensor some op of the step produces (STAR's effective weights, APG's generated
         # ones): measured where it is used.
         self.stable = False
@@ -977,18 +977,6 @@ def scatter_symbol(E):
     return "scatter_fold_kernel" if E in (4, 8, 16) else ("scatter_hash_kernel" if E <= 16 else "scatter_atomic_kernel")
 
 
-def _opt_dense_symbol(numel, ntensors, form=0):
-    """Kernel symbol of a dense optimizer launch (csrc/optim_ew.hip: mml_opt_step_dense's choice).  form: the loop form
-    of the streaming kernel -- 0 plain, 1 two chunks per iteration (MMLREC_OPT_VARIANT bit 1), 2 untouched rows of the
-    split update under a capped grid, 3 marked gradients under a capped grid, 4 marked gradients plus the deferred totals
-    of the deterministic scatter (any grid)."""
-    if not (numel >= (1 << 24) and (ntensors <= 4 or form in (3, 4))):
-        return "opt_flat_kernel"
-    u = {0: 1, 1: 1, 2: 4, 3: int(os.environ.get("MMLREC_OPT_U", "2")),
-         4: 4 if os.environ.get("MMLREC_OPT_U") == "4" else 2}[form]
-    return "opt_dense_kernel<true, %d, %d>" % (form, u)
-
-
 class Op:
     def writes_grad16(self, plan, v):
         """bf16-storage path: this op, as the ONLY consumer of v, writes dL/dv once and can write it as bf16."""
@@ -1021,7 +1009,7 @@ class GatherOp(Op):
         # (BaseModel.scatter_mode = "deterministic"); needs store.ensure_det(tables)
         self.deterministic = None
         # set by bwd_calls when the deterministic scatter leaves its 64-bit row totals to the table optimizer
-        # (MML_SCATTER_DET_DEFER_TOTALS): dict(slot, shift) that Optimizer.calls_split hands to mml_opt_tensor
+        # (MML_SCATTER_DET_DEFER_TOTALS): dict(slot, shift) that optimizer.Optimizer hands to mml_opt_tensor
         self.det_deferred = None
 
     def outputs(self):
@@ -1120,9 +1108,8 @@ class GatherOp(Op):
             # the totals stay in acc64 for the ONE marked streaming launch of the dense table optimizer
             self.det_deferred = None
             # (never in a PCGrad per-task plan: its banks take the fp32 rows of every pass)
-            if (fused and type(self) is GatherOp and self.grad_marks is not None and sr is None and
-                    not getattr(plan, "pcgrad_T", 0) and len(self.tables) <= L.MAX_OPT_TENSORS and
-                    sum(t.data.numel() for t in self.tables) >= (1 << 24)):
+            if (fused and type(self) is GatherOp and sr is None and not getattr(plan, "pcgrad_T", 0) and
+                    L.opt_takes_det_totals([t.data.numel() for t in self.tables], self.grad_marks is not None)):
                 flags |= L.SCATTER_DET_DEFER_TOTALS
                 self.det_deferred = dict(slot=slot, shift=int(lib.mml_scatter_det_shift(plan.B)))
             calls = [(lib.mml_scatter_bwd_det, (gt, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), plan.B,
@@ -1142,7 +1129,7 @@ class GatherOp(Op):
 
 class PooledGatherOp(GatherOp):
     """K1p / K2p: the gather of a schema with multi-valued (pooled) fields and its scatter backward.  `tables` holds
-    every TABLE once (the order of ParamStore.table_names, which is also the order of the touched-row bookkeeping);
+    every TABLE once (the order of optimizer.ParamStore.table_names, which is also the order of the touched-row bookkeeping);
     `singles` = [(X column, table number)], `pooled` = [(first X column, maxlen, combiner, table number, length column
     or None)] (model.utils.pooled_layout)."""
 
@@ -2633,450 +2620,6 @@ class PAddOp(Op):
                 calls.append((L.load().mml_copy2d, (self.out.grad.data_ptr(), n, p.grad.data_ptr(), n, 1, n, _claim(p)),
                               dict(kernel="copy2d_kernel", side=True)))
         return calls
-
-
-# ==================================================================================================
-# parameter store + optimizer state shared by all plans of one model
-# ==================================================================================================
-class TableRows:
-    """Bookkeeping for the sparse-row table update: per-table `seen` bitmaps + the touched-row list."""
-
-    def __init__(self, vocab, device, cap):
-        self.rowbase = [0]
-        for v in vocab:
-            self.rowbase.append(self.rowbase[-1] + int(v))
-        self.seen = [torch.zeros((int(v) + 31) // 32, dtype=torch.int32, device=device) for v in vocab]
-        # one byte per row, all-zero between launches: rows are marked with plain stores, a compaction pass turns the
-        # marks into the bitmaps + the list (include/mmlrec.h: row_marks)
-        self.marks = torch.zeros(ops.marks_bytes(vocab), dtype=torch.uint8, device=device)
-        self.touched = torch.zeros(max(int(cap), 1), dtype=torch.int32, device=device)
-        self.count = torch.zeros(1, dtype=torch.int32, device=device)
-
-
-class ParamStore:
-    """Gradient buffers and optimizer state for one model on one device.
-
-    Dense (MLP) parameter gradients live in ONE flat arena (a single buffer to all-reduce under data parallelism);
-    every table gets a dense [V,E] accumulator that is kept all-zero between steps (the optimizer kernels re-zero
-    what they consume), so the scatter can add into it without a per-step 400 MB memset."""
-
-    def __init__(self, model, device):
-        self.device = device
-        self.model = model
-        tables, dense = [], []
-        for name, p in model.named_parameters():
-            (tables if name.startswith("embedding_dict.") else dense).append((name, p))
-        self.sig = tuple(p.data_ptr() for _, p in tables + dense)
-        total = sum(p.numel() for _, p in dense)
-        self.arena = torch.zeros(max(total, 1), dtype=torch.float32, device=device)
-        self.pvals = {}
-        off = 0
-        for name, p in dense:
-            g = self.arena[off:off + p.numel()].view(p.shape)
-            off += p.numel()
-            self.pvals[name] = PVal(p.data, g, name)
-            self.pvals[name].stable = True
-        self.table_names = [n for n, _ in tables]
-        for name, p in tables:
-            self.pvals[name] = PVal(p.data, None, name, is_table=True)
-        par = getattr(model, "_parallel", None)
-        if par is not None and par.mode == "row_sharded":
-            # the trained rows of this rank live in ONE flat buffer (parallel.RowSharding); the full per-field tables
-            # stay registered (state_dict / predict contract) but are never written by a step
-            self.pvals["embedding_shard"] = PVal(par.shard, None, "embedding_shard", is_table=True)
-            self.table_names = ["embedding_shard"]
-        self.table_grads_ready = False
-        self.opt = None
-        self.rows = None
-        self.extra = {}  # derived / frozen tensors registered by models (STAR)
-
-    def ensure_table_grads(self):
-        if not self.table_grads_ready:
-            for n in self.table_names:
-                pv = self.pvals[n]
-                pv.grad = torch.zeros_like(pv.data)
-                pv.needs_grad = True
-            self.table_grads_ready = True
-
-    def ensure_rows(self, cap, names=None):
-        """Touched-row bookkeeping over the tables this rank updates (all of them unless `names` is given)."""
-        names = list(self.table_names if names is None else names)
-        if self.rows is None or self.rows.touched.numel() < cap or self.rows_names != names:
-            self.rows = TableRows([self.pvals[n].data.shape[0] for n in names], self.device, cap)
-            self.rows_names = names
-        return self.rows
-
-    def ensure_grad_marks(self, tables):
-        """Byte map over the rows of `tables` (a gather's field order; ops.marks_bytes layout) for the marked-gradient
-        dense update.  Returns (map, byte offset of every table)."""
-        vocab = [int(t.data.shape[0]) for t in tables]
-        key = tuple(t.data.data_ptr() for t in tables)
-        if getattr(self, "_grad_marks_key", None) != key:
-            self.grad_marks = torch.zeros(ops.marks_bytes(vocab), dtype=torch.uint8, device=self.device)
-            self._grad_marks_key = key
-        base, off = [], 0
-        for v in vocab:
-            base.append(off)
-            off += (v + 31) // 32 * 32
-        return self.grad_marks, base
-
-    def grad_marks_by_table(self, gop):
-        """{id(table): its rows' slice of the mark map} for the tables of a gather whose scatter marks rows; {} for one
-        that does not (or for no gather at all)."""
-        gm = getattr(gop, "grad_marks", None)
-        if gm is None:
-            return {}
-        _, base = self.ensure_grad_marks(gop.tables)
-        return {id(t): gm[base[f]:base[f] + t.data.shape[0]] for f, t in enumerate(gop.tables)}
-
-    def ensure_det(self, tables):
-        """Buffers of the deterministic scatter for `tables` (a gather's field order): int64 [V, E] totals per table (kept
-        all zero between steps by the scatter's second launch, or by the table optimizer that takes the totals over), a
-        mark map of its own and a magnitude slot."""
-        key = tuple(t.data.data_ptr() for t in tables)
-        if getattr(self, "_det_key", None) != key:
-            uniq = {}
-            for t in tables:
-                uniq.setdefault(t.data.data_ptr(), torch.zeros(t.data.shape, dtype=torch.int64, device=self.device))
-            self._det = dict(acc64=[uniq[t.data.data_ptr()] for t in tables],
-                             marks=torch.zeros(ops.marks_bytes([int(t.data.shape[0]) for t in tables]), dtype=torch.uint8,
-                                               device=self.device),
-                             slot=ops.amax_slots(1, self.device)[0])
-            self._det_key = key
-        return self._det
-
-    def stale(self):
-        return self.sig != tuple(p.data_ptr() for _, p in self.model.named_parameters())
-
-    def reset_written(self):
-        for pv in self.pvals.values():
-            pv.written = 0
-        for pv in self.extra.values():
-            pv.written = 0
-
-
-class _OptState(dict):
-    """name -> (state1, state2), zero-initialised on first use (a row-sharded run never touches the full tables)."""
-
-    def __init__(self, store, kind):
-        super().__init__()
-        self.store, self.kind = store, kind
-
-    def __missing__(self, name):
-        pv = self.store.pvals[name]
-        s1 = torch.zeros_like(pv.data) if self.kind != "sgd" else None
-        s2 = torch.zeros_like(pv.data) if self.kind == "adam" else None
-        self[name] = (s1, s2)
-        return self[name]
-
-
-class Optimizer:
-    """K8 front end: dense update for MLP parameters; for the tables one of
-      dense_exact : every row every step, like the reference's torch.optim over dense gradients;
-      sparse_rows : rows of the batch only -- exactly the dense result for SGD / Adagrad, "lazy Adam" otherwise;
-      lazy_exact  : rows of the batch only, but the zero-gradient steps a row skipped are replayed before it is next
-                    read (mml_opt_catchup_rows) and for all rows before evaluation (flush): the dense Adam / RMSprop
-                    trajectory at sparse cost (SURVEY.md A14 "hard part" solved without changing results).
-    'auto' = sparse_rows for SGD / Adagrad (exactly the dense result); for Adam / RMSprop lazy_exact where it is
-    available -- embedding width 4, 8 or 16, one table per field, no regulariser on the tables (round 4: the same
-    dense trajectory, tests at 2e-6, at 51 M instead of 37 M samples/s on AE-30 incl. the flush of a 500-step epoch) --
-    else dense_exact.  MMLREC_AUTO_TABLE_UPDATE=dense_exact keeps the reference's literal schedule under 'auto'."""
-
-    def __init__(self, store, kind, lr, table_update="auto"):
-        self.store, self.kind, self.lr = store, kind, float(lr)
-        if kind not in L.OPT_KINDS:
-            raise NotImplementedError(kind)  # model/basemodel.py:581
-        self.auto = table_update == "auto"
-        if table_update == "auto":
-            if kind in ("sgd", "adagrad"):
-                table_update = "sparse_rows"
-            else:
-                import os
-                tabs = [p for n, p in store.model.named_parameters() if n.startswith("embedding_dict.")]
-                widths = {int(p.shape[1]) for p in tabs}
-                cols = store.model._sparse_cols() if hasattr(store.model, "_sparse_cols") else []
-                one_per_field = len({f.embedding_name for f in cols}) == len(cols)
-                # (small tables: the literal dense update of a few hundred thousand parameters is one short launch, the
-                # row bookkeeping of lazy_exact -- mark + compact, catch-up, row update: four launches -- costs more than it
-                # saves; KuaiRec-32's 24 k rows x 16: 90 us of bookkeeping against ~5 us, round 5)
-                big = sum(p.numel() for p in tabs) > int(os.environ.get("MMLREC_LAZY_MIN_PARAMS", str(1 << 22)))
-                ok = (bool(tabs) and widths <= {4, 8, 16} and len(widths) == 1 and one_per_field and big and
-                      os.environ.get("MMLREC_AUTO_TABLE_UPDATE", "lazy_exact") == "lazy_exact")
-                table_update = "lazy_exact" if ok else "dense_exact"
-            if self._table_reg(self._reg_map()):  # a regulariser on the tables moves every row every step
-                table_update = "dense_exact"
-        if table_update == "lazy_exact" and kind in ("sgd", "adagrad"):
-            table_update = "sparse_rows"  # nothing to replay: zero gradients do not move these optimizers
-        if table_update not in ("dense_exact", "sparse_rows", "lazy_exact"):
-            raise ValueError("table_update must be auto, dense_exact, sparse_rows or lazy_exact")
-        self.table_update = table_update
-        self.last = None   # lazy_exact: per-table int32 [V] "row is current as of step"
-        self.dirty = False
-        dev = store.device
-        self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.state = _OptState(store, kind)  # moments are allocated when a tensor is first updated
-        self.steps_done = 0
-
-    def calls(self, plan):
-        """Optimizer call list for one step (appended after a plan's backward)."""
-        c = self.calls_split(plan)
-        return c["pre"] + c["early"] + c["mlp"] + c["tables"]
-
-    def can_split_dense(self, plan):
-        """The dense table update may run as (untouched rows early, next to the forward) + (touched rows after the
-        scatter): needs the batch's row set before the forward (mml_index_unique: E <= 16, indices on this rank) and
-        an update that is the same function of (p, g, state) in both kernels (no regulariser on the tables)."""
-        if self.table_update != "dense_exact" or self._table_reg(self._reg_map()):
-            return False
-        gop = plan.ops[0] if plan.ops else None
-        if not isinstance(gop, GatherOp) or isinstance(gop, PooledGatherOp):  # (the pooled gather marks no rows)
-            return False
-        return all(t.data.shape[1] <= 16 and t.data.shape[1] % 4 == 0 for t in gop.tables)
-
-    def calls_split(self, plan, split_dense=False):
-        """{'pre': step-counter bump (+ the index pre-pass), 'early': the untouched-rows half of a split dense table
-        update (may run beside the forward / backward), 'mlp': dense MLP update, 'tables': table update (+ touched-list
-        reset)} so a trainer can put them on different streams."""
-        lib = L.load()
-        st = self.store
-        pre = [(lib.mml_counter_update, (self.step_dev.data_ptr(), 1, 0))]
-        if self.table_update == "lazy_exact":
-            pre += self._lazy_pre_calls(plan)
-        split_dense = bool(split_dense) and self.can_split_dense(plan)
-        if split_dense and getattr(plan.ops[0], "mark_rows", None) is None:  # (else the gather itself lists the rows)
-            pre += self._unique_pre_calls(plan)
-        calls = []
-        reg = self._reg_map()
-        # (a regularised parameter is updated even when no gradient reaches it -- the reference's dead PLE tensors,
-        # SURVEY D10: its arena slice stays zero, the update sees the regulariser's gradient alone)
-        dense = [(pv, n) for n, pv in st.pvals.items()
-                 if not pv.is_table and pv.grad is not None and (pv.written or pv.data.data_ptr() in reg)]
-        entries = [(pv.data, pv.grad) + self.state[n] + (reg.get(pv.data.data_ptr()),) for pv, n in dense]
-        tabs = [st.pvals[n] for n in st.table_names if st.pvals[n].written]
-        tnames = [n for n in st.table_names if st.pvals[n].written]
-        treg = self._table_reg(reg)
-        if treg and self.table_update != "dense_exact":
-            raise NotImplementedError("l2_reg_embedding / l1 on the tables makes every row's gradient non-zero: use "
-                                      "table_update='dense_exact' (the reference's own dense optimizer)")
-        hyper = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev, zero_grad=False)
-        plan.keep.append(hyper)
-        if entries:
-            arr = ops.make_opt_tensors(entries)
-            plan.keep.append(arr)
-            per = {"sgd": 12, "adam": 28, "adagrad": 20, "rmsprop": 20}[self.kind]
-            calls.append((lib.mml_opt_step_dense, (arr, len(entries), C.byref(hyper)),
-                          dict(kernel=_opt_dense_symbol(sum(e[0].numel() for e in entries), len(entries)),
-                               bytes=float(per) * sum(e[0].numel() for e in entries))))
-        mlp_calls, calls, early = calls, [], []
-        if tabs:
-            if self.table_update == "dense_exact":
-                # the early half of a split update shares the chip with the forward / backward; its grid can be capped
-                # (mml_opt_hyper.max_blocks, MMLREC_EARLY_BLOCKS) so that it leaves them wave slots.  Same-box A/B runs
-                # (B = 65 536 and 4 096, caps 512 .. 2048) stayed inside the run-to-run noise, so the default is the
-                # full grid, at which the stream runs at its stand-alone bandwidth.
-                # Round 3: the single marked launch runs beside the weight-gradient GEMMs of the side stream.  Every loop
-                # form is its own kernel (csrc/optim_ew.hip: the plain loop at 54 VGPRs / 8 waves per SIMD, two chunks per
-                # thread at 100 / 4, four at 172 / 2, eight at 256 / 1).  Alone (same box, ms): two chunks 0.39-0.44, plain
-                # 0.43-0.49, four chunks 0.47-0.50, eight 0.85.  In the step (three interleaved repetitions on a quiet box):
-                # plain 1.928, two chunks 1.912, four chunks under a 3072-workgroup cap 1.883 -- the two-wave form leaves
-                # the GEMMs their registers -- but on other boxes the three are level within the +-3 % drift of a run.
-                # Default: two chunks on the full grid, the best stream by itself (0.66-0.74 of 8 TB/s) and level in the
-                # step; MMLREC_TAIL_BLOCKS (workgroup cap, 0 = plain loop) / MMLREC_OPT_U override.
-                cap = int(os.environ.get("MMLREC_EARLY_BLOCKS", "0")) if split_dense else \
-                    int(os.environ.get("MMLREC_TAIL_BLOCKS", str(1 << 20)))
-                hz = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev, zero_grad=not split_dense,
-                                    max_blocks=cap)
-                plan.keep.append(hz)
-                # p, g, m, v read + p, m, v written; the split form never reads g
-                per = {"sgd": 12, "adam": 28, "adagrad": 20, "rmsprop": 20}[self.kind] - (4 if split_dense else 0)
-                # one C call = one launch (the same size rule mml_opt_step_dense applies inside a call), so that a
-                # call's label is the kernel symbol a profiler reports
-                # the huge tables stream through opt_dense_kernel<true> (one call), every other table shares one
-                # balanced opt_flat_kernel launch (the same split mml_opt_step_dense makes for a mixed call)
-                big = [i for i in range(len(tabs)) if tabs[i].data.numel() >= (1 << 22)]
-                if len(big) > 4 or sum(tabs[i].data.numel() for i in big) < (1 << 24):
-                    big = []
-                small = [i for i in range(len(tabs)) if i not in big]
-                groups = [g_ for g_ in (big, small) if g_]
-                seen_of = {}
-                if split_dense:
-                    seen_of = dict(zip(st.rows_names, st.rows.seen))
-                # marked gradients (the scatter of this plan marked every row it added to): the streaming launch does not
-                # read the gradient of unmarked rows -- 24 instead of 28 bytes per Adam parameter
-                gop = plan.ops[0] if plan.ops else None
-                marks_of = {} if split_dense else st.grad_marks_by_table(gop)
-                # Round 6, built and measured, NOT the default: every table in ONE marked streaming launch (workgroups dealt
-                # in proportion to the tables' sizes, csrc/optim_ew.hip) instead of the streaming launch of the huge tables
-                # + a flat launch of the small ones (AE-30: 26 tables, 31-34 us).  Two call lists over ONE model replayed in
-                # alternating blocks, both orders (tools/lab/ab_inproc.py --shared, profiles/r06_tail_lab.txt): the single
-                # launch is 13 us per step SLOWER (workgroups dealt in proportion to the sizes) or 8 us slower (every tensor
-                # the grid a launch of its own would get, small tables first: the form kept).  MMLREC_OPT_ONE_LAUNCH=1: on.
-                one_launch = (big and small and cap > 0 and len(tabs) <= L.MAX_OPT_TENSORS and not split_dense and
-                              all(id(t) in marks_of for t in tabs) and
-                              os.environ.get("MMLREC_OPT_ONE_LAUNCH", "0") == "1")
-                # Deterministic scatter with deferred totals (GatherOp.det_deferred): the scatter's second launch is
-                # folded into this one -- every table in ONE marked streaming launch that adds the marked rows' 64-bit
-                # totals to the gradient it reads (mml_opt_tensor.acc64) -- so the small tables cannot go to the flat
-                # kernel, which reads neither marks nor totals
-                dd = getattr(gop, "det_deferred", None)
-                acc_of = {}
-                if dd is not None:
-                    if (split_dense or {id(t) for t in tabs} != {id(t) for t in gop.tables} or
-                            not all(id(t) in marks_of for t in tabs)):
-                        raise L.MMLError("the deterministic scatter deferred its totals to a marked dense update of "
-                                         "exactly its tables")
-                    acc_of = {id(t): a for t, a in zip(gop.tables, gop.deterministic["acc64"])}
-                    one_launch = True
-                if one_launch:
-                    big = small + big   # (the small tables' workgroups first: they start with the launch)
-                    groups = [big]
-                for grp in groups:
-                    marked = grp is big and all(id(tabs[i]) in marks_of for i in grp)
-                    arr = ops.make_opt_tensors([(tabs[i].data, tabs[i].grad) + self.state[tnames[i]] +
-                                                (treg, seen_of.get(tnames[i]), marks_of[id(tabs[i])] if marked else None,
-                                                 (acc_of[id(tabs[i])], dd["slot"], dd["shift"]) if dd else None)
-                                                for i in grp])
-                    plan.keep.append(arr)
-                    numel = sum(tabs[i].data.numel() for i in grp)
-                    nbytes = float(per) * numel
-                    v = int(os.environ.get("MMLREC_OPT_VARIANT", "0"))
-                    form = (4 if dd else 3 if (cap > 0 and marked) else 2 if (cap > 0 and split_dense) else
-                            1 if (v & 2 and not marked and not split_dense) else 0)
-                    if marked:  # g is read for the touched rows only (~1 %): count the mark bytes instead
-                        nbytes += sum(tabs[i].data.shape[0] - 4.0 * tabs[i].data.numel() for i in grp)
-                    m = dict(kernel=_opt_dense_symbol(numel, len(grp), form), bytes=nbytes)
-                    if dd:  # (+ 32 bytes of totals read and zeroed per 16-byte chunk of a marked row; the buffers the
-                        # descriptors hide from trainer.fork_conflicts)
-                        m.update(det_acc64=True, ptrs=[dd["slot"].data_ptr()] + [a.data_ptr() for a in acc_of.values()])
-                    (early if split_dense else calls).append((lib.mml_opt_step_dense, (arr, len(grp), C.byref(hz)), m))
-            if self.table_update != "dense_exact" or split_dense:
-                rows = st.rows
-                lazy = self.table_update == "lazy_exact"
-                F = len(tabs)
-                E = tabs[0].data.shape[1]
-                pt = ops._ptr_array([pv.data for pv in tabs])
-                pg = ops._ptr_array([pv.grad for pv in tabs])
-                p1 = ops._ptr_array([self.state[n][0] for n in tnames]) if self.kind != "sgd" else None
-                p2 = ops._ptr_array([self.state[n][1] for n in tnames]) if self.kind == "adam" else None
-                ps = ops._ptr_array(rows.seen)
-                rb = (L.i64 * (F + 1))(*rows.rowbase)
-                plan.keep += [pt, pg, p1, p2, ps, rb]
-                pl = ops._ptr_array([self.last[n] for n in tnames]) if lazy else None
-                plan.keep.append(pl)
-                calls.append((lib.mml_opt_step_rows, (pt, pg, p1, p2, ps, rb, F, E, rows.touched.data_ptr(),
-                                                      rows.count.data_ptr(), rows.touched.numel(), pl,
-                                                      C.byref(hyper)), dict(kernel="opt_rows_kernel")))
-                # the list is REBUILT every step by the compaction that follows the marking kernels (E in 4, 8, 16: it
-                # resets the counter itself); only the appending atomic path needs the reset here
-                if E not in (4, 8, 16) or os.environ.get("MMLREC_SCATTER_OLD"):
-                    calls.append((lib.mml_counter_update, (rows.count.data_ptr(), 0, 1)))
-        return {"pre": pre, "early": early, "mlp": mlp_calls, "tables": calls}
-
-    def _unique_pre_calls(self, plan):
-        """Index pre-pass of the split dense update: the batch's distinct rows -> `seen` bitmaps + touched list."""
-        lib, st = L.load(), self.store
-        gop = plan.ops[0]
-        names, rows = st.table_names, st.rows
-        if rows is None or list(st.rows_names) != list(names):
-            raise L.MMLError("split dense update needs ParamStore.ensure_rows over every table")
-        F = len(names)
-        E = st.pvals[names[0]].data.shape[1]
-        vocab = (L.i64 * F)(*[st.pvals[n].data.shape[0] for n in names])
-        ps = ops._ptr_array(rows.seen)
-        rb = (L.i64 * (F + 1))(*rows.rowbase)
-        X, nrows = gop.index_view(plan)
-        col = (L.i32 * F)(*gop.cols)
-        plan.keep += [vocab, ps, rb, col]
-        return gop.pre_index_calls(plan) + [
-            (lib.mml_index_unique, (vocab, col, F, E, X.data_ptr(), ops._ld(X), nrows, ps, rb,
-                                    rows.touched.data_ptr(), rows.count.data_ptr(), rows.touched.numel(),
-                                    rows.marks.data_ptr(), plan.status.data_ptr()),
-             dict(kernel="mark_rows_kernel+rows_compact_kernel", bytes=float(nrows) * F * 5))]
-
-    # ---- regulariser (model/basemodel.py:524-540) ---------------------------------------------------------
-    def _reg_map(self):
-        """data_ptr -> (l1, l2) summed over the groups the model registered with add_regularization_weight."""
-        out = {}
-        for weight_list, l1, l2 in getattr(self.store.model, "regularization_weight", []):
-            if not (l1 > 0 or l2 > 0):
-                continue
-            for w in weight_list:
-                p = w[1] if isinstance(w, tuple) else w
-                a, b = out.get(p.data_ptr(), (0.0, 0.0))
-                out[p.data_ptr()] = (a + float(l1), b + float(l2))
-        return out
-
-    def _table_reg(self, reg):
-        """(l1, l2) of the embedding tables (one setting for all of them: l2_reg_embedding), or None."""
-        vals = {reg[p.data_ptr()] for n, p in self.store.model.named_parameters()
-                if n.startswith("embedding_dict.") and p.data_ptr() in reg}
-        if not vals:
-            return None
-        if len(vals) > 1:
-            raise NotImplementedError("different regularisers on different embedding tables")
-        return vals.pop()
-
-    # ---- lazy_exact ----------------------------------------------------------------------------------
-    def _lazy_pre_calls(self, plan):
-        """Before the gather: unique rows of the batch (LDS dedup on the indices) -> replay their skipped steps."""
-        lib, st = L.load(), self.store
-        gop = plan.ops[0]
-        names = st.table_names
-        rows = st.rows
-        if self.last is None:
-            self.last = {n: torch.zeros(st.pvals[n].data.shape[0], dtype=torch.int32, device=st.device) for n in names}
-        F = len(names)
-        E = st.pvals[names[0]].data.shape[1]
-        vocab = (L.i64 * F)(*[st.pvals[n].data.shape[0] for n in names])
-        ps = ops._ptr_array(rows.seen)
-        rb = (L.i64 * (F + 1))(*rows.rowbase)
-        pt = ops._ptr_array([st.pvals[n].data for n in names])
-        p1 = ops._ptr_array([self.state[n][0] for n in names])
-        p2 = ops._ptr_array([self.state[n][1] for n in names]) if self.kind == "adam" else None
-        pl = ops._ptr_array([self.last[n] for n in names])
-        hyper = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev)
-        plan.keep += [vocab, ps, rb, pt, p1, p2, pl, hyper]
-        catchup = (lib.mml_opt_catchup_rows, (pt, p1, p2, pl, rb, F, E, rows.touched.data_ptr(), rows.count.data_ptr(),
-                                              rows.touched.numel(), C.byref(hyper)), dict(kernel="opt_catchup_kernel"))
-        if getattr(gop, "owns_lazy", False):
-            # row-sharded tables: the keys to bring up to date only exist on the owner after the index exchange, so
-            # the gather op launches (unique -> catch-up) itself, on the flat shard (F == 1)
-            if F != 1:
-                raise L.MMLError("row-sharded lazy_exact expects the single flat shard")
-
-            def launch(keys_ptr, n, stream):
-                if n:
-                    L.check(lib.mml_index_unique_idx32(vocab, 1, E, keys_ptr, 1, n, ps, rb, rows.touched.data_ptr(),
-                                                       rows.count.data_ptr(), rows.touched.numel(),
-                                                       rows.marks.data_ptr(), plan.status.data_ptr(), stream),
-                            "mml_index_unique_idx32")
-                    L.check(catchup[0](*catchup[1], stream), "mml_opt_catchup_rows")
-            gop.lazy_launch = launch
-            return []
-        if not isinstance(gop, GatherOp):
-            raise L.MMLError("lazy_exact table updates are not available on the table-wise sharded path")
-        if isinstance(gop, PooledGatherOp):
-            return gop.pre_index_calls(plan) + gop.unique_calls(plan, rows) + [catchup]
-        X, nrows = gop.index_view(plan)
-        col = (L.i32 * F)(*gop.cols)
-        plan.keep.append(col)
-        return gop.pre_index_calls(plan) + [
-            (lib.mml_index_unique, (vocab, col, F, E, X.data_ptr(), ops._ld(X), nrows, ps, rb,
-                                    rows.touched.data_ptr(), rows.count.data_ptr(), rows.touched.numel(),
-                                    rows.marks.data_ptr(), plan.status.data_ptr()),
-             dict(kernel="mark_rows_kernel+rows_compact_kernel", bytes=float(nrows) * F * 5)),
-            catchup,
-        ]
-
-    def flush(self):
-        """Bring EVERY table row to the current step (needed before anything outside the fused step reads a table)."""
-        if self.table_update != "lazy_exact" or not self.dirty or self.last is None:
-            return
-        hyper = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev)
-        for n in self.store.table_names:
-            s1, s2 = self.state[n]
-            ops.opt_catchup_dense(self.store.pvals[n].data, s1, s2 if self.kind == "adam" else None, self.last[n], hyper)
-        self.dirty = False
 
 
 # ---- PCGrad per-task step (reference model/optimizer.py:10-138; trainer.PCGradSchedule) --------------------------------

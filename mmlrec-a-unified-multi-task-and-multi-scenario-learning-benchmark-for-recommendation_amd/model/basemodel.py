@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import engine as E
+from .. import optimizer as O
 from .. import ops
 from .. import profiling
 from .utils import (DenseFeat, PredictionLayer, SparseFeat, VarLenSparseFeat, build_input_features,
@@ -255,7 +256,7 @@ class BaseModel(nn.Module):
             dev = next(self.parameters()).device
             if dev.type != "cuda":
                 raise L.MMLError("mmlrec_amd models run on an MI355X only: move the model to cuda (no CPU fallback)")
-            st = E.ParamStore(self, dev)
+            st = O.ParamStore(self, dev)
             self._caches = {"store": st, "plans": {}, "steps": {}}
         return st
 
@@ -623,7 +624,7 @@ class BaseModel(nn.Module):
         store = self._store()
         opt = getattr(self, "_optimizer", None)
         if opt is None or opt.store is not store:
-            opt = E.Optimizer(store, self.optim_name, self.optim_config.get("lr", 1e-3), self.table_update)
+            opt = O.Optimizer(store, self.optim_name, self.optim_config.get("lr", 1e-3), self.table_update)
             self._optimizer = opt
         return opt
 

@@ -29,6 +29,7 @@ import torch
 
 from . import _lib as L
 from . import engine as E
+from . import optimizer as O
 from . import ops
 
 
@@ -240,7 +241,7 @@ class _RouteSet:
         self.send_keys = torch.empty(B * F, dtype=torch.int32, device=dev)
         self.pos = torch.empty(B, F, dtype=torch.int32, device=dev)
         if op.dedup:
-            self.req = E.TableRows(sh.vocab, dev, B * F)      # requester-side row set of the batch (full vocabulary)
+            self.req = O.TableRows(sh.vocab, dev, B * F)      # requester-side row set of the batch (full vocabulary)
             self.req_seen = ops._ptr_array(self.req.seen)
             self.req_rb = (L.i64 * (F + 1))(*self.req.rowbase)
             self.slot_of = torch.empty(self.req.rowbase[-1], dtype=torch.int32, device=dev)
@@ -257,7 +258,7 @@ class RowShardedGatherOp(E.Op):
         self.shard, self.X, self.cols, self.dense_col0, self.nd, self.out = shard_pv, X, cols, dense_col0, nd, out
         self.sparse_rows = sparse_rows
         self.lazy_launch = None
-        self.tables = [shard_pv]   # (engine.Optimizer: the one table this op's scatter feeds)
+        self.tables = [shard_pv]   # (optimizer.Optimizer: the one table this op's scatter feeds)
         self.grad_marks = None     # byte per shard row: marked-gradient dense update (engine.GatherOp.grad_marks)
         # requester-side de-duplication: the exchange carries every DISTINCT row of the local batch once (under Zipf a
         # 65 536-sample AE-30 batch holds 209 k distinct rows against 1.97 M lookups), gradients of duplicates are

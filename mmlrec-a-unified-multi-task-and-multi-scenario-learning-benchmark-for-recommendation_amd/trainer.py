@@ -593,7 +593,7 @@ class TrainStep:
             p.merge_wgrad16()  # (the bf16-storage path's launches: csrc/gemm16.hip)
         opt = self.opt_split = self.opt.calls_split(p, split_dense=split)
         if pcg and self.opt.table_update == "sparse_rows":
-            opt["pre"] = opt["pre"] + self.opt._unique_pre_calls(p)
+            opt["pre"] = opt["pre"] + self.opt.index_pre_calls(p)
         self.split_dense = bool(opt["early"])
         self.opt_calls = opt["pre"] + opt["early"] + opt["mlp"] + opt["tables"]
         # Two streams pay when there is a long table stream to put beside the weight-gradient GEMMs.  The row-wise table
@@ -644,7 +644,7 @@ class TrainStep:
         lazy = self.opt.table_update == "lazy_exact" or (pcg and self.opt.table_update == "sparse_rows")
         if lazy and par is not None and par.mode == "table_wise":
             raise NotImplementedError("lazy_exact table updates on the table-wise sharded path (use row_sharded)")
-        # Split dense table update (engine.Optimizer.can_split_dense): the reference-exact dense optimizer as
+        # Split dense table update (optimizer.Optimizer.can_split_dense): the reference-exact dense optimizer as
         #   early : every row the batch does NOT touch (zero gradient), streamed beside the forward / backward,
         #   tables: the touched rows, with their gradients, after the scatter (mml_opt_step_rows)
         # -- the same arithmetic on every row as one dense launch.  Same-box A/B on AE-30: 0.70-0.76 against 0.77 ms at
@@ -653,11 +653,9 @@ class TrainStep:
         # not mark (grad_marks below: 24 instead of 28 bytes per Adam parameter, no extra launch or stream) the two
         # are level at B = 4 096 too (0.767 / 0.769 ms on one box), so the split form only runs on request
         # (split_dense="force").
-        split = (split_dense == "force" and self.opt.table_update == "dense_exact" and not pcg and
-                 (par is None or par.mode == "replicated") and
+        split = (split_dense == "force" and not pcg and (par is None or par.mode == "replicated") and
                  not model._pooled_cols() and  # (the pooled gather marks no rows: the single-launch schedule)
-                 not self.opt._table_reg(self.opt._reg_map()) and model.embedding_size <= 16 and
-                 model.embedding_size % 4 == 0)
+                 self.opt.split_dense_ok([model.embedding_size]))
         if self.opt.table_update in ("sparse_rows", "lazy_exact") or split:
             if par is None:
                 rows = self.store.ensure_rows(int(B) * max(model._lookups_per_sample(), 1))

@@ -1,5 +1,5 @@
 """The fused deterministic step: the scatter takes the magnitude of d(dnn_input) from the GEMM that wrote it and leaves
-its 64-bit row totals to the table optimizer (engine.GatherOp.bwd_calls, engine.Optimizer.calls_split) -- against the
+its 64-bit row totals to the table optimizer (engine.GatherOp.bwd_calls, optimizer.Optimizer.calls_split) -- against the
 same step with MMLREC_DET_FUSED=0 (magnitude pass + finalize launch), bit for bit."""
 import pytest
 
