@@ -10,7 +10,9 @@ kernels do this); otherwise consumers add raw contributions and one `mml_act_bwd
 """
 import contextlib
 import ctypes as C
+import dataclasses
 import os
+import typing
 
 import torch
 
@@ -98,9 +100,44 @@ def _claim(x):
     return acc
 
 
+@dataclasses.dataclass(frozen=True)
+class PlanKnobs:
+    """Every environment switch the recorder and the passes read, read ONCE per Plan (from_env; never at import: tests and
+    lab scripts set the variables between constructions) and kept as plan.knobs.  The A/B behind a switch stands where
+    the switch is used.  MMLREC_DEFER_REDUCE is not here: it overrides a context, not a plan (_defer_reduce)."""
+    amax: typing.Optional[bool] = None  # MMLREC_AMAX=0 / 1: the two-plane fp16 GEMMs off / on; unset: from B = 32 768 on
+    bf16_storage: bool = True    # MMLREC_BF16_STORAGE=0: fp32 buffers under GEMM mode 1 too (operands rounded in registers)
+    gemm_planes: bool = True     # MMLREC_GEMM_PLANES=0: no pre-cut weight planes, every wave cuts the fragment it stages
+    merge_copies: bool = True    # MMLREC_MERGE_COPIES=0: neighbouring strided copies stay one launch each
+    amax_merge: bool = True      # MMLREC_AMAX_MERGE=0: the weights' magnitudes in a launch of their own (round 3)
+    nt_group: int = L.NT_MAX_GROUP  # MMLREC_NT_GROUP=n: problems per merged gemm_nt_kernel launch (16: round 5's launches)
+    tower_head: bool = True      # MMLREC_TOWER_HEAD=0: last tower layer, heads and the towers' dgrad stay three launches
+    gather_wgmax: bool = True    # MMLREC_GATHER_WGMAX=0: the gathered input's magnitude from a pass over the whole output
+    det_fused: bool = True       # MMLREC_DET_FUSED=0: the deterministic scatter measures and finalizes for itself
+    grad_parts: bool = True      # MMLREC_GRAD_PARTS=0: gate products that share a factor accumulate into ONE buffer, in order
+    grad_cols: bool = True       # MMLREC_GRAD_COLS=0: the input gradient is formed for every column, read or not
+    split_dgrad: bool = True     # MMLREC_SPLIT_DGRAD=0: a many-source input gradient stays ONE problem at small batches
+
+    @classmethod
+    def from_env(cls, env=None):
+        env = os.environ if env is None else env
+
+        def on(name):
+            return env.get(name, "1") != "0"
+
+        return cls(amax={"0": False, "1": True}.get(env.get("MMLREC_AMAX", "")),
+                   bf16_storage=on("MMLREC_BF16_STORAGE"), gemm_planes=on("MMLREC_GEMM_PLANES"),
+                   merge_copies=on("MMLREC_MERGE_COPIES"), amax_merge=on("MMLREC_AMAX_MERGE"),
+                   nt_group=min(L.NT_MAX_GROUP, max(1, int(env.get("MMLREC_NT_GROUP", str(L.NT_MAX_GROUP))))),
+                   tower_head=on("MMLREC_TOWER_HEAD"), gather_wgmax=on("MMLREC_GATHER_WGMAX"),
+                   det_fused=on("MMLREC_DET_FUSED"), grad_parts=on("MMLREC_GRAD_PARTS"), grad_cols=on("MMLREC_GRAD_COLS"),
+                   split_dgrad=on("MMLREC_SPLIT_DGRAD"))
+
+
 class Plan:
     def __init__(self, device, B, training, use_amax=None):
         self.device, self.B, self.training = device, int(B), bool(training)
+        knobs = self.knobs = PlanKnobs.from_env()
         self.ops = []
         self.fwd, self.head_infer, self.head_train, self.head_bwd, self.bwd = [], [], [], [], []
         # backward is kept in three pieces so a trainer can overlap them on two HIP streams: `bwd` = the critical
@@ -134,8 +171,7 @@ class Plan:
         # weights of the end of round 3: 32 768: 1.272 -> 1.244 ms (lazy_exact 0.927 -> 0.894), 16 384: 0.994 -> 1.036,
         # 8 192: 0.760 -> 0.802, 4 096: 0.696 -> 0.720.  So: on from 32 768 samples per step, the three-plane bf16 form
         # below.  MMLREC_AMAX=0 / 1 forces.
-        env = os.environ.get("MMLREC_AMAX", "")
-        self.use_amax = (env != "0") and (env == "1" or self.B >= 32768)
+        self.use_amax = knobs.amax if knobs.amax is not None else self.B >= 32768
         if use_amax is False:
             # (a PCGrad per-task plan replays its backward once per objective: the gradient slots only ever rise within a
             # step, so a later pass would cut its operands with an earlier pass's magnitudes)
@@ -145,11 +181,13 @@ class Plan:
         # GEMM mode 1 (operands rounded to bf16) the values and gradients that only GEMMs read are STORED as bf16 and the
         # layer groups that read them run csrc/gemm16.hip -- same products, half the activation traffic, no conversion in
         # the kernels.  Models mark such values (Plan.val(store16=True)); MMLREC_BF16_STORAGE=0 keeps fp32 buffers.
-        self.bf16 = (device.type == "cuda" and os.environ.get("MMLREC_BF16_STORAGE", "1") != "0" and
+        self.bf16 = (device.type == "cuda" and knobs.bf16_storage and
                      L.load().mml_gemm_get_mode() == 1)
         if self.bf16:
             self.use_amax = False  # (mode 1 reads no operand magnitudes)
-        self.tower_head = None   # the mml_tower_head_group of the fused top of the network (fuse_tower_head), if any
+        # the mml_tower_head_group of the fused top of the network (passes.fuse_tower_head), if any: such a plan's `fwd` no
+        # longer writes the heads' input, so only run_train_fwd_bwd replays it (_refuse_fused)
+        self.tower_head = None
         self.cast16_items = []   # (fp32 weight, bf16 copy, transposed): refreshed by ONE launch at the start of a step
         self.cast16_cache = {}
         self.amax_pool = ops.amax_slots(1024, device) if (device.type == "cuda" and self.use_amax) else None
@@ -160,7 +198,8 @@ class Plan:
         # GEMMs read, cut once at the start of a step instead of by every wave that stages a fragment of it
         self.planes_items = []   # (W, planes, layout, [slots], kexp)
         self.planes_cache = {}
-        self.n_pre = 0           # entries of `fwd` that precede the first op's calls
+        self.n_pre = 0           # entries of `fwd` that precede the first op's calls (prepend)
+        self.amax_pre_done = self.cast16_pre_done = False  # passes.amax_prologue / cast16_prologue ran
 
     # ---- buffers -----------------------------------------------------------------------------
     def empty(self, *shape, dtype=torch.float32):
@@ -262,7 +301,7 @@ class Plan:
         (None, None): only stable weights in nn.Linear layout whose magnitude is taken at the start of the step.
         padded: the launch reads the zero-padded operand (q["Wp"], reduction extent rounded up to 16): the planes are cut
         from the weight itself into a zero-initialised buffer of the padded shape."""
-        if self.amax_pool is None or os.environ.get("MMLREC_GEMM_PLANES", "1") == "0":
+        if self.amax_pool is None or not self.knobs.gemm_planes:
             return None, None
         qs = [q] if group is None else group
         slots = []
@@ -365,12 +404,12 @@ class Plan:
             v.gamax, v.gamax_writers = slot, v.written
         return slot
 
-    def amax_call(self, need, **meta):
+    def amax_call(self, need, lib=None, **meta):
         arr = ops.make_amax_descs(need)
         self.keep.append(arr)
         m = dict(kernel="amax_kernel", bytes=4.0 * sum(t.numel() for t, _ in need), need=list(need))
         m.update(meta)
-        return (L.load().mml_amax_batch, (arr, len(need)), m)
+        return ((lib or L.load()).mml_amax_batch, (arr, len(need)), m)
 
     # ---- execution ---------------------------------------------------------------------------
     @staticmethod
@@ -433,7 +472,13 @@ class Plan:
             # launches are priced in FLOPs (`flops`) but still move their operands -- bench.py's whole-step fraction
             e["hbm_bytes"] = e.get("hbm_bytes", 0.0) + meta.get("hbm_bytes", meta.get("bytes", 0.0))
 
+    def _refuse_fused(self, what):
+        if self.tower_head is not None:
+            raise L.MMLError(f"{what} on a plan rewritten by fuse_tower_head: its forward no longer stores the heads' "
+                             "input, which this entry point reads (run_train_fwd_bwd replays such a plan)")
+
     def run_forward(self):
+        self._refuse_fused("run_forward")
         self._run(self.fwd)
         self._run(self.head_infer)
 
@@ -447,12 +492,19 @@ class Plan:
         self._run(self.bwd_side)
 
     def run_backward_from_dprob(self):
+        self._refuse_fused("run_backward_from_dprob")
         self._run(self.head_bwd)
         self._run(self.bwd)
         self._run(self.bwd_tail)
         self._run(self.bwd_side)
 
     # ---- graph recording ---------------------------------------------------------------------
+    def prepend(self, calls):
+        """Puts `calls` in front of `fwd`: the ONE way entries get there (the prologues of passes.py, the step counter of an
+        uncompiled model with dropout), so n_pre counts them all -- trainer.segmented_step cuts the forward by it."""
+        self.fwd[:0] = calls
+        self.n_pre += len(calls)
+
     def add(self, op):
         self.ops.append(op)
         seen = set()
@@ -470,9 +522,10 @@ class Plan:
             if isinstance(v, Val) and v.needs_grad:
                 v.consumers.append(head_op)
         self.head_infer = head_op.infer_calls(self)
+        from . import passes  # (passes imports this module)
         if not self.training:
-            self._amax_prologue()
-            self._cast16_prologue()
+            passes.amax_prologue(self)
+            passes.cast16_prologue(self)
             return
         calls = head_op.train_calls(self, use_dprob=False)
         self.head_train = [c for c in calls if not call_meta(c).get("side")]
@@ -500,446 +553,14 @@ class Plan:
             # a side call reads dL/d(this op's outputs) and forward values only: it may start once the chain has issued
             # everything up to and including this op's own entries (TrainStep's early fork of the side stream)
             for c in mine:
-                call_meta(c)["ready"] = len(self.bwd)
-        self._amax_prologue()
-        self._cast16_prologue()
-        if os.environ.get("MMLREC_MERGE_COPIES", "1") != "0":
-            for name in ("fwd", "bwd", "bwd_tail", "bwd_side", "head_train", "head_bwd"):
-                where = [] if name == "bwd" else None
-                setattr(self, name, self._merge_copies(getattr(self, name), where=where))
-                if name == "bwd" and where:
-                    # the side calls' `ready` tags count entries of the UNMERGED chain: into the merged list's index
-                    # space (ready = k: the first k entries have been issued -> everything up to the merged entry that
-                    # holds old entry k - 1)
-                    for c in list(self.bwd_side) + list(self.head_side):
-                        m = call_meta(c)
-                        if m.get("ready"):
-                            m["ready"] = where[min(m["ready"], len(where)) - 1] + 1
+                call_meta(c)["ready"] = len(self.bwd)  # (an index into `bwd`: passes.reindex_ready)
+        passes.amax_prologue(self)
+        passes.cast16_prologue(self)
+        passes.merge_plan_copies(self)
         # (Measured on MI355X: issuing every weight-gradient partial-product GEMM before the first reduction -- the
         # phased wgrad entry point allows it -- makes the step SLOWER, 2.35 ms vs 2.19 ms: the GEMMs then run next to
         # the table scatter and the dense table optimizer for longer and all of them are HBM-bound together.  The
         # list stays in program order: partial products and reduction of one layer back to back.)
-
-    def _merge_copies(self, calls, lib=None, where=None):
-        """Runs of neighbouring strided copies (mml_copy2d / mml_copy2d_batch: concat / split of feature blocks, gradient
-        hand-overs of shared parameters) as ONE launch each -- inside a step's graph every launch takes >= 4.6 us from
-        start to end, and PepNet's step had four of them in a row three times.  A copy joins the run only if it touches
-        nothing an earlier copy of the run writes, and writes nothing an earlier one reads (one launch has no order).
-        where: a list that receives, per input call, the index of the output entry it went into."""
-        lib = lib or L.load()  # (tests/test_plan_passes_cpu.py passes stand-ins: only the functions' identity is used)
-        f1, fb = lib.mml_copy2d, lib.mml_copy2d_batch
-
-        def descs_of(c):
-            if c[0] is f1:
-                src, lds, dst, ldd, rows, cols, acc = c[1]
-                return [(src, lds, dst, ldd, rows, cols, acc, None)]
-            arr, n = c[1]
-            # (the 8th entry: an item's optional magnitude slot, mml_copy2d_desc.amax_out -- stand-in arrays of the CPU
-            #  tests need not have the field)
-            return [(arr[k].src, arr[k].lds, arr[k].dst, arr[k].ldd, arr[k].rows, arr[k].cols, arr[k].accumulate,
-                     getattr(arr[k], "amax_out", None)) for k in range(n)]
-
-        def span(ptr, ld, rows, cols):
-            return (ptr, ld, rows, cols)
-
-        def hits(a, b):
-            """Do the [rows, cols] regions a, b (pointer, pitch, rows, cols; float32) share an element?  Exact for regions of
-            one pitch (column blocks of one buffer: the concat / split case), the byte-interval test otherwise."""
-            (pa, la, ra, ca), (pb, lb, rb, cb) = a, b
-            ea, eb = pa + 4 * ((max(ra, 1) - 1) * la + ca), pb + 4 * ((max(rb, 1) - 1) * lb + cb)
-            if not (pa < eb and pb < ea):
-                return False
-            if la == lb and la > 0 and (pb - pa) % 4 == 0:
-                delta = (pb - pa) // 4
-                q, r = divmod(delta, la)   # b's origin in a's grid: row q, column r (Python's floor semantics)
-                if ca <= la and r + cb <= la:
-                    rows_meet = q < ra and q + rb > 0
-                    cols_meet = r < ca and r + cb > 0
-                    return rows_meet and cols_meet
-            return True
-
-        out, run, meta_run = [], [], []
-        pos = [0] * len(calls)
-        run_src = []
-
-        def flush():
-            if not run:
-                return
-            for i_ in run_src:
-                pos[i_] = len(out)
-            run_src.clear()
-            if len(meta_run) == 1:
-                out.append(meta_run[0])
-            else:
-                arr = (L.Copy2dDesc * len(run))()
-                for d, (src, lds, dst, ldd, rows, cols, acc, am) in zip(arr, run):
-                    d.src, d.lds, d.dst, d.ldd, d.rows, d.cols, d.accumulate = src, lds, dst, ldd, rows, cols, acc
-                    if am:
-                        d.amax_out = am
-                self.keep.append(arr)
-                meta = dict(kernel="copy2d_batch_kernel",
-                            bytes=sum(8.0 * r[4] * r[5] for r in run))
-                for c in meta_run:  # (the scheduling tags of the merged calls: they were neighbours of ONE list)
-                    m = call_meta(c)
-                    for k in ("side", "tail", "rank", "ready"):
-                        if k in m:
-                            meta[k] = max(meta.get(k, m[k]), m[k]) if k == "ready" else m[k]
-                out.append((fb, (arr, len(run)), meta))
-            run.clear()
-            meta_run.clear()
-
-        for ci, c in enumerate(calls):
-            if c[0] is f1 or c[0] is fb:
-                ds = descs_of(c)
-                ok = len(run) + len(ds) <= 32
-                for (src, lds, dst, ldd, rows, cols, acc, _am) in ds:
-                    rs, ws = span(src, lds, rows, cols), span(dst, ldd, rows, cols)
-                    for (s2, l2, d2, ld2, r2, c2, a2, _am2) in run:
-                        rs2, ws2 = span(s2, l2, r2, c2), span(d2, ld2, r2, c2)
-                        if hits(rs, ws2) or hits(ws, rs2) or hits(ws, ws2):
-                            ok = False
-                if not ok:
-                    flush()
-                run.extend(ds)
-                meta_run.append(c)
-                run_src.append(ci)
-            else:
-                flush()
-                pos[ci] = len(out)
-                out.append(c)
-        flush()
-        if where is not None:
-            where[:] = pos
-        return out
-
-    def _cast16_prologue(self):
-        """bf16-storage path: the bf16 copies of the weights, ONE launch in front of everything else; and the promise
-        behind every bf16 value -- only bf16-storage layer groups read it -- is checked."""
-        for op in list(self.ops) + [getattr(self, "head_op", None)]:
-            for v in (op.inputs() if op is not None else []):
-                if isinstance(v, Val) and v.is16 and isinstance(op, GateGroupOp) and any(v is e for e in op.experts):
-                    continue  # (the fast gate kernels read bf16 expert outputs: mml_gate_group.out_bf16 bit 3)
-                if isinstance(v, Val) and v.is16 and not (isinstance(op, LinearGroupOp) and op.use16):
-                    raise L.MMLError(f"bf16 value {v.name!r} is read by {type(op).__name__}: only bf16-storage layer "
-                                     "groups may read a store16 value")
-        if not self.cast16_items or getattr(self, "_cast16_done", False):
-            return
-        arr = ops.make_cast16_descs(self.cast16_items)
-        self.keep.append(arr)
-        n = sum(w.numel() for w, _, _ in self.cast16_items)
-        self.fwd.insert(0, (L.load().mml_cast16_batch, (arr, len(self.cast16_items)),
-                            dict(kernel="cast16_kernel", bytes=6.0 * n)))
-        self.n_pre += 1
-        self._cast16_done = True
-
-    def _amax_prologue(self):
-        """Zero EVERY magnitude slot of the plan (forward and backward ones: the producers only ever raise them) and
-        measure the stable weights, as the first entries of `fwd`.  Called when the whole plan has been recorded."""
-        if self.amax_pool is None or not self.amax_next or self.n_pre:
-            return
-        lib = L.load()
-        pre = [(lib.mml_amax_reset, (self.amax_pool.data_ptr(), self.amax_next),
-                dict(kernel="amax_reset", bytes=32.0 * self.amax_next))]
-        cut = []
-        if self.planes_items:  # (after the magnitudes of the weights: the cut reads them)
-            arr = ops.make_planes_descs(self.planes_items)
-            self.keep.append(arr)
-            cut.append((lib.mml_gemm_planes_cut, (arr, len(self.planes_items)),
-                        dict(kernel="planes_cut_kernel", bytes=8.0 * sum((it[0][0] if isinstance(it[0], tuple) else it[0]).numel()
-                                                                        for it in self.planes_items))))
-        # The weights' magnitudes ride in the magnitude launch that stands in front of the first GEMM anyway (the pass over
-        # the gathered input): one launch fewer at the head of the step (~6 us of a 1.7 ms step).  Nothing in front of the
-        # first GEMM reads a weight's slot or planes.  MMLREC_AMAX_MERGE=0: the separate launch of round 3.
-        first_gemm = next((i for i, c in enumerate(self.fwd) if c[0] in (lib.mml_gemm_grouped_fwd, lib.mml_pep_gate_fwd)),
-                          len(self.fwd))
-        host = next((i for i, c in enumerate(self.fwd[:first_gemm]) if c[0] is lib.mml_amax_batch and
-                     "need" in call_meta(c)), None)
-        if self.amax_wlist and host is not None and os.environ.get("MMLREC_AMAX_MERGE", "1") != "0":
-            c = self.fwd[host]
-            merged = self.amax_call(call_meta(c)["need"] + self.amax_wlist,
-                                    **{k: v for k, v in call_meta(c).items() if k not in ("kernel", "bytes", "need")})
-            self.fwd = self.fwd[:host] + [merged] + cut + self.fwd[host + 1:]
-        else:
-            if self.amax_wlist:
-                pre.append(self.amax_call(self.amax_wlist))
-            pre += cut
-        self.fwd = pre + self.fwd
-        self.n_pre = len(pre)
-
-    def merge_wgrad(self):
-        """Small batches: every weight-gradient GEMM of the step in ONE grouped launch (+ one reduction) instead of one
-        pair per layer.  At M = 4 096 a layer's launch fills a fraction of the chip for ~15 us; together they take the
-        time of the longest (lazy_exact step on AE-30: 0.327 -> see DESIGN 10.12).  Only when every problem writes its
-        own dW (a weight shared by two layers is written by two launches in order).  At large batches the per-layer
-        order stays: each launch fills the chip by itself and the reductions interleave with the next GEMM."""
-        lib = L.load()
-        fn = lib.mml_gemm_grouped_wgrad_phase
-        idx = [i for i, c in enumerate(self.bwd_side) if c[0] is fn]
-        if len(idx) <= 2:
-            return False
-        descs, groups = [], []
-        for i in idx:
-            c = self.bwd_side[i]
-            if c[1][4] == 1:  # the partial-product phase carries the problems (phase 2 repeats them)
-                groups.append([c[1][0][k] for k in range(c[1][1])])
-                descs += groups[-1]
-        chunks = [descs]  # (small batches: ONE call, the library splits it into groups of MML_MAX_GROUP for the tile kernel)
-        if self.B >= 16384:
-            # Large batches (gemm_nt_kernel: 128 x 128 output tiles, the batch cut into `slabs` pieces so that tiles x
-            # slabs fill the chip's 512 workgroup slots once; at most MML_MAX_GROUP problems per launch): merge when the
-            # merged launches take fewer batch steps than the per-layer launches together, a launch + reduction pair
-            # priced at ~8 steps.  AE-30: 20 / 8 / 2 tiles -> 82 + 32 + 32 steps per layer against 121 merged (measured
-            # 1.65 -> 1.565 ms); KuaiRec-32: 72 / 32 / 4 tiles -> 293 + 128 + 32 against 512 merged (108 tiles x 4 slabs
-            # leave 80 slots idle: 3.33 -> 3.38 ms merged, so it stays per layer); PepNet's 40-odd small problems go
-            # into launches of 16 (2.21 -> 2.13 ms already as ONE call that fell to the tile kernel).
-            steps = self.B // 32
-            # (what gemm_nt_kernel takes -- csrc/gemm_nt.hip, mml_gemm_nt_try_wgrad -- goes together: ONE problem it does
-            # not take, e.g. a final layer with a single output row, would send its whole launch to the tile kernel)
-            serves = [bool(lib.mml_gemm_nt_serves(C.byref(d))) for d in descs]  # (the library's own predicate)
-            fits = [d for d, ok in zip(descs, serves) if ok]
-            other = [d for d, ok in zip(descs, serves) if not ok]
-            chunks = []
-            # (round 6: gemm_nt_kernel takes 48 problems per launch; MMLREC_NT_GROUP=16 restores the launches of round 5)
-            nt_group = min(L.NT_MAX_GROUP, max(1, int(os.environ.get("MMLREC_NT_GROUP", str(L.NT_MAX_GROUP)))))
-            for part in (fits, other):
-                if part:
-                    nch = -(-len(part) // (nt_group if part is fits else L.MAX_GROUP))
-                    per = -(-len(part) // nch)
-                    chunks += [part[i:i + per] for i in range(0, len(part), per)]
-
-            def cost(tiles):
-                sl = max(1, min(512 // max(tiles, 1), steps // 8, 64))
-                return -(-steps // sl) * -(-tiles * sl // 512) + 8
-
-            def tiles_of(g):
-                return sum(-(-d.N // 128) * -(-d.K // 128) for d in g)
-
-            if sum(cost(tiles_of(g)) for g in chunks) >= sum(cost(tiles_of(g)) for g in groups):
-                return False
-        targets = [d.dW for d in descs] + [d.dbias for d in descs if d.dbias]
-        if len(set(targets)) != len(targets) or any(d.accumulate for d in descs):
-            return False
-        flops = sum(call_meta(self.bwd_side[i]).get("flops", 0.0) for i in idx)
-        hbm = sum(call_meta(self.bwd_side[i]).get("hbm_bytes", 0.0) for i in idx)
-        merged, reduces = [], []
-        for ch in chunks:
-            arr = (L.GemmWgradDesc * len(ch))()
-            for k, d in enumerate(ch):
-                C.memmove(C.byref(arr[k]), C.byref(d), C.sizeof(L.GemmWgradDesc))
-            nbytes = lib.mml_gemm_grouped_wgrad_workspace_bytes(arr, len(ch))
-            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
-            self.keep += [arr, ws]
-            share = len(ch) / float(len(descs))
-            merged.append((fn, (arr, len(ch), ws.data_ptr(), ws.numel(), 1),
-                           dict(kernel=_gemm_symbol(False, False, [], 2), flops=flops * share, hbm_bytes=hbm * share,
-                                side=True, rank=0)))
-            reduces.append((fn, (arr, len(ch), ws.data_ptr(), ws.numel(), 2),
-                            dict(kernel="slab_reduce", bytes=float(nbytes), side=True, rank=1)))
-        rest = [c for i, c in enumerate(self.bwd_side) if i not in set(idx)]  # (un-padding copies: after the reduction)
-        # (each reduction right behind its launch: the next launch's first tiles start beside it)
-        self.bwd_side = [c for pair in zip(merged, reduces) for c in pair] + rest
-        return True
-
-    def fuse_tower_head(self):
-        """K5' (csrc/tower_head.hip): the last tower layer of every task, the heads + summed BCE and the towers' input gradient
-        -- three launches of the recorded step -- as ONE launch (+ its share of the batched reduction), when the recorded
-        lists hold exactly that pattern: a forward launch of T Linear + ReLU problems whose outputs are the T heads' inputs and
-        nothing else's, the deferred head launch, and an input-gradient launch of T single-source problems over the heads'
-        dH.  Rewrites fwd / head_train / head_side / bwd of THIS plan (a TrainStep's own: the forward-only and the dL/dprob
-        lists of a model's cached plans are never touched).  MMLREC_TOWER_HEAD=0: off."""
-        lib = L.load()
-        if (os.environ.get("MMLREC_TOWER_HEAD", "1") == "0" or self.amax_pool is None or self.bf16 or
-                self.device.type != "cuda"):
-            return False
-        fh, ff, fd = lib.mml_head_bce_fwd_bwd_phase, lib.mml_gemm_grouped_fwd, lib.mml_gemm_grouped_dgrad
-        if len(self.head_train) != 1 or len(self.head_side) != 1:
-            return False
-        hc, hs = self.head_train[0], self.head_side[0]
-        if hc[0] is not fh or hs[0] is not fh or hc[1][3] != 1 or hs[1][3] != 2:
-            return False
-        grp = hc[1][0]._obj
-        T = int(grp.n_heads)
-        if grp.dh_bf16 or grp.dprob or not grp.y or not grp.prob or T < 1:
-            return False
-        heads = [grp.head[t] for t in range(T)]
-        if any(h.gate or h.w2 or not h.dH or not h.h_relu or not h.dw or not h.dbias for h in heads):
-            return False
-        hin = {int(h.Hin): t for t, h in enumerate(heads)}
-        dh = {int(h.dH): t for t, h in enumerate(heads)}
-        if len(hin) != T or len(dh) != T:
-            return False
-        # the forward launch that writes the heads' inputs
-        fi = None
-        for i in range(len(self.fwd) - 1, -1, -1):
-            c = self.fwd[i]
-            if c[0] is ff and c[1][1] == T and all(int(c[1][0][k].C or 0) in hin for k in range(T)):
-                fi = i
-                break
-        if fi is None:
-            return False
-        fdesc = self.fwd[fi][1][0]
-        # the input-gradient launch over the heads' dH
-        di = None
-        for i, c in enumerate(self.bwd):
-            if c[0] is fd and c[1][1] == T and all(c[1][0][k].n_src == 1 and int(c[1][0][k].dC[0] or 0) in dh for k in range(T)):
-                di = i
-                break
-        if di is None:
-            return False
-        ddesc = self.bwd[di][1][0]
-        by_t_f = {hin[int(fdesc[k].C)]: fdesc[k] for k in range(T)}
-        by_t_d = {dh[int(ddesc[k].dC[0])]: ddesc[k] for k in range(T)}
-        if len(by_t_f) != T or len(by_t_d) != T:
-            return False
-        g = L.TowerHeadGroup()
-        g.n, g.M = T, int(grp.B)
-        g.prob, g.ldprob, g.y, g.ldy, g.mask, g.ldmask, g.loss = grp.prob, grp.ldprob, grp.y, grp.ldy, grp.mask, grp.ldmask, grp.loss
-        for t in range(T):
-            f, d, h = by_t_f[t], by_t_d[t], heads[t]
-            if (f.act != L.ACT_RELU or f.w_kn or f.mul or not f.w_planes or not f.w_kexp or not f.amax_a or f.M != g.M or
-                    f.N != h.H or int(f.ldc) != int(h.ldh)):
-                return False
-            if (d.gate_h or d.Y or d.relu_mask or d.act != L.ACT_NONE or d.accumulate or d.w_kn[0] or not d.w_planes[0] or
-                    not d.w_kexp[0] or not d.dA or d.K != f.K or d.N[0] != f.N or int(d.W[0] or 0) != int(f.W or 0) or
-                    int(d.lddc[0]) != int(h.lddh)):
-                return False
-            q = g.t[t]
-            q.A, q.lda, q.amax_a, q.K, q.N = f.A, f.lda, f.amax_a, f.K, f.N
-            q.w_planes_fwd, q.ldpf, q.kexp_fwd = f.w_planes, f.ldw, f.w_kexp
-            q.w_planes_bwd, q.ldpb, q.kexp_bwd = d.w_planes[0], d.ldw[0], d.w_kexp[0]
-            q.bias1, q.w, q.hbias, q.hbias2, q.n_hbias2 = f.bias, h.w, h.bias, h.bias2, h.n_bias2
-            q.dH, q.lddh, q.dA, q.ldda, q.dw, q.dhbias = h.dH, h.lddh, d.dA, d.ldda, h.dw, h.dbias
-            q.amax_dH, q.amax_dA = grp.amax_dH, d.amax_out
-            q.mask_col, q.head, q.kind = h.mask_col, t, h.kind
-        if not lib.mml_tower_head_serves(C.byref(g)):
-            return False
-        nws = int(lib.mml_tower_head_workspace_bytes(C.byref(g)))
-        ws = torch.empty(max(nws, 256), dtype=torch.uint8, device=self.device)
-        self.keep += [g, ws]
-        K, N = int(g.t[0].K), int(g.t[0].N)
-        byts = 4.0 * g.M * T * (2 * K + N + 3)
-        fused = (lib.mml_tower_head_fwd_bwd, (C.byref(g), ws.data_ptr(), ws.numel(), 1),
-                 dict(kernel="tower_head_kernel", bytes=byts, hbm_bytes=byts))
-        red = (lib.mml_tower_head_fwd_bwd, (C.byref(g), ws.data_ptr(), ws.numel(), 2),
-               dict(kernel="slab_reduce", bytes=float(nws), side=True, rank=1, ready=0))
-        del self.fwd[fi]
-        del self.bwd[di]
-        for c in list(self.bwd_side) + list(self.head_side):  # (`ready` counts entries of the backward chain)
-            m = call_meta(c)
-            if m.get("ready", 0) > di:
-                m["ready"] -= 1
-        self.head_train = [fused]
-        self.head_side = [red]
-        self.tower_head = g
-        return True
-
-    def merge_row_reduces(self, lib=None):
-        """The deferred reductions of the head / gate kernels' partial sums (`head_side`, and the gate groups' entries of
-        `bwd_side`: only the optimizer and the host read their results) as ONE launch in front of the weight gradients
-        (as few as the launch's segment capacity allows)."""
-        lib = lib or L.load()  # (tests/test_plan_passes_cpu.py passes stand-ins: only the functions' identity is used)
-        fh, fg = lib.mml_head_bce_fwd_bwd_phase, lib.mml_gate_mix_bwd_phase
-        ft = getattr(lib, "mml_tower_head_fwd_bwd", None)  # (K5': Plan.fuse_tower_head)
-        is_red = lambda c: c[0] in (fh, fg, ft) and c[0] is not None and c[1][3] == 2  # noqa: E731
-        picked = [c for c in list(self.head_side) + list(self.bwd_side) if is_red(c)]
-        if len(picked) < 2:
-            return False
-
-        def segments(c):
-            """Reduction segments the C side makes of this item (csrc/gate_head.hip, phase 2): a head group one per dw and
-            dbias of every head plus the loss, a gate group one per active gate's dWg."""
-            g = c[1][0]._obj
-            if c[0] is fh:
-                return 2 * int(g.n_heads) + (1 if g.loss else 0)
-            if c[0] is ft:
-                return 2 * int(g.n) + (1 if g.loss else 0)
-            return sum(1 for k in range(int(g.n_gates)) if g.gate[k].active)
-
-        # one launch takes at most MAX_REDUCE_SEGS segments (csrc/reduce.hpp): a deep PLE (7 tasks x 4 levels: 15 + 8 + 8 +
-        # 8 + 7 = 46) goes into as many launches as it needs, in list order
-        chunks, cur, nseg = [], [], 0
-        for c in picked:
-            s = segments(c)
-            if s > L.MAX_REDUCE_SEGS:
-                return False  # (a single group beyond the launch's capacity: leave every reduction where it was)
-            if cur and nseg + s > L.MAX_REDUCE_SEGS:
-                chunks.append(cur)
-                cur, nseg = [], 0
-            cur.append(c)
-            nseg += s
-        chunks.append(cur)
-        calls = []
-        for ch in chunks:
-            if len(ch) == 1:  # (nothing to merge it with: its own phase-2 call, on the side list)
-                calls.append(ch[0])
-                continue
-            items = (L.RowsReduceItem * len(ch))()
-            for it, c in zip(items, ch):
-                grp, ws, nbytes, _ = c[1]
-                it.kind = (L.ROWS_REDUCE_HEAD if c[0] is fh else
-                           (L.ROWS_REDUCE_TOWER_HEAD if c[0] is ft else L.ROWS_REDUCE_GATE))
-                it.group = C.addressof(grp._obj)  # (the ops pass C.byref(group); the group itself lives in plan.keep)
-                it.workspace, it.workspace_bytes = ws, nbytes
-            self.keep.append(items)
-            calls.append((lib.mml_rows_reduce_batch, (items, len(ch)),
-                          dict(kernel="slab_reduce", bytes=sum(call_meta(c).get("bytes", 0.0) for c in ch), side=True, rank=1,
-                               ready=max(call_meta(c).get("ready", 0) for c in ch))))
-        self.head_side = [c for c in self.head_side if not is_red(c)]
-        self.bwd_side = calls + [c for c in self.bwd_side if not is_red(c)]
-        return True
-
-    def merge_wgrad16(self):
-        """bf16-storage path (csrc/gemm16.hip: mml_g16_wgrad, at most G16_MAX_GROUP problems per launch, 128 x 128 tiles
-        of 64-row steps, at most 32 slabs): neighbouring weight-gradient launches go together where the tile model says
-        the merged launch takes fewer steps -- KuaiRec-32: towers (4 tiles -> 128 workgroups for 512 slots) + second
-        expert layers (32 tiles) as one launch of 36 tiles."""
-        lib = L.load()
-        fn = lib.mml_g16_wgrad
-        idx = [i for i, c in enumerate(self.bwd_side) if c[0] is fn and c[1][4] == 1]
-        if len(idx) < 2 or any(self.bwd_side[i + 1][0] is not fn or self.bwd_side[i + 1][1][4] != 2 for i in idx):
-            return False
-        steps = max(self.B // 64, 1)
-
-        def cost(g):
-            tiles = sum((d.N // 128) * (d.K // 128) for d in g)
-            sl = max(1, min(512 // max(tiles, 1), steps // 4, 32))
-            return -(-steps // sl) * -(-tiles * sl // 512) + 8
-
-        groups = [[self.bwd_side[i][1][0][k] for k in range(self.bwd_side[i][1][1])] for i in idx]
-        metas = [call_meta(self.bwd_side[i]) for i in idx]
-        out, om = [groups[0]], [dict(metas[0])]
-        for g, m in zip(groups[1:], metas[1:]):
-            cur = out[-1]
-            tg = [d.dW for d in cur + g] + [d.dbias for d in cur + g if d.dbias]
-            if (len(cur) + len(g) <= L.G16_MAX_GROUP and cost(cur + g) < cost(cur) + cost(g) and
-                    len(set(tg)) == len(tg) and not any(d.accumulate for d in cur + g)):
-                out[-1] = cur + g
-                for k in ("flops", "hbm_bytes"):
-                    om[-1][k] = om[-1].get(k, 0.0) + m.get(k, 0.0)
-            else:
-                out.append(g)
-                om.append(dict(m))
-        if len(out) == len(groups):
-            return False
-        calls = []
-        for g, m in zip(out, om):
-            arr = (L.G16WgradDesc * len(g))()
-            for k, d in enumerate(g):
-                C.memmove(C.byref(arr[k]), C.byref(d), C.sizeof(L.G16WgradDesc))
-            nbytes = int(lib.mml_g16_wgrad_workspace_bytes(arr, len(g)))
-            if nbytes < 0:
-                L.check(-1, "mml_g16_wgrad_workspace_bytes")
-            ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.device)
-            self.keep += [arr, ws]
-            m["kernel"] = "g16_nt_kernel(wgrad %d problems)" % len(g)
-            calls.append((fn, (arr, len(g), ws.data_ptr(), ws.numel(), 1), m))
-            calls.append((fn, (arr, len(g), ws.data_ptr(), ws.numel(), 2),
-                          dict(kernel="g16_reduce_kernel", bytes=float(nbytes), side=True, rank=1)))
-        drop = set(idx) | {i + 1 for i in idx}
-        first = idx[0]
-        self.bwd_side = ([c for i, c in enumerate(self.bwd_side) if i < first and i not in drop] + calls +
-                         [c for i, c in enumerate(self.bwd_side) if i > first and i not in drop])
-        return True
 
     def _flat_numel(self, v):
         # act_bwd is a flat kernel: value and gradient must share the padded pitch (they do by construction)
@@ -1052,7 +673,7 @@ class GatherOp(Op):
                      dict(kernel="rows_compact_kernel", bytes=float(mr.marks.numel())))]
         out = self.out.buf
         nwg = int(lib.mml_gather_wgmax_len(F, E, self.nd, plan.B)) if plan.amax_pool is not None else 0
-        if (nwg > 0 and os.environ.get("MMLREC_GATHER_WGMAX", "1") != "0" and ops._ld(out) % 4 == 0 and
+        if (nwg > 0 and plan.knobs.gather_wgmax and ops._ld(out) % 4 == 0 and
                 out.data_ptr() % 16 == 0 and all(t.data.data_ptr() % 16 == 0 for t in self.tables)):
             # the magnitude of the gathered input comes out of the gather itself: one value per workgroup, read by the
             # magnitude launch in front of the first GEMM instead of a pass over the whole output (25 -> 6 us at 65 536)
@@ -1097,7 +718,7 @@ class GatherOp(Op):
             slot = det["slot"]
             plan.keep += [acc]
             flags = 0 if keep_marks else L.SCATTER_DET_CLEAR_MARKS
-            fused = os.environ.get("MMLREC_DET_FUSED", "1") != "0"  # (0: the call measures and finalizes for itself)
+            fused = plan.knobs.det_fused  # (MMLREC_DET_FUSED=0: the call measures and finalizes for itself)
             g = self.out
             # the magnitude of d(dnn_input) from the launch that wrote it: the one writer raised g.gamax (a slot of the
             # pool the step's opening mml_amax_reset zeroes) with the exact maximum over the [B, F * E] region read here
@@ -1161,7 +782,7 @@ class PooledGatherOp(GatherOp):
                     bytes=float(plan.B) * (len(self.singles) * (4 + 8 * E) + 8 * self.nd +
                                            sum(4 * pf[1] + 4 * E * pf[1] + 4 * E for pf in self.pooled)))
         wg, nwg = None, 0
-        if plan.amax_pool is not None and os.environ.get("MMLREC_GATHER_WGMAX", "1") != "0":
+        if plan.amax_pool is not None and plan.knobs.gather_wgmax:
             nwg = int(lib.mml_gather_pool_wgmax_len(C.byref(d), self.nd, plan.B))
             if nwg > 0:
                 wg = plan.zeros(1, nwg)
@@ -1572,7 +1193,7 @@ class LinearGroupOp(Op):
         # (at most seven: the summing launch takes eight terms per target -- parts + the plain gradient buffer a
         # further reader would add to)
         use_part = (parts is not None and h.act == L.ACT_NONE and len(parts) < 7 and
-                    h.buf.stride(0) == h.n and os.environ.get("MMLREC_GRAD_PARTS", "1") != "0")
+                    h.buf.stride(0) == h.n and plan.knobs.grad_parts)
         for key, v, nc in (("h", h, 1), ("g", g, 0)):
             if key == "h" and use_part:
                 part = plan.empty(plan.B, h.n)
@@ -1599,13 +1220,13 @@ class LinearGroupOp(Op):
                   ((pl, kx) if pl is not None else ()) for q, (pl, kx) in zip(qs, gp)]))
 
     @staticmethod
-    def _grad_cols(x, qs):
+    def _grad_cols(plan, x, qs):
         """Columns of the input gradient somebody reads (Val.grad_cols), or 0 for all of them: a narrower launch over the
         same buffers."""
         return x.grad_cols if (0 < x.grad_cols < x.n and x.grad_cols % 16 == 0 and x.act == L.ACT_NONE and
                                all(isinstance(c, LinearGroupOp) for c in x.consumers) and
                                not any(q.get("w_kn", 0) for q in qs) and
-                               os.environ.get("MMLREC_GRAD_COLS", "1") != "0") else 0
+                               plan.knobs.grad_cols) else 0
 
     @staticmethod
     def _splits(plan, x, qs):
@@ -1614,11 +1235,11 @@ class LinearGroupOp(Op):
         dealt to up to four problems of the same launch (partial sums into scratch, one add afterwards): 4x the
         tiles, a quarter of the steps.  Only without an activation derivative in the epilogue (input layers)."""
         return (plan.B <= 8192 and 2 <= len(qs) <= L.MAX_SRC and x.act == L.ACT_NONE and
-                sum(q["out"].n for q in qs) >= 512 and os.environ.get("MMLREC_SPLIT_DGRAD", "1") != "0")
+                sum(q["out"].n for q in qs) >= 512 and plan.knobs.split_dgrad)
 
     def _dgrad_split(self, plan, x, qs, waves):
         """The split problem (_splits): up to four problems of the first launch; returns the call that sums the parts."""
-        gc = self._grad_cols(x, qs)
+        gc = self._grad_cols(plan, x, qs)
         cut = (lambda t: t[:, :gc]) if gc else (lambda t: t)
         nparts = min(4, len(qs))
         parts = [[] for _ in range(nparts)]
@@ -1646,7 +1267,7 @@ class LinearGroupOp(Op):
         """The plain problem: the layers that read x in chunks of MAX_SRC sources, chunk k in launch k."""
         chunks = [qs[i:i + L.MAX_SRC] for i in range(0, len(qs), L.MAX_SRC)]
         fuse = len(chunks) == 1 and len(x.consumers) == 1 and x.act != L.ACT_NONE
-        gc = self._grad_cols(x, qs)
+        gc = self._grad_cols(plan, x, qs)
         cut = (lambda t: t[:, :gc]) if gc else (lambda t: t)
         for ci, ch in enumerate(chunks):
             acc = _claim(x)
@@ -1810,7 +1431,7 @@ def _defer_reduce():
     e = os.environ.get("MMLREC_DEFER_REDUCE")
     if e is not None:
         return e == "1"
-    # Round 5, ONE stream: deferred, and Plan.merge_row_reduces turns the deferred reductions of a step into ONE launch
+    # Round 5, ONE stream: deferred, and passes.merge_row_reduces turns the deferred reductions of a step into ONE launch
     # (mml_rows_reduce_batch): MMoE one launch fewer per step, a PLE of two levels two.
     return bool(_DEFER)
 

@@ -405,12 +405,11 @@ class BaseModel(nn.Module):
             # move it -- every forward would draw the SAME dropout mask.  The forward bumps it first; the
             # backward of that forward regenerates the mask from the same value.
             own = plan.shared_step_dev
-            plan.fwd.insert(0, (L.load().mml_counter_update, (own.data_ptr(), 1, 0),
-                                dict(kernel="mml_counter_update", bytes=4.0)))
-            # (a 4-byte copy: the kernel moves the word's bits unchanged)
-            plan.fwd.insert(1, (L.load().mml_copy2d, (own.data_ptr(), 1, plan.step_dev.data_ptr(), 1, 1, 1, 0),
-                                dict(kernel="copy2d_kernel", bytes=8.0)))
-            plan.n_pre += 2
+            plan.prepend([(L.load().mml_counter_update, (own.data_ptr(), 1, 0),
+                           dict(kernel="mml_counter_update", bytes=4.0)),
+                          # (a 4-byte copy: the kernel moves the word's bits unchanged)
+                          (L.load().mml_copy2d, (own.data_ptr(), 1, plan.step_dev.data_ptr(), 1, 1, 1, 0),
+                           dict(kernel="copy2d_kernel", bytes=8.0))])
         return plan
 
     def _maybe_deterministic(self, gop, store, tables, training, E_dim):

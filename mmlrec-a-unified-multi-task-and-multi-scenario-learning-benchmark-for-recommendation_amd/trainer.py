@@ -24,6 +24,7 @@ import typing
 import torch
 
 from . import engine as E
+from . import passes
 from .ops import concurrent_stream as ops_concurrent_stream
 from . import profiling
 
@@ -588,9 +589,9 @@ class TrainStep:
         # launches of a large batch do not all fill the chip either (AE-30's tower layers: 2 tiles x 64 slabs = 128
         # workgroups for 512 slots), and one reduction over 17 slabs replaces three over 25 / 64 / 64.
         self.wgrad_merged = (int(B) <= 8192 or self.opt.table_update != "dense_exact" or not overlap) and \
-            knobs.merge_wgrad and p.merge_wgrad()
+            knobs.merge_wgrad and passes.merge_wgrad(p)
         if not overlap and knobs.merge_wgrad:
-            p.merge_wgrad16()  # (the bf16-storage path's launches: csrc/gemm16.hip)
+            passes.merge_wgrad16(p)  # (the bf16-storage path's launches: csrc/gemm16.hip)
         opt = self.opt_split = self.opt.calls_split(p, split_dense=split)
         if pcg and self.opt.table_update == "sparse_rows":
             opt["pre"] = opt["pre"] + self.opt.index_pre_calls(p)
@@ -676,7 +677,7 @@ class TrainStep:
                   (par is None or par.mode in ("row_sharded", "replicated")) and
                   knobs.grad_marks)
         # one stream (and no split table update, whose early pass forks anyway): the reductions of the head / gate kernels'
-        # partial sums are deferred behind the backward chain and merged into ONE launch (Plan.merge_row_reduces)
+        # partial sums are deferred behind the backward chain and merged into ONE launch (passes.merge_row_reduces)
         one_list = not overlap and not split and knobs.merge_reduces
         with E.deferred_reductions(one_list):
             self.plan = model._record(B, True, False, self.store, sparse_rows=None if (lazy or split) else rows,
@@ -686,8 +687,8 @@ class TrainStep:
         if one_list:
             # the top of the network -- last tower layer, heads + BCE, the towers' input gradient -- as one launch where
             # the recorded lists hold that pattern (csrc/tower_head.hip; before the reductions are merged: it brings its own)
-            self.tower_head_fused = self.plan.fuse_tower_head()
-            self.plan.merge_row_reduces()
+            self.tower_head_fused = passes.fuse_tower_head(self.plan)
+            passes.merge_row_reduces(self.plan)
         self.grad_marks = getattr(self.plan.ops[0], "grad_marks", None) is not None
         return split
 

@@ -351,7 +351,7 @@ def _check_bench_steps(W, table_update, streams, scatter_mode):
     assert runner.use_graph and runner.overlap == (streams == 2) and (runner.whole is not None) == (streams == 1)
     if streams == 1:
         # round 6: the top of the network (last tower layer + heads + BCE + the towers' input gradient) is ONE launch of
-        # the one-stream step (csrc/tower_head.hip; Plan.fuse_tower_head) -- and the three launches it replaces are gone
+        # the one-stream step (csrc/tower_head.hip; passes.fuse_tower_head) -- and the three launches it replaces are gone
         from mmlrec_amd import _lib
         lib_ = _lib.load()
         calls = [c for part in runner.whole.parts if part[0] == "c" for c in part[1]]

@@ -1,4 +1,4 @@
-"""Call-list passes of engine.Plan that need no GPU: Plan._merge_copies (runs of neighbouring strided copies as one
+"""Call-list passes (passes.py) that need no GPU: merge_copies (runs of neighbouring strided copies as one
 launch).  The pass only looks at the functions' identity and the descriptors, so stand-in functions serve; the merged
 lists are EXECUTED here on numpy buffers, with every launch's items applied in a scrambled order (one launch has no
 order), and must give what the original list gives call by call."""
@@ -12,10 +12,10 @@ import pytest
 @pytest.fixture()
 def env():
     import mmlrec_amd  # noqa: F401
-    from mmlrec_amd import _lib as L, engine as E
+    from mmlrec_amd import _lib as L, passes as P
     lib = types.SimpleNamespace(mml_copy2d=lambda *a: 0, mml_copy2d_batch=lambda *a: 0, other=lambda *a: 0)
     fake = types.SimpleNamespace(keep=[])
-    return L, E, lib, fake
+    return L, P, lib, fake
 
 
 def addr(a):
@@ -46,7 +46,7 @@ def run(lib, calls, scramble=None):
 
 
 def test_independent_neighbours_become_one_launch(env):
-    L, E, lib, fake = env
+    L, P, lib, fake = env
     a, b, c, d = (np.arange(12, dtype=np.float32).reshape(3, 4) + 100 * i for i in range(4))
     out1, out2 = np.zeros((3, 8), np.float32), np.zeros((3, 4), np.float32)
     calls = [(lib.mml_copy2d, (addr(a), 4, addr(out1), 8, 3, 4, 0)),                 # concat: a | b into out1
@@ -54,7 +54,7 @@ def test_independent_neighbours_become_one_launch(env):
              (lib.mml_copy2d, (addr(c), 4, addr(out2), 4, 3, 4, 0), dict(kernel="copy2d_kernel")),
              (lib.other, (1, 2)),
              (lib.mml_copy2d, (addr(d), 4, addr(out2), 4, 3, 4, 1))]
-    merged = E.Plan._merge_copies(fake, calls, lib=lib)
+    merged = P.merge_copies(calls, fake.keep, lib=lib)
     assert [c[0] for c in merged] == [lib.mml_copy2d_batch, lib.other, lib.mml_copy2d]
     assert merged[0][1][1] == 3 and merged[0][2]["kernel"] == "copy2d_batch_kernel"
     run(lib, merged, scramble=np.random.default_rng(0))
@@ -62,7 +62,7 @@ def test_independent_neighbours_become_one_launch(env):
 
 
 def test_dependent_copies_keep_their_order(env):
-    L, E, lib, fake = env
+    L, P, lib, fake = env
     rng = np.random.default_rng(1)
     x, y, z = (rng.standard_normal((4, 6)).astype(np.float32) for _ in range(3))
     t = np.zeros((4, 6), np.float32)
@@ -75,19 +75,19 @@ def test_dependent_copies_keep_their_order(env):
                 (lib.mml_copy2d, (addr(y), 6, addr(z_), 6, 4, 6, 0))]       # z = y         (overwrites what the fourth read)
     t0, g0, z0 = t.copy(), g.copy(), z.copy()
     run(lib, calls_on(t0, g0, z0))
-    merged = E.Plan._merge_copies(fake, calls_on(t, g, z), lib=lib)
+    merged = P.merge_copies(calls_on(t, g, z), fake.keep, lib=lib)
     # 1 | 2 (reads what 1 wrote) | 3 (adds to what 2 wrote) + 4 (independent of 3; 2 has run by then) | 5 (overwrites what
     # 4 reads): four launches, the third a batch of two
     assert [c[0] is lib.mml_copy2d_batch for c in merged] == [False, False, True, False] and merged[2][1][1] == 2
     for trial in range(5):
         t1, g1, z1 = np.zeros_like(t), np.zeros_like(g), z.copy()
-        m = E.Plan._merge_copies(fake, calls_on(t1, g1, z1), lib=lib)
+        m = P.merge_copies(calls_on(t1, g1, z1), fake.keep, lib=lib)
         run(lib, m, scramble=np.random.default_rng(trial))
         assert np.array_equal(t1, t0) and np.array_equal(g1, g0) and np.array_equal(z1, z0)
 
 
 def test_existing_batches_join_and_strided_ranges_count(env):
-    L, E, lib, fake = env
+    L, P, lib, fake = env
     buf = np.zeros((5, 16), np.float32)
     src = np.arange(20, dtype=np.float32).reshape(5, 4)
     arr = (L.Copy2dDesc * 2)()
@@ -99,7 +99,7 @@ def test_existing_batches_join_and_strided_ranges_count(env):
              # the column block 2..5 of the same rows: its strided range interleaves with the blocks above -> the
              # conservative interval test refuses it (a new launch), which is always safe
              (lib.mml_copy2d, (addr(src), 4, addr(buf) + 4 * 2, 16, 5, 4, 1))]
-    merged = E.Plan._merge_copies(fake, calls, lib=lib)
+    merged = P.merge_copies(calls, fake.keep, lib=lib)
     assert [c[0] for c in merged] == [lib.mml_copy2d_batch, lib.mml_copy2d] and merged[0][1][1] == 3
     run(lib, merged, scramble=np.random.default_rng(3))
     want = np.zeros((5, 16), np.float32)
@@ -110,18 +110,18 @@ def test_existing_batches_join_and_strided_ranges_count(env):
     # more than 32 items never share a launch
     many = [(lib.mml_copy2d, (addr(src), 4, addr(np.zeros((5, 4), np.float32)), 4, 5, 4, 0)) for _ in range(40)]
     keep = [c[1][2] for c in many]  # (the destination buffers above are temporaries: only the split is checked)
-    m = E.Plan._merge_copies(fake, many, lib=lib)
+    m = P.merge_copies(many, fake.keep, lib=lib)
     assert sum(c[1][1] if c[0] is lib.mml_copy2d_batch else 1 for c in m) == 40 and len(m) >= 2 and keep
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# Plan.merge_row_reduces: the deferred head / gate reductions as few launches as the C side's segment capacity allows
+# passes.merge_row_reduces: the deferred head / gate reductions as few launches as the C side's segment capacity allows
 # (a PLE with 7 tasks and 4 levels needs 15 + 8 + 8 + 8 + 7 = 46 segments; csrc/reduce.hpp takes 40 per launch)
 # ---------------------------------------------------------------------------------------------------------------
 def _reduce_plan(env, n_heads, gate_groups):
     """A stand-in plan whose side lists hold the phase-2 calls of one head group (n_heads heads + the loss) and of gate
     groups with the given numbers of active gates (one inactive gate each on top)."""
-    L, E, _, _ = env
+    L, P, _, _ = env
     lib = types.SimpleNamespace(mml_head_bce_fwd_bwd_phase=lambda *a: 0, mml_gate_mix_bwd_phase=lambda *a: 0,
                                 mml_rows_reduce_batch=lambda *a: 0, other=lambda *a: 0)
     hg = L.HeadGroup()
@@ -162,9 +162,9 @@ def _segments_of(L, lib, call):
 
 
 def test_merge_row_reduces_mmoe_is_one_launch(env):
-    L, E, _, _ = env
+    L, P, _, _ = env
     lib, plan = _reduce_plan(env, 2, [2])
-    assert E.Plan.merge_row_reduces(plan, lib=lib)
+    assert P.merge_row_reduces(plan, lib=lib)
     assert plan.head_side == []
     assert [c[0] for c in plan.bwd_side] == [lib.mml_rows_reduce_batch, lib.other]
     assert _segments_of(L, lib, plan.bwd_side[0]) == (2 * 2 + 1 + 2, 2)
@@ -172,9 +172,9 @@ def test_merge_row_reduces_mmoe_is_one_launch(env):
 
 
 def test_merge_row_reduces_deep_ple_is_chunked(env):
-    L, E, _, _ = env
+    L, P, _, _ = env
     lib, plan = _reduce_plan(env, 7, [8, 8, 8, 7])           # 15 + 8 + 8 + 8 + 7 = 46 segments
-    assert E.Plan.merge_row_reduces(plan, lib=lib)
+    assert P.merge_row_reduces(plan, lib=lib)
     reds = [c for c in plan.bwd_side if c[0] is not lib.other]
     assert plan.head_side == [] and len(reds) == 2 and plan.bwd_side[:2] == reds
     segs = [_segments_of(L, lib, c) for c in reds]
@@ -186,17 +186,17 @@ def test_merge_row_reduces_deep_ple_is_chunked(env):
 
 
 def test_merge_row_reduces_single_group_is_left_alone(env):
-    L, E, _, _ = env
+    L, P, _, _ = env
     lib, plan = _reduce_plan(env, 2, [])
     before = list(plan.head_side)
-    assert not E.Plan.merge_row_reduces(plan, lib=lib)
+    assert not P.merge_row_reduces(plan, lib=lib)
     assert plan.head_side == before and plan.bwd_side == []
 
 
 def test_merge_copies_reports_where_every_call_went(env):
-    """`where` maps old indices to merged ones: Plan.finish turns the side calls' `ready` tags (counted on the unmerged
-    backward chain) into the merged list's index space with it."""
-    L, E, lib, fake = env
+    """`where` maps old indices to merged ones: passes.merge_plan_copies turns the side calls' `ready` tags (counted on the
+    unmerged backward chain) into the merged list's index space with it."""
+    L, P, lib, fake = env
     bufs = [np.zeros((3, 4), np.float32) for _ in range(8)]
     calls = [(lib.other, (0,)),
              (lib.mml_copy2d, (addr(bufs[0]), 4, addr(bufs[1]), 4, 3, 4, 0)),
@@ -206,7 +206,7 @@ def test_merge_copies_reports_where_every_call_went(env):
              (lib.mml_copy2d, (addr(bufs[5]), 4, addr(bufs[6]), 4, 3, 4, 0)),   # reads what the previous wrote: its own launch
              (lib.other, (2,))]
     where = []
-    merged = E.Plan._merge_copies(fake, calls, lib=lib, where=where)
+    merged = P.merge_copies(calls, fake.keep, lib=lib, where=where)
     assert len(merged) == 6 and where == [0, 1, 1, 2, 3, 4, 5]
     # ready = k (first k old entries issued) -> where[k - 1] + 1 merged entries
     assert [where[k - 1] + 1 for k in (1, 2, 3, 4, 7)] == [1, 2, 2, 3, 6]
