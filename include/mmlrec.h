@@ -1150,6 +1150,14 @@ typedef struct {
   const uint32_t* acc_amax;
   int32_t acc_shift;
   int32_t acc_pad_;
+  /* Warm rows (Adam / RMSprop / Adagrad tables whose moments start at zero): warm_rows != NULL is one byte per table row,
+   * 0 = "state1 / state2 of this row are still all zero".  Such a row with an unmarked (zero) gradient is left exactly
+   * where it is by the update (m' = v' = 0, p' = p - step * 0), so the kernel neither reads nor writes it; a marked row
+   * gets its byte set (plain byte store, by the lane that clears the mark), warm unmarked rows are updated as ever.  The
+   * caller owns the map: all zero when the moments are created as zeros, and set to 1 for every row a writer of
+   * state1 / state2 other than this launch may have touched.  Same needs as grad_marks and honoured only together with
+   * it (the streaming launch); the tensor must carry no regulariser (l1 = l2 = 0).  NULL: every row is updated. */
+  uint8_t* warm_rows;
 } mml_opt_tensor;
 typedef struct {
   int32_t kind;      /* MML_OPT_* */

@@ -151,7 +151,7 @@ class TowerHeadGroup(C.Structure):
 class OptTensor(C.Structure):
     _fields_ = [("param", fp), ("grad", fp), ("state1", fp), ("state2", fp), ("n", i64), ("l1", C.c_float),
                 ("l2", C.c_float), ("skip_rows", fp), ("row_elems", i32), ("zero_grads", i32), ("grad_marks", fp),
-                ("acc64", fp), ("acc_amax", fp), ("acc_shift", i32), ("acc_pad_", i32)]
+                ("acc64", fp), ("acc_amax", fp), ("acc_shift", i32), ("acc_pad_", i32), ("warm_rows", fp)]
 
 
 class Copy2dDesc(C.Structure):

@@ -7,6 +7,12 @@
 
 #include <stdlib.h>
 
+// chunks whose mark / warm bytes a thread of the mostly-cold table stream reads before it looks at any of them (lab builds:
+// -DMML_OPT_COLD_CB=2 / 4 / 16, tools/lab/opt_cold_rows.py; DESIGN_HISTORY.md has the numbers)
+#ifndef MML_OPT_COLD_CB
+#define MML_OPT_COLD_CB 8
+#endif
+
 namespace mml {
 
 struct OptLaunch {
@@ -87,6 +93,9 @@ __device__ __forceinline__ float reg_grad(float g, float p, float l1, float l2) 
 //   2 split update, untouched rows, U chunks in flight per thread            3 marked gradients, U chunks in flight
 //   4 marked gradients whose rows' 64-bit totals of the deterministic scatter are still in mml_opt_tensor.acc64 (the
 //     scatter's second launch folded in): as 3, plus 32 bytes of totals read, converted and zeroed per marked chunk
+// Forms 3 and 4 with a warm map (mml_opt_tensor.warm_rows, decided at run time inside the same instantiations): a row that
+// is neither marked nor warm has m = v = 0 and g = 0, the update leaves p, m and v as they are bit for bit, and the kernel
+// neither reads nor writes it -- it walks the two byte maps and touches the rows they name.
 enum { OPT_PLAIN = 0, OPT_UNROLL2 = 1, OPT_SKIP_U = 2, OPT_MARK_U = 3, OPT_MARK_ACC_U = 4 };
 template <bool STREAM, int PATH, int U>
 __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
@@ -221,6 +230,72 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
         }
       }
     }
+    // warm map (forms 3 and 4, and the remainder loop of every form): 0 = the row's moments are still zero.  Read like
+    // the mark: by every lane of the row in one wave-instruction, before the first chunk's lane sets it.
+    uint8_t* const wr = gm ? T.warm_rows : nullptr;
+    if ((PATH == OPT_MARK_U || PATH == OPT_MARK_ACC_U) && wr && !skip) {  // (workgroup-uniform)
+      // Mostly-cold stream: the bytes of CB chunks' rows (2 CB one-byte loads in flight, no load depends on another), then
+      // only the live chunks, two at a time as in the forms below; a wave none of whose lanes has a live chunk moves on
+      // without a further memory access.  The block covers its own remainder (chunks past the end are not live).
+      constexpr int CB = MML_OPT_COLD_CB;
+      for (; i < n4; i += CB * stride) {
+        uint32_t lm = 0, wm = 0;  // bit k: chunk i + k * stride is marked / warm
+#pragma unroll
+        for (int k = 0; k < CB; ++k) {
+          const int64_t j = i + k * stride;
+          const bool in = j < n4;
+          const int64_t row = row_of(in ? j : i);  // (a valid address either way: no branch around the loads)
+          const uint8_t mk = gm[row], wk = wr[row];
+          lm |= (uint32_t)(in && mk != 0) << k;
+          wm |= (uint32_t)(in && wk != 0) << k;
+        }
+        const uint32_t act = lm | wm;
+        if (__builtin_amdgcn_ballot_w64(act != 0) == 0) continue;
+#pragma unroll 1
+        for (int kk = 0; kk < CB; kk += 2) {  // (one copy of the pair's code: unrolled, the kernel loses a wave per SIMD)
+          if (__builtin_amdgcn_ballot_w64(((act >> kk) & 3u) != 0) == 0) continue;
+          f4 p[2], a[2], b[2], g[2];
+          l2 t0[2], t1[2];
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const int64_t j = i + (kk + k) * stride;
+            const bool on = (act >> (kk + k)) & 1u, lv = (lm >> (kk + k)) & 1u;
+            p[k] = a[k] = b[k] = g[k] = zero;
+            t0[k] = t1[k] = lzero;
+            if (on) {
+              p[k] = ld(P + j);
+              if (S1) a[k] = ld(S1 + j);
+              if (S2) b[k] = ld(S2 + j);
+            }
+            if (lv) {
+              if (!zg) g[k] = ld(G + j);
+              if (PATH == OPT_MARK_ACC_U && A64) {
+                t0[k] = A64[2 * j];
+                t1[k] = A64[2 * j + 1];
+              }
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const int64_t j = i + (kk + k) * stride;
+            const bool on = (act >> (kk + k)) & 1u, lv = (lm >> (kk + k)) & 1u;
+            if (!on) continue;
+            f4 gs = g[k];
+            if (PATH == OPT_MARK_ACC_U && A64 && lv) add_totals(gs, t0[k], t1[k], j);
+            one(p[k], gs, a[k], b[k]);
+            st(P + j, p[k]);
+            if (S1) st(S1 + j, a[k]);
+            if (S2) st(S2 + j, b[k]);
+            if (h.zero_grad && (g[k].x != 0.f || g[k].y != 0.f || g[k].z != 0.f || g[k].w != 0.f)) G[j] = zero;
+            const int64_t row = row_of(j);
+            if (lv && (j << 2) == row * re) {
+              gm[row] = 0;
+              if (!((wm >> (kk + k)) & 1u)) wr[row] = 1;
+            }
+          }
+        }
+      }
+    }
     if (PATH == OPT_MARK_U && gm && !skip) {
       // marked single-launch update under a capped grid (mml_opt_hyper.max_blocks: it runs beside the weight-gradient
       // GEMMs and leaves them their wave slots): the memory-level parallelism comes from the thread -- U chunks, 3U
@@ -292,11 +367,15 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
     }
     for (; i < n4; i += stride) {
       if (skip && skipped(i)) continue;
-      bool live = true;
+      bool live = true, warm = true;
       int64_t row = 0;
       if (gm) {
         row = row_of(i);
         live = gm[row] != 0;
+        if (wr) {
+          warm = wr[row] != 0;
+          if (!live && !warm) continue;  // (zero moments, zero gradient: the update changes nothing)
+        }
       }
       f4 p = ld(P + i);
       const f4 g = (zg || !live) ? zero : ld(G + i);
@@ -314,7 +393,10 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
       if (S2) st(S2 + i, b);
       // re-zero only what the scatter touched (~1 % of the rows): saves the 4 B/element store of a blind memset
       if (h.zero_grad && (g.x != 0.f || g.y != 0.f || g.z != 0.f || g.w != 0.f)) G[i] = zero;
-      if (gm && live && (i << 2) == row * re) gm[row] = 0;
+      if (gm && live && (i << 2) == row * re) {
+        gm[row] = 0;
+        if (!warm) wr[row] = 1;
+      }
     }
   }
   const int64_t tail0 = vec ? (n4 << 2) : 0;
@@ -905,6 +987,11 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
                     "mml_opt_step_dense: tensor %d: grad_marks needs 16-byte aligned [rows, row_elems] tensors with "
                     "row_elems / 4 a power of two <= 64 and no skip_rows", i);
       }
+      if (t.warm_rows) {
+        MML_REQUIRE(t.grad_marks && t.l1 == 0.f && t.l2 == 0.f,
+                    "mml_opt_step_dense: tensor %d: warm_rows needs grad_marks and no regulariser (a regulariser moves a "
+                    "row whose moments and gradient are zero)", i);
+      }
       L.chunk0[L.n] = chunks;
       L.t[L.n++] = t;
       total += t.n;
@@ -941,6 +1028,18 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
       if (bx > 256 * 8) bx = 256 * 8;
       if (hyper->max_blocks > 0 && bx * L.n > hyper->max_blocks) bx = cdiv(hyper->max_blocks, L.n);
       dim3 grid((unsigned)bx, (unsigned)L.n);
+      // Workgroups per tensor at most.  With a warm map on every tensor most of the stream is passed over and a workgroup's
+      // fixed cost (tensor search, bias corrections, magnitude words) is what is left of a short one: MMLREC_OPT_COLD_WGS
+      // (lab knob) caps them lower.
+      bool all_warm = true;
+      for (int k = 0; k < L.n; ++k) all_warm = all_warm && L.t[k].warm_rows;
+      static int cold_wgs = -1;
+      if (cold_wgs < 0) {
+        const char* e = getenv("MMLREC_OPT_COLD_WGS");
+        cold_wgs = e ? atoi(e) : 256 * 8;
+        if (cold_wgs < 1 || cold_wgs > 256 * 8) cold_wgs = 256 * 8;
+      }
+      const int64_t wg_cap = all_warm ? cold_wgs : 256 * 8;
       if (many) {
         // every tensor gets what a launch of its own would give it (one workgroup per 256 chunks, at most 2 048): the huge
         // tables stream exactly as in their four-tensor launch, the small ones add a few hundred workgroups (the caller
@@ -948,7 +1047,7 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
         int64_t want = 0;
         for (int k = 0; k < L.n; ++k) {
           const int64_t need = cdiv(cdiv(L.t[k].n, 4), 256);
-          want += need > 256 * 8 ? 256 * 8 : (need < 1 ? 1 : need);
+          want += need > wg_cap ? wg_cap : (need < 1 ? 1 : need);
         }
         const bool capped = hyper->max_blocks > 0 && want > hyper->max_blocks;
         int64_t tb = capped ? hyper->max_blocks : want;
@@ -957,7 +1056,7 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
         for (int k = 0; k < L.n; ++k) {
           L.blk0[k] = (int32_t)at;
           const int64_t need = cdiv(cdiv(L.t[k].n, 4), 256);
-          int64_t nb = capped ? tb * L.t[k].n / total : (need > 256 * 8 ? 256 * 8 : need);
+          int64_t nb = capped ? tb * L.t[k].n / total : (need > wg_cap ? wg_cap : need);
           if (nb > need) nb = need;
           if (nb < 1) nb = 1;
           at += nb;

@@ -972,7 +972,9 @@ def make_opt_tensors(entries):
     """entries: (param, grad, state1 or None, state2 or None[, (l1, l2)[, skip bitmap[, gradient marks[, totals]]]]) with
     equal element counts, contiguous.  A skip bitmap (int32 words, one bit per table row) turns the entry into the untouched-rows half of the
     split dense table update (include/mmlrec.h: mml_opt_tensor.skip_rows).  totals = (acc64 tensor, magnitude slot,
-    scatter_det_shift(B)): the deferred row totals of the deterministic scatter (mml_opt_tensor.acc64)."""
+    scatter_det_shift(B)): the deferred row totals of the deterministic scatter (mml_opt_tensor.acc64).  A ninth
+    element, the warm map (uint8, one byte per table row, kept with the moments: mml_opt_tensor.warm_rows), lets a marked
+    launch pass over the rows whose moments are still zero; it goes with gradient marks only."""
     arr = (L.OptTensor * len(entries))()
     for d, ent in zip(arr, entries):
         p, g, s1, s2 = ent[:4]
@@ -984,6 +986,8 @@ def make_opt_tensors(entries):
             d.grad_marks, d.row_elems = ent[6].data_ptr(), p.shape[1]
         if len(ent) > 7 and ent[7] is not None:
             d.acc64, d.acc_amax, d.acc_shift = ent[7][0].data_ptr(), ent[7][1].data_ptr(), int(ent[7][2])
+        if len(ent) > 8 and ent[8] is not None:
+            d.warm_rows = ent[8].data_ptr()
     return arr
 
 

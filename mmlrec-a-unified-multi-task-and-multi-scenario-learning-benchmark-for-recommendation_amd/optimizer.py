@@ -51,6 +51,9 @@ class OptKnobs:
     one_launch: bool = False
     variant: int = 0           # MMLREC_OPT_VARIANT: bit 1 = two chunks per iteration in the unmarked, unsplit stream
     scatter_old: bool = False  # MMLREC_SCATTER_OLD: the appending atomic scatter, whose touched list is reset here
+    # MMLREC_OPT_COLD_ROWS=0: the marked streaming launch gets no warm map (mml_opt_tensor.warm_rows) and updates every
+    # row, as it did before the map existed (A/B switch; the results are the same bits either way)
+    cold_rows: bool = True
 
     @classmethod
     def from_env(cls, env=None):
@@ -63,7 +66,8 @@ class OptKnobs:
                    opt_u=int(u) if u is not None else None,
                    one_launch=env.get("MMLREC_OPT_ONE_LAUNCH", "0") == "1",
                    variant=int(env.get("MMLREC_OPT_VARIANT", "0")),
-                   scatter_old=bool(env.get("MMLREC_SCATTER_OLD")))
+                   scatter_old=bool(env.get("MMLREC_SCATTER_OLD")),
+                   cold_rows=env.get("MMLREC_OPT_COLD_ROWS", "1") != "0")
 
 
 TABLE_UPDATES = ("dense_exact", "sparse_rows", "lazy_exact")
@@ -167,6 +171,20 @@ def dense_table_launches(kind, numels, rows, marks, split_dense, cap, det_deferr
             nbytes += sum(rows[i] - 4.0 * numels[i] for i in grp)
         out.append(DenseLaunch(tuple(grp), marked, form, nbytes, opt_dense_symbol(numel, len(grp), form, knobs.opt_u)))
     return out
+
+
+WARM_KINDS = ("adam", "rmsprop", "adagrad")
+
+
+def launch_trusts_warm_map(kind, marked, table_reg, knobs, sharded=False):
+    """May a launch of dense_table_launches pass over the rows whose byte in the table's warm map (Optimizer.warm) is 0?
+    Only the marked streaming launch reads the map (mml_opt_tensor.warm_rows goes with grad_marks); a row with zero
+    moments and a zero gradient stays where it is under Adam / RMSprop / Adagrad and no regulariser (SGD has no moments
+    to be zero, and a regulariser moves every row every step); knobs.cold_rows switches the map off, and the sharded
+    updates of parallel.py (sharded: the gather is not an engine.GatherOp) do without it.  A launch that may
+    not trust the map takes None and, since it writes moments the map does not know of, marks every row of its tables
+    warm (Optimizer.all_rows_warm) -- as does every other writer of a table's moments."""
+    return bool(marked and kind in WARM_KINDS and not table_reg and knobs.cold_rows and not sharded)
 
 
 class TableRows:
@@ -289,18 +307,33 @@ class ParamStore:
 
 
 class _OptState(dict):
-    """name -> (state1, state2), zero-initialised on first use (a row-sharded run never touches the full tables)."""
+    """name -> (state1, state2), zero-initialised on first use (a row-sharded run never touches the full tables).
+
+    warm: table name -> uint8 [rows], 0 = the row's moments are still the zeros they were created as.  A table's map is
+    born all-zero with its zero moments, here and nowhere else; moments that come from outside (state[name] = ...: a
+    loaded checkpoint, a test that plants a state) have no map, and none is made for them later."""
 
     def __init__(self, store, kind):
         super().__init__()
         self.store, self.kind = store, kind
+        self.warm = {}
 
     def __missing__(self, name):
         pv = self.store.pvals[name]
         s1 = torch.zeros_like(pv.data) if self.kind != "sgd" else None
         s2 = torch.zeros_like(pv.data) if self.kind == "adam" else None
-        self[name] = (s1, s2)
-        return self[name]
+        dict.__setitem__(self, name, (s1, s2))
+        if pv.is_table and s1 is not None:
+            self.warm[name] = torch.zeros(pv.data.shape[0], dtype=torch.uint8, device=pv.data.device)
+        return (s1, s2)
+
+    def __setitem__(self, name, value):
+        self.warm.pop(name, None)
+        dict.__setitem__(self, name, value)
+
+    def __delitem__(self, name):
+        self.warm.pop(name, None)
+        dict.__delitem__(self, name)
 
 
 class Optimizer:
@@ -333,7 +366,22 @@ class Optimizer:
         dev = store.device
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
         self.state = _OptState(store, kind)  # moments are allocated when a tensor is first updated
+        self.warm = self.state.warm          # table name -> byte per row: may the row's moments be non-zero?
         self.steps_done = 0
+
+    def warm_map(self, name):
+        """The warm map of table `name` for a launch that honours it (launch_trusts_warm_map), or None when the table's
+        moments did not start as zeros of this optimizer's making."""
+        self.state[name]
+        return self.warm.get(name)
+
+    def all_rows_warm(self, names):
+        """Every writer of a table's moments that is not a warm-aware launch calls this when its call list is built (the
+        map only ever goes from 0 to 1, so doing it early is safe): from here on no row of these tables is passed over."""
+        for n in names:
+            self.state[n]
+            if n in self.warm:
+                self.warm[n].fill_(1)
 
     def calls(self, plan):
         """Optimizer call list for one step (appended after a plan's backward)."""
@@ -421,9 +469,14 @@ class Optimizer:
         acc_of = {id(t): a for t, a in zip(gop.tables, gop.deterministic["acc64"])} if dd else {}
         calls = []
         for ln in launches:
+            # rows whose moments are still zero and whose gradient is unmarked are not even read (mml_opt_tensor.warm_rows)
+            trust = launch_trusts_warm_map(self.kind, ln.marked, treg, knobs, sharded=not isinstance(gop, E.GatherOp))
+            if not trust:
+                self.all_rows_warm([names[i] for i in ln.tables])
             arr = ops.make_opt_tensors([(tabs[i].data, tabs[i].grad) + self.state[names[i]] +
                                         (treg, seen_of.get(names[i]), marks_of[id(tabs[i])] if ln.marked else None,
-                                         (acc_of[id(tabs[i])], dd["slot"], dd["shift"]) if dd else None)
+                                         (acc_of[id(tabs[i])], dd["slot"], dd["shift"]) if dd else None,
+                                         self.warm_map(names[i]) if trust else None)
                                         for i in ln.tables])
             plan.keep.append(arr)
             m = dict(kernel=ln.kernel, bytes=ln.bytes)
@@ -438,6 +491,7 @@ class Optimizer:
         for the appending scatter only, the list's reset."""
         rows = self.store.rows
         a = self._row_arrays(plan, names, grads=True, last=self.table_update == "lazy_exact")
+        self.all_rows_warm(names)  # (the row kernels write moments and know no warm map)
         calls = [(L.load().mml_opt_step_rows, (a["param"], a["grad"], a["s1"], a["s2"], a["seen"], a["rowbase"], a["F"],
                                                a["E"], rows.touched.data_ptr(), rows.count.data_ptr(),
                                                rows.touched.numel(), a["last"], C.byref(hyper)),
@@ -519,6 +573,7 @@ class Optimizer:
         if self.last is None:
             self.last = {n: torch.zeros(st.pvals[n].data.shape[0], dtype=torch.int32, device=st.device) for n in names}
         a = self._row_arrays(plan, names, last=True)
+        self.all_rows_warm(names)  # (the catch-up writes moments)
         hyper = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev)
         plan.keep.append(hyper)
         catchup = (lib.mml_opt_catchup_rows, (a["param"], a["s1"], a["s2"], a["last"], a["rowbase"], a["F"], a["E"],
@@ -551,6 +606,7 @@ class Optimizer:
         if self.table_update != "lazy_exact" or not self.dirty or self.last is None:
             return
         hyper = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev)
+        self.all_rows_warm(self.store.table_names)
         for n in self.store.table_names:
             s1, s2 = self.state[n]
             ops.opt_catchup_dense(self.store.pvals[n].data, s1, s2 if self.kind == "adam" else None, self.last[n], hyper)
