@@ -1111,6 +1111,31 @@ int mml_escm_combine(const float* p_raw, int64_t ldr, const float* y, int64_t ld
  * ---------------------------------------------------------------------------------------------- */
 int mml_auc_segments(const float* pred, int64_t ldp, const float* y, int64_t ldy, int64_t n, int32_t cols, int32_t seg,
                      double* auc, mml_stream_t stream);
+/* The same AUC for segments of ANY length, with optional row masks: a multi-workgroup radix sort of the scores
+ * (csrc/auc_sort.hip).  Whole-set metrics (BaseModel.evaluate, the masked per-domain columns of the CLI's result row,
+ * reference main.py:136-144) and the per-batch train AUC of batches above 4096 rows use it.
+ *   problems   `seg` consecutive rows (seg == 0 or seg >= n: one segment of n rows; the last segment may be short) times
+ *              a column c < cols is one independent problem s * cols + c.  n * cols < 2^31 keys per call.
+ *   labels     a row is positive iff y[r * ldy + c] > 0.5 (as in mml_auc_segments).
+ *   mask       NULL: every row counts.  Otherwise row r takes part in column c iff
+ *              mask[r * ldm + (mask_cols == 1 ? 0 : c)] != 0  (masked_select before scoring); mask_cols is 1 or cols.
+ *   result     auc[s * cols + c] = (double)2U / (2.0 * P * N), NaN when P == 0 or N == 0, with
+ *              counts[3 * (s * cols + c) + {0, 1, 2}] = {2U, P, N} (counts may be NULL) and
+ *              2U = sum over positives of (2 * #negatives with a smaller score + #negatives with an equal score):
+ *              sklearn's roc_auc_score in integer arithmetic.  2U <= 2 * P * N <= n^2 / 2 < 2^61 for every n the call
+ *              accepts, so the 64-bit sums cannot overflow.  +0.0 and -0.0 are one tie group; every finite fp32 score
+ *              is accepted, negative ones included.  A NaN or infinite score at a PARTICIPATING row sets bit 4 (value 16)
+ *              of *status (a device int32 the caller cleared) and makes that problem's auc NaN.
+ *   rules      nothing is allocated or synchronised; HIP-graph capturable; every sum is an integer sum, so the result is
+ *              bitwise repeatable and independent of the order of the rows inside a segment.  `workspace` is a device
+ *              buffer of at least mml_auc_sorted_workspace_bytes(n, cols, seg) bytes (8-byte aligned; -1 for extents the
+ *              call refuses); a shorter one is MML_ERR_ARG, as are mask_cols outside {1, cols} and n * cols >= 2^31.
+ *              n == 0 is MML_OK.  mml_auc_sorted_tile(): keys of one scatter tile (the unit a workgroup ranks in LDS). */
+int32_t mml_auc_sorted_tile(void);
+int64_t mml_auc_sorted_workspace_bytes(int64_t n, int32_t cols, int64_t seg);
+int mml_auc_sorted(const float* pred, int64_t ldp, const float* y, int64_t ldy, const float* mask, int64_t ldm,
+                   int32_t mask_cols, int64_t n, int32_t cols, int64_t seg, void* workspace, int64_t workspace_bytes,
+                   double* auc, int64_t* counts, int32_t* status, mml_stream_t stream);
 /* dst = act'(y) * dy for MML_ACT_SIGMOID2 / SIGMOID / RELU given the forward OUTPUT y (GateNN backward) */
 int mml_act_bwd(const float* y, const float* dy, float* dst, int64_t n, int32_t act, mml_stream_t stream);
 

@@ -282,6 +282,9 @@ _SIGS = {
     "mml_pcgrad_combine": (C.c_int, [_PP(PcgradSeg), i32, i32, fp, fp]),
     "mml_pcgrad_stash": (C.c_int, [_PP(PcgradSeg), i32, i32, fp]),
     "mml_auc_segments": (C.c_int, [fp, i64, fp, i64, i64, i32, i32, fp, fp]),
+    "mml_auc_sorted_tile": (i32, []),
+    "mml_auc_sorted_workspace_bytes": (i64, [i64, i32, i64]),
+    "mml_auc_sorted": (C.c_int, [fp, i64, fp, i64, fp, i64, i32, i64, i32, i64, fp, i64, fp, fp, fp, fp]),
     "mml_bn_workspace_bytes": (C.c_int64, [i64, i32]),
     "mml_bn_fwd": (C.c_int, [fp, i64, fp, fp, fp, fp, fp, fp, fp, fp, i64, i64, i32, i32, i32, C.c_float, C.c_float, fp,
                              i64, fp]),

@@ -68,6 +68,29 @@ def ordered_labels(label_columns):
     return out
 
 
+def _device_aucs(model, labels, pred_ans, test_mask):
+    """The AUCs of the result row with the device_metrics switch on: per_task[i] = AUC of task
+    i over the rows of its domain's test mask, all tasks in ONE ops.auc_sorted call with one mask column per task;
+    total(y, p) = macro-average AUC of summed float64 columns, ordered exactly (BaseModel._order_scores).  A column
+    with one class is NaN (the host path raises there)."""
+    from . import ops
+    dev = next(model.parameters()).device
+    D = model.data_config.get("num_domains", 0)
+    T = len(model.task_types)
+    dom = [i if model.task_name == "msl" else i % D for i in range(T)]
+
+    def f32(a):
+        return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32).to(dev)
+
+    per_task = ops.auc_sorted(f32(pred_ans[:, :T]), f32(labels[:, :T]), mask=f32(test_mask[:, dom]))[0].cpu().numpy()
+
+    def total(y_true, y_score):
+        ps = torch.as_tensor(np.ascontiguousarray(y_score), dtype=torch.float64).to(dev)
+        pr = torch.stack([model._order_scores(ps[:, c]) for c in range(ps.shape[1])], -1).contiguous()
+        return float(ops.auc_sorted(pr, f32(y_true)).mean().item())
+    return per_task, total
+
+
 def evaluate_predictions(model, config, test, target, test_mask, pred_ans):
     """Per-head LogLoss/AUC (+ total_auc for msl/mtmsl) rounded like the reference (main.py:128-172); a regression task
     writes mse_{i} / mae_{i} instead (the reference's rows have no regression form: INTEGRATION.md)."""
@@ -77,6 +100,9 @@ def evaluate_predictions(model, config, test, target, test_mask, pred_ans):
     labels = np.asarray(test[target].values)
     total_auc = None
     D = dc.get("num_domains", 0)
+    dev_task = dev_total = None
+    if getattr(model, "device_metrics", False) and model.task_name in ("msl", "mtmsl"):
+        dev_task, dev_total = _device_aucs(model, labels, pred_ans, test_mask)
     for i, task_type in enumerate(model.task_types):
         yl, yp = labels[:, i], pred_ans[:, i]
         if model.task_name in ("msl", "mtmsl"):
@@ -86,16 +112,24 @@ def evaluate_predictions(model, config, test, target, test_mask, pred_ans):
         if task_type == "regression":
             res[f"mse_{i}"] = round(float(mean_squared_error(yl, yp)), 4)
             res[f"mae_{i}"] = round(float(mean_absolute_error(yl, yp)), 4)
+        elif dev_task is not None:
+            res[f"log_loss_{i}"], res[f"auc_{i}"] = round(log_loss(yl, yp), 4), round(float(dev_task[i]), 4)
         else:
             res[f"log_loss_{i}"], res[f"auc_{i}"] = round(log_loss(yl, yp), 4), round(roc_auc_score(yl, yp), 4)
     if model.task_name == "msl" and model.task_types[0] == "binary":
-        total_auc = roc_auc_score(labels[:, 0], np.sum(pred_ans, axis=-1))
+        if dev_total is not None:
+            total_auc = dev_total(labels[:, :1], np.sum(pred_ans, axis=-1, keepdims=True))
+        else:
+            total_auc = roc_auc_score(labels[:, 0], np.sum(pred_ans, axis=-1))
     elif model.task_name == "mtmsl":
         groups = [g for g in (0, 1) if model.task_types[g * D] == "binary"]
         if groups:
             yt = labels[:, [g * D for g in groups]]
             yp = np.stack([pred_ans[:, g * D:(g + 1) * D].sum(-1) for g in groups], -1)
-            total_auc = roc_auc_score(yt[:, 0], yp[:, 0]) if len(groups) == 1 else roc_auc_score(yt, yp)
+            if dev_total is not None:
+                total_auc = dev_total(yt, yp)
+            else:
+                total_auc = roc_auc_score(yt[:, 0], yp[:, 0]) if len(groups) == 1 else roc_auc_score(yt, yp)
     if total_auc is not None:
         res["total_auc"] = round(total_auc, 4)
     return res

@@ -147,6 +147,8 @@ class BaseModel(nn.Module):
         self._caches = {"store": None, "plans": {}, "steps": {}}
         self.table_update = self.model_config.get("table_update", "auto")  # additive key: auto|dense_exact|sparse_rows
         self.use_hip_graph = bool(self.model_config.get("use_hip_graph", True))
+        # additive key, off by default: whole-set and large-batch metrics on the device
+        self.device_metrics = self._parse_switch(self.optim_config.get("device_metrics", False))
         self.to(device)
 
     # ---- schema helpers ------------------------------------------------------------------------
@@ -519,7 +521,22 @@ class BaseModel(nn.Module):
         return out
 
     # ---- compile (reference :557-647) ------------------------------------------------------------
-    def compile(self, optimizer, loss=None, metrics=None):
+    @staticmethod
+    def _parse_switch(v):
+        """A boolean switch as a config file may spell it (true / false, 1 / 0, "true" / "off" ...)."""
+        if isinstance(v, str):
+            if v.strip().lower() in ("1", "true", "yes", "y", "on"):
+                return True
+            if v.strip().lower() in ("", "0", "false", "no", "n", "off", "none"):
+                return False
+            raise ValueError(f"device_metrics: expected a boolean, got {v!r}")
+        return bool(v)
+
+    def compile(self, optimizer, loss=None, metrics=None, device_metrics=None):
+        """device_metrics: True / False sets the model's `device_metrics` switch (evaluate and the per-batch metrics of
+        batches above 4096 rows on the device); None leaves it as optim_config["device_metrics"] or the attribute set it."""
+        if device_metrics is not None:
+            self.device_metrics = self._parse_switch(device_metrics)
         # a second compile (new optimizer / lr for a second training phase) drops the fused optimizer: rows whose
         # zero-gradient steps are still pending under lazy_exact must replay them first, or the tables silently leave
         # the reference's dense trajectory (ADVICE r4)
@@ -828,10 +845,15 @@ class BaseModel(nn.Module):
         (macro-average AUC over tasks, exact-match accuracy).  Returns {} when a metric cannot be done on the device
         (batches over 4096 rows): the caller then falls back to the host path."""
         want = [m for m in self.metrics if m in ("auc", "acc", "accuracy", "mse")]
-        if not want or batch_size > 4096 or not pred.is_cuda:
+        # batches above 4096 rows: one workgroup cannot sort them (ops.auc_segments); with the device_metrics switch on
+        # they take the multi-workgroup sort (ops.auc_sorted), otherwise the host path as before
+        big = batch_size > 4096
+        if not want or (big and not getattr(self, "device_metrics", False)) or not pred.is_cuda:
             return {}
         ye = yd.index_select(0, perm_d)
-        if self.task_name == "msl":
+        if big:  # (the heads of a group are summed in float64, as on the host: _order_scores)
+            yt, pt = self._device_columns(ye, pred)
+        elif self.task_name == "msl":
             yt, pt = ye[:, :1], pred.sum(-1, keepdim=True)
         elif self.task_name == "mtmsl":
             D = self.num_domains
@@ -857,7 +879,10 @@ class BaseModel(nn.Module):
 
         if "auc" in want:
             ya, pa = columns("auc")
-            a = ops.auc_segments(pa, ya, batch_size)            # [steps, C]; NaN = single-class batch
+            # [steps, C]; NaN = single-class batch
+            if big and pa.dtype == torch.float64:
+                pa = torch.stack([self._order_scores(pa[:, c]) for c in range(pa.shape[1])], -1).contiguous()
+            a = ops.auc_sorted(pa, ya, seg=batch_size) if big else ops.auc_segments(pa, ya, batch_size)
             out["auc"] = float(a.mean(1).sum().item()) / steps  # macro average over columns, mean over steps
         for name in ("acc", "accuracy"):
             if name in want:
@@ -885,7 +910,64 @@ class BaseModel(nn.Module):
         except ValueError:  # a batch with a single class has no AUC; the reference would raise here
             return float("nan")
 
+    @staticmethod
+    def _order_scores(s64):
+        """fp32 scores with exactly the order and the ties of a float64 device vector: its dense ranks, written as the bit
+        patterns of increasing normal floats.  The host path ranks the float64 sum of an msl / mtmsl group's heads; rounding
+        that sum to fp32 would merge scores that differ, and one merged (positive, negative) pair moves the AUC by
+        1 / (2 P N).  mml_auc_sorted orders by bit pattern, so ranks up to 2^31 - 2^24 are exact.  A NaN or infinite score
+        stays NaN (torch.unique would rank it like any value): the kernel then flags it and the problem's AUC is NaN, as
+        sklearn's refusal makes it on the host."""
+        _, inv = torch.unique(s64, sorted=True, return_inverse=True)
+        ranks = (inv + 0x00800000).to(torch.int32).view(torch.float32)
+        return torch.where(torch.isfinite(s64), ranks, torch.full_like(ranks, float("nan")))
+
+    def _device_columns(self, yd, pred):
+        """The task-mode reduction of _metric on device tensors: labels [n, C] float32 and scores [n, C] (float64 where a
+        column is a sum of heads, as on the host, else the fp32 predictions)."""
+        if self.task_name == "msl":
+            return yd[:, :1], pred.double().sum(-1, keepdim=True)
+        if self.task_name == "mtmsl":
+            D = self.num_domains
+            p64 = pred.double()
+            return yd[:, [0, D]], torch.stack([p64[:, :D].sum(-1), p64[:, D:].sum(-1)], -1)
+        return yd, pred
+
+    def _evaluate_device(self, x, y, batch_size, domain_mask):
+        """evaluate() with the device_metrics switch on: the predictions stay in HBM; auc = macro average over the columns
+        of ops.auc_sorted over the whole set, acc / mse as in _device_batch_metrics.  logloss keeps the host path
+        (O(n), and the clip rule is sklearn's)."""
+        pred_d, _ = self._predict_device(x, batch_size, domain_mask)
+        if self.metric_columns is not None:
+            pred_d = pred_d[:, list(self.metric_columns)]
+        n = pred_d.shape[0]
+        y = np.asarray(y).reshape(n, -1)
+        yd = torch.as_tensor(y, dtype=torch.float32).to(pred_d.device)
+        yt, pt = self._device_columns(yd, pred_d)
+        out, host_pred = {}, None
+        for name, fn in self.metrics.items():
+            cols = self.metric_cols.get(name)
+            # (msl has ONE summed column and _metric never selects from it: the same here)
+            ya, pa = (yt, pt) if cols is None or self.task_name == "msl" else (yt[:, cols], pt[:, cols])
+            if name == "auc":
+                if pa.dtype == torch.float64:
+                    pa = torch.stack([self._order_scores(pa[:, c]) for c in range(pa.shape[1])], -1)
+                a = ops.auc_sorted(pa.contiguous(), ya.contiguous(), seg=0)  # [1, C]; NaN = single-class column
+                out[name] = float(a.mean().item())
+            elif name in ("acc", "accuracy"):
+                out[name] = int(((pa > 0.5) == (ya > 0.5)).all(1).sum().item()) / n  # exact match over the columns
+            elif name == "mse":
+                out[name] = float(((pa.double() - ya.double()) ** 2).mean(0).mean().item())
+            else:
+                if host_pred is None:
+                    host_pred = pred_d.cpu().numpy().astype("float64")
+                out[name] = self._metric(fn, y, host_pred, cols)
+        return out
+
     def evaluate(self, x, y, batch_size=256, domain_mask=None):
+        # (a model that is not on a GPU keeps the host path, like _device_batch_metrics; it cannot predict there anyway)
+        if getattr(self, "device_metrics", False) and self._store().device.type == "cuda":
+            return self._evaluate_device(x, y, batch_size, domain_mask)
         pred = self.predict(x, batch_size, domain_mask)
         if self.metric_columns is not None:  # (the reference scores all columns here and raises for ESCM: model/escm.py)
             pred = pred[:, list(self.metric_columns)]
@@ -895,6 +977,14 @@ class BaseModel(nn.Module):
     def predict(self, x, batch_size=256, domain_mask=None):
         """float64 [N,T] predictions -- probabilities, raw values in the columns of regression tasks (reference :395-457).  Like the reference's loop (:436-437) the heads
         are NOT masked here; pass a mask to forward() directly for masked outputs."""
+        pred, layers = self._predict_device(x, batch_size, domain_mask)
+        pred = pred.cpu().numpy().astype("float64")
+        if self.save_layer_output:
+            return pred, {k: np.concatenate(v).astype("float64") for k, v in layers.items()}
+        return pred
+
+    def _predict_device(self, x, batch_size=256, domain_mask=None):
+        """The predict loop: float32 [N,T] predictions on the device, and the collected layer outputs (host lists)."""
         was_training = self.training
         self.eval()
         X = x if isinstance(x, np.ndarray) and x.ndim == 2 else self._as_matrix(x)
@@ -914,8 +1004,6 @@ class BaseModel(nn.Module):
             self._defer_status = False
         for pl in self._caches["plans"].values():  # out-of-range indices of ANY batch are sticky in the plan's status word
             ops.check_status(pl.status, "embedding lookup (nn.Embedding semantics)")
-        pred = torch.cat(outs).cpu().numpy().astype("float64")
+        pred = torch.cat(outs)
         self.train(was_training)
-        if self.save_layer_output:
-            return pred, {k: np.concatenate(v).astype("float64") for k, v in layers.items()}
-        return pred
+        return pred, layers

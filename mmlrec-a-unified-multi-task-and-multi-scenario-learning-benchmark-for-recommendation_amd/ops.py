@@ -1046,6 +1046,77 @@ def auc_segments(pred, y, seg):
     return out
 
 
+AUC_STATUS_NONFINITE = 16  # bit 4 of mml_auc_sorted's status word: a NaN / infinite score at a participating row
+
+
+def auc_key_image(score):
+    """The 32-bit order-preserving image of an fp32 score that mml_auc_sorted sorts by (csrc/auc_sort.hip, auc_image):
+    -0.0 becomes +0.0, negative floats have all bits flipped, the others get the sign bit set.  a < b as floats
+    <=> image(a) < image(b) as unsigned integers, and a == b <=> equal images.  Pure Python, for tests and docs."""
+    import struct
+    u, = struct.unpack("<I", struct.pack("<f", float(score)))
+    if u == 0x80000000:
+        u = 0
+    return (~u & 0xffffffff) if u & 0x80000000 else (u | 0x80000000)
+
+
+_auc_workspaces = {}
+
+
+def _auc_workspace(device, n, cols, seg):
+    """The workspace of one (device, stream, n, cols, seg): cached, a few shapes recur (evaluate's set, fit's epoch).  One
+    per stream, because two calls that share a workspace must be ordered.  While a graph is being captured the buffer
+    is allocated for that call instead (from the capture's memory pool, so it lives as long as the graph that holds its
+    address): an entry of the cache may be evicted, a captured address may not."""
+    nbytes = L.load().mml_auc_sorted_workspace_bytes(int(n), int(cols), int(seg))
+    if nbytes < 0:
+        raise L.MMLError(f"mml_auc_sorted: n * cols = {n} * {cols} keys, the call takes fewer than 2^31")
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+    key = (device.type, device.index, _stream(), int(n), int(cols), int(seg))
+    ws = _auc_workspaces.get(key)
+    if ws is None:
+        if len(_auc_workspaces) >= 8:  # (16 bytes per key each: the oldest shape goes)
+            _auc_workspaces.pop(next(iter(_auc_workspaces)))
+        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+        _auc_workspaces[key] = ws
+    return ws
+
+
+def auc_sorted(pred, y, seg=0, mask=None, return_counts=False, status=None):
+    """AUC of every (segment of `seg` rows, column) pair of device matrices pred / y [n, C] -> float64 [segments, C], for
+    segments of ANY length (seg = 0: the whole set is one segment) -- mml_auc_sorted, a multi-workgroup radix sort.
+    mask [n, 1] or [n, C] float32: a row takes part in a column iff its mask entry is non-zero (masked_select before
+    scoring).  NaN where a problem holds one class, no row, or a non-finite score at a participating row; the latter
+    also sets AUC_STATUS_NONFINITE in `status` (a device int32 tensor of one element the caller cleared; optional).
+    return_counts: also the int64 [segments, C, 3] tensor of (2U, P, N), the integers the AUC is formed from."""
+    _need_gpu(pred, y, mask, status)
+    lib = L.load()
+    pred, y = _f32_2d(pred, "pred"), _f32_2d(y, "y")
+    n, c = pred.shape
+    if tuple(y.shape) != (n, c):
+        raise L.MMLError(f"auc_sorted: pred {tuple(pred.shape)} and y {tuple(y.shape)} differ")
+    seg = int(seg)
+    if seg <= 0 or seg >= n:
+        seg = 0
+    nseg = 1 if seg == 0 else (n + seg - 1) // seg
+    mask_cols = 0
+    if mask is not None:
+        mask = _f32_2d(mask, "mask")
+        mask_cols = mask.shape[1]
+        if mask.shape[0] != n:
+            raise L.MMLError(f"auc_sorted: mask has {mask.shape[0]} rows, pred {n}")
+    out = torch.empty((nseg, c), dtype=torch.float64, device=pred.device)
+    counts = torch.empty((nseg, c, 3), dtype=torch.int64, device=pred.device) if return_counts else None
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=pred.device)
+    ws = _auc_workspace(pred.device, n, c, seg)
+    L.check(lib.mml_auc_sorted(pred.data_ptr(), _ld(pred), y.data_ptr(), _ld(y), L.ptr(mask),
+                               _ld(mask) if mask is not None else 0, mask_cols, n, c, seg, ws.data_ptr(), ws.numel(),
+                               out.data_ptr(), L.ptr(counts), status.data_ptr(), _stream()), "mml_auc_sorted")
+    return (out, counts) if return_counts else out
+
+
 # ---------------------------------------------------------------------------------------------- K3' (bf16 storage)
 def _is16(t):
     return t.dtype == torch.bfloat16
