@@ -1195,6 +1195,11 @@ typedef struct {
    * leave them slots (uncapped, a B = 4 096 step's GEMMs waited 0.3 ms for a slot), and it has the whole forward +
    * backward to finish in. */
   int32_t max_blocks;
+  /* Loop of the marked streaming launch over tensors with a warm map.  0: a lane reads one aligned dword of marks and one
+   * of warm bytes (four rows), the wave compacts its live rows and shares their chunks out among its lanes.  1: the loop
+   * before that (a byte of each map per 16-byte chunk), kept for A/B runs; a tensor whose maps are not 4-byte aligned takes
+   * it either way.  The same bits in both.  (The field fills what was the struct's tail padding: its size is unchanged.) */
+  int32_t cold_loop;
 } mml_opt_hyper;
 /* dense update of up to MML_MAX_OPT_TENSORS whole tensors in one launch (tables included: the reference's
  * optimizer touches every row of every table every step) */

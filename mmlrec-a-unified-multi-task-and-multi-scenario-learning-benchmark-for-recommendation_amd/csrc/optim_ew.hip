@@ -18,7 +18,7 @@ namespace mml {
 struct OptLaunch {
   mml_opt_tensor t[MML_MAX_OPT_TENSORS];
   int32_t n;
-  int32_t variant;  // streaming form of the vector loop (tuning knob MMLREC_OPT_VARIANT): bit 0 = nontemporal, bit 1 = 2x unroll; bit 2 = capped grid (4 chunks in flight per thread)
+  int32_t variant;  // streaming form of the vector loop (tuning knob MMLREC_OPT_VARIANT): bit 0 = nontemporal, bit 1 = 2x unroll; bit 2 = capped grid (4 chunks in flight per thread); bit 3 = mml_opt_hyper.cold_loop is 1 (the byte-walking loop over a warm map)
   mml_opt_hyper h;
   int64_t chunk0[MML_MAX_OPT_TENSORS + 1];  // flat kernel: first 4-element chunk of tensor i in the concatenation
   // streaming kernel over MANY tensors (round 6: every table of the model in one marked launch): a 1-D grid whose
@@ -233,8 +233,162 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
     // warm map (forms 3 and 4, and the remainder loop of every form): 0 = the row's moments are still zero.  Read like
     // the mark: by every lane of the row in one wave-instruction, before the first chunk's lane sets it.
     uint8_t* const wr = gm ? T.warm_rows : nullptr;
-    if ((PATH == OPT_MARK_U || PATH == OPT_MARK_ACC_U) && wr && !skip) {  // (workgroup-uniform)
-      // Mostly-cold stream: the bytes of CB chunks' rows (2 CB one-byte loads in flight, no load depends on another), then
+    // (workgroup-uniform: the launch's switch and this tensor's map pointers)
+    const bool compact = !(L.variant & 8) && wr &&
+                         ((reinterpret_cast<uintptr_t>(gm) | reinterpret_cast<uintptr_t>(wr)) & 3) == 0;
+    if ((PATH == OPT_MARK_U || PATH == OPT_MARK_ACC_U) && compact && !skip) {
+      // Mostly-cold stream, wave-compacted.  A wave owns spans of SPAN consecutive rows, dealt by its number in the tensor's
+      // workgroups; lane l reads the marks and the warm bytes of rows [4 l, 4 l + 4) of the span with one aligned dword
+      // load each (the next span's are in flight while this one is worked on) and is the only reader and writer of those map
+      // bytes in the launch.  The live rows (marked or warm) are listed in the wave's LDS list -- exclusive prefix sum of
+      // the lanes' counts from ballots of the counts' bits, no atomics, no workgroup barrier -- and the list's 16-byte
+      // chunks are shared out 128 at a time, two per lane in flight, every load of a lane before its first store: a wave
+      // pays one round trip for the maps (hidden behind the previous span) and one per 128 live chunks, wherever in the
+      // span they lie.  A span with no live row costs nothing more; one with more than a few live rows skips the list (DENSE_PCT).
+      // (Four dwords of each map per lane, spans of 1 024 rows, lost at every warm share: DESIGN_HISTORY.md, "Cold rows".)
+      constexpr int RPL = 4, SPAN = 64 * RPL;  // rows per lane (one dword of each map), rows per wave trip
+      // Live rows, in per cent of a span, from which the span is walked row by row instead of listed.  Measured with 1, 15,
+      // 33, 50 and 100: listing spans that are 15-50 % live cost 8-12 us of ~500 at 60-76 % warm rows, at 15 the launch is
+      // level with the loop before from there on and keeps the list's whole gain below (DESIGN_HISTORY.md).
+      constexpr int DENSE_PCT = 15;
+      constexpr int WAVES = 4;  // per workgroup: every launch of this kernel has 256 threads (__launch_bounds__(256))
+      __shared__ uint16_t live_rows[WAVES][SPAN];  // entry: bits 0-13 row of the span, 14 marked, 15 was warm
+      const int lane = threadIdx.x & 63;
+      const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (scalar: the span loop is wave-uniform)
+      uint16_t* const lst = live_rows[wv];
+      const int csh = rsh - 2;  // log2(chunks per row): row_elems / 4 is a power of two (mml_opt_step_dense checks)
+      const int64_t rows = T.n >> rsh;
+      const int64_t nspan = (rows + SPAN - 1) / SPAN, nwv = (int64_t)nblk * WAVES;
+      // 0x80 in every byte of x that is not zero
+      auto nz80 = [](uint32_t x) { return (x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u; };
+      auto pack4 = [](uint32_t t) { return ((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u); };
+      // the lane's map bytes of span s: the whole words where all four rows exist, else the bytes below `rows` one by one
+      auto scan = [&](int64_t s, uint32_t& mk, uint32_t& wk) {
+        const int64_t r0 = s * SPAN + lane * RPL;
+        mk = wk = 0u;
+        if (r0 + RPL <= rows) {
+          mk = *reinterpret_cast<const uint32_t*>(gm + r0);
+          wk = *reinterpret_cast<const uint32_t*>(wr + r0);
+        } else {
+#pragma unroll
+          for (int k = 0; k < RPL; ++k)
+            if (r0 + k < rows) {
+              mk |= (uint32_t)gm[r0 + k] << (8 * k);
+              wk |= (uint32_t)wr[r0 + k] << (8 * k);
+            }
+        }
+      };
+      int64_t s = (int64_t)lblk * WAVES + wv;
+      uint32_t mk = 0, wk = 0;
+      if (s < nspan) scan(s, mk, wk);
+      for (; s < nspan; s += nwv) {  // (wave-uniform)
+        uint32_t mkn = 0, wkn = 0;
+        if (s + nwv < nspan) scan(s + nwv, mkn, wkn);
+        const uint32_t lm = pack4(nz80(mk)), wm = pack4(nz80(wk));  // bit k: row k of this lane is marked / warm
+        const uint32_t act = lm | wm;
+        if (__builtin_amdgcn_ballot_w64(act != 0) != 0) {
+          const int64_t row0 = s * SPAN;
+          // live rows of the span and, per lane, of the lanes below it: ballots of the bits of the lanes' counts
+          const uint32_t cnt = (uint32_t)__builtin_popcount(act);
+          uint32_t pre = 0;
+          int nlive = 0;
+#pragma unroll
+          for (int bit = 0; (1 << bit) <= RPL; ++bit) {
+            const uint64_t bal = __builtin_amdgcn_ballot_w64(((cnt >> bit) & 1u) != 0);
+            pre += __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u)) << bit;
+            nlive += __builtin_popcountll(bal) << bit;
+          }
+          // A span with that many live rows is walked row by row without the list, dead chunks passed over (the 100 %-warm
+          // stream pays no compaction)
+          const bool dense = nlive * 100 >= SPAN * DENSE_PCT;
+          if (!dense) {
+            // (the lanes' reads of the previous span's list come before these writes, and these before the reads below:
+            // the LDS serves a wave's instructions in order)
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int k = 0; k < RPL; ++k)
+              if ((act >> k) & 1u)
+                lst[pre++] = (uint16_t)((lane * RPL + k) | (((lm >> k) & 1u) << 14) | (((wm >> k) & 1u) << 15));
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+          }
+          // map upkeep by the bytes' only reader: marks cleared, the marked rows that were cold now warm
+          if (lm) {
+            const int64_t r0 = row0 + lane * RPL;
+            if (r0 + RPL <= rows) {
+              *reinterpret_cast<uint32_t*>(gm + r0) = 0u;
+              const uint32_t set = (nz80(mk) & ~nz80(wk)) >> 7;  // 1 in the byte of every marked row that was cold
+              if (set) *reinterpret_cast<uint32_t*>(wr + r0) = wk | set;
+            } else {
+#pragma unroll
+              for (int k = 0; k < RPL; ++k)
+                if ((lm >> k) & 1u) {  // (only rows below `rows` were read)
+                  gm[r0 + k] = 0;
+                  if (!((wm >> k) & 1u)) wr[r0 + k] = 1;
+                }
+            }
+          }
+          const int items = (dense ? SPAN : nlive) << csh;
+#pragma unroll 1
+          for (int b0 = 0; b0 < items; b0 += 128) {
+            f4 p[2], a[2], b[2], g[2];
+            l2 t0[2], t1[2];
+            int64_t jj[2];
+            bool on[2], lv[2];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const int it = b0 + 64 * k + lane;
+              const int ent = it >> csh;
+              on[k] = it < items;
+              uint32_t e;
+              if (dense) {  // (all 256 rows in order; the live and marked bits from the lane that read the row's bytes)
+                const uint32_t src = (uint32_t)__shfl((int)(lm | (act << 16)), (ent / RPL) & 63);
+                on[k] = on[k] && ((src >> (16 + (ent & (RPL - 1)))) & 1u);
+                e = (uint32_t)ent | (((src >> (ent & (RPL - 1))) & 1u) << 14);
+              } else {
+                e = on[k] ? lst[ent] : 0u;
+              }
+              lv[k] = on[k] && ((e >> 14) & 1u);
+              const int64_t j = ((row0 + (int64_t)(e & 0x3fffu)) << csh) | (int64_t)(it & ((1 << csh) - 1));
+              jj[k] = j;
+              p[k] = a[k] = b[k] = g[k] = zero;
+              t0[k] = t1[k] = lzero;
+              if (on[k]) {
+                p[k] = ld(P + j);
+                if (S1) a[k] = ld(S1 + j);
+                if (S2) b[k] = ld(S2 + j);
+              }
+              if (lv[k]) {
+                if (!zg) g[k] = ld(G + j);
+                if (PATH == OPT_MARK_ACC_U && A64) {
+                  t0[k] = A64[2 * j];
+                  t1[k] = A64[2 * j + 1];
+                }
+              }
+            }
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              if (!on[k]) continue;
+              const int64_t j = jj[k];
+              f4 gs = g[k];
+              if (PATH == OPT_MARK_ACC_U && A64 && lv[k]) add_totals(gs, t0[k], t1[k], j);
+              one(p[k], gs, a[k], b[k]);
+              st(P + j, p[k]);
+              if (S1) st(S1 + j, a[k]);
+              if (S2) st(S2 + j, b[k]);
+              if (h.zero_grad && (g[k].x != 0.f || g[k].y != 0.f || g[k].z != 0.f || g[k].w != 0.f)) G[j] = zero;
+            }
+          }
+        }
+        mk = mkn;
+        wk = wkn;
+      }
+      i = n4;  // (every chunk of the tensor is done: the loops below find nothing left)
+    }
+    if ((PATH == OPT_MARK_U || PATH == OPT_MARK_ACC_U) && wr && !skip && !compact) {  // (workgroup-uniform)
+      // The loop before the compacted one (mml_opt_hyper.cold_loop = 1, or map pointers that are not aligned for the word
+      // loads).  Mostly-cold stream: the bytes of CB chunks' rows (2 CB one-byte loads in flight, no load depends on another), then
       // only the live chunks, two at a time as in the forms below; a wave none of whose lanes has a live chunk moves on
       // without a further memory access.  The block covers its own remainder (chunks past the end are not live).
       constexpr int CB = MML_OPT_COLD_CB;
@@ -1005,7 +1159,7 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
       const char* e = getenv("MMLREC_OPT_VARIANT");
       variant = e ? atoi(e) : 0;
     }
-    L.variant = variant | (hyper->max_blocks > 0 ? 4 : 0);
+    L.variant = variant | (hyper->max_blocks > 0 ? 4 : 0) | (hyper->cold_loop == 1 ? 8 : 0);
     // A group dominated by one huge tensor (the dense table update) streams with the per-tensor kernel (blockIdx.y =
     // tensor: no index search on the 2.7 GB stream); everything else (dozens of tensors from 64 B to a few MB) goes
     // through the flat kernel, where every workgroup has the same amount of work.

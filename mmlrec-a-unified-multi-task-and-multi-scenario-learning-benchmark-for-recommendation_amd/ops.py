@@ -954,8 +954,10 @@ def act_bwd(y, dy, dst, act):
 
 
 # ---------------------------------------------------------------------------------------------- K8
-def make_hyper(kind, lr, step=1, step_dev=None, zero_grad=False, max_blocks=0):
+def make_hyper(kind, lr, step=1, step_dev=None, zero_grad=False, max_blocks=0, cold_loop=0):
+    """cold_loop: mml_opt_hyper.cold_loop (1 = the byte-walking loop over a warm map, for A/B runs)."""
     h = L.OptHyper()
+    h.cold_loop = int(cold_loop)
     h.kind = L.OPT_KINDS[kind] if isinstance(kind, str) else int(kind)
     h.step = int(step)
     h.step_dev = L.ptr(step_dev)

@@ -54,6 +54,9 @@ class OptKnobs:
     # MMLREC_OPT_COLD_ROWS=0: the marked streaming launch gets no warm map (mml_opt_tensor.warm_rows) and updates every
     # row, as it did before the map existed (A/B switch; the results are the same bits either way)
     cold_rows: bool = True
+    # MMLREC_OPT_COLD_COMPACT=0: the launch walks a warm map byte by byte, chunk by chunk, as before the wave-compacted loop
+    # (mml_opt_hyper.cold_loop = 1; A/B switch, the same bits either way)
+    cold_compact: bool = True
 
     @classmethod
     def from_env(cls, env=None):
@@ -67,7 +70,8 @@ class OptKnobs:
                    one_launch=env.get("MMLREC_OPT_ONE_LAUNCH", "0") == "1",
                    variant=int(env.get("MMLREC_OPT_VARIANT", "0")),
                    scatter_old=bool(env.get("MMLREC_SCATTER_OLD")),
-                   cold_rows=env.get("MMLREC_OPT_COLD_ROWS", "1") != "0")
+                   cold_rows=env.get("MMLREC_OPT_COLD_ROWS", "1") != "0",
+                   cold_compact=env.get("MMLREC_OPT_COLD_COMPACT", "1") != "0")
 
 
 TABLE_UPDATES = ("dense_exact", "sparse_rows", "lazy_exact")
@@ -185,6 +189,12 @@ def launch_trusts_warm_map(kind, marked, table_reg, knobs, sharded=False):
     not trust the map takes None and, since it writes moments the map does not know of, marks every row of its tables
     warm (Optimizer.all_rows_warm) -- as does every other writer of a table's moments."""
     return bool(marked and kind in WARM_KINDS and not table_reg and knobs.cold_rows and not sharded)
+
+
+def cold_loop_of(knobs):
+    """mml_opt_hyper.cold_loop of the dense table launches: 0 = the wave-compacted loop over a warm map, 1 = the loop
+    before it (knobs.cold_compact off).  A launch without a warm map does not look at the field."""
+    return 0 if knobs.cold_compact else 1
 
 
 class TableRows:
@@ -451,7 +461,7 @@ class Optimizer:
         tabs = [st.pvals[n] for n in names]
         cap = knobs.early_blocks if split_dense else knobs.tail_blocks
         hz = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev, zero_grad=not split_dense,
-                            max_blocks=cap)
+                            max_blocks=cap, cold_loop=cold_loop_of(knobs))
         plan.keep.append(hz)
         seen_of = dict(zip(st.rows_names, st.rows.seen)) if split_dense else {}
         # marked gradients (the scatter of this plan marked every row it added to): the streaming launch does not

@@ -6,7 +6,7 @@ row for the last line; the first line is the launch without a map (every row upd
 more batch, as the scatter of a step does, and runs behind a 1 GiB pass that empties the caches; HIP events around the
 launch, median of `reps` replays after `warm-up` ones.
 usage: python tools/lab/opt_cold_rows.py [reps [warm-up [lines]]]   lines: e.g. 4,every (default 4,30,300,1000,every);
-MMLREC_LIB=<library> times another build of the kernel (-DMML_OPT_COLD_CB=...)."""
+MMLREC_LIB=<library> times another build of the kernel (-DMML_OPT_COLD_CB=...) or the library of another commit."""
 import os
 import sys
 
