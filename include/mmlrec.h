@@ -1198,9 +1198,35 @@ typedef struct {
   /* Loop of the marked streaming launch over tensors with a warm map.  0: a lane reads one aligned dword of marks and one
    * of warm bytes (four rows), the wave compacts its live rows and shares their chunks out among its lanes.  1: the loop
    * before that (a byte of each map per 16-byte chunk), kept for A/B runs; a tensor whose maps are not 4-byte aligned takes
-   * it either way.  The same bits in both.  (The field fills what was the struct's tail padding: its size is unchanged.) */
+   * it either way.  The same bits in both.  (The field fills what was the struct's tail padding: its size is unchanged.)
+   * Where loop 0 runs: a launch ALL of whose tensors carry a warm map with 4-byte aligned map pointers runs on one grid
+   * sized for the chip (8 workgroups per compute unit, no more than the launch would get otherwise, max_blocks included),
+   * the 256-row spans of all tensors dealt to its waves; any other launch on the workgroups of each tensor.
+   * 2: loop 0 on the per-tensor workgroups in every launch (A/B arm).  3: as 0 with 4 workgroups per compute unit, which
+   * is what fits the chip at once (A/B arm). */
   int32_t cold_loop;
 } mml_opt_hyper;
+/* The constants of one optimizer step, computed once per step on the device by mml_opt_step_begin instead of by every
+ * workgroup of every optimizer launch: Adam's lr / (1 - beta1^step) and 1 / sqrt(1 - beta2^step) (the double-precision
+ * expressions of torch.optim.Adam, the same bits as the kernels' own), and the step they belong to.  16 bytes on the
+ * device, 16-byte aligned. */
+typedef struct {
+  int32_t step;
+  float step_size;
+  float inv_bc2s;
+  int32_t pad_;
+} mml_opt_step_consts;
+/* Start of a step, ONE single-thread launch: *step_dev += delta, then *consts = the constants of the new step under
+ * hyper's kind / lr / beta1 / beta2 (hyper->step and hyper->step_dev are not read).  The library remembers that `consts`
+ * belongs to `step_dev` under those four values: mml_opt_step_dense and mml_opt_step_rows launched afterwards with
+ * hyper->step_dev == step_dev and the same four values have their kernels read *consts instead of computing the
+ * constants per workgroup -- at run time, so a captured [begin, update] sequence replays correctly.  A kernel that finds
+ * consts->step != *step_dev (somebody else moved the counter) computes them itself.  `consts` must stay allocated as
+ * long as the binding exists: until mml_opt_step_unbind(step_dev), a mml_counter_update on step_dev, or another
+ * mml_opt_step_begin on it.  Other hyper values, a host step (step_dev == NULL) or no binding: as before. */
+int mml_opt_step_begin(int32_t* step_dev, int32_t delta, const mml_opt_hyper* hyper, mml_opt_step_consts* consts,
+                       mml_stream_t stream);
+int mml_opt_step_unbind(const int32_t* step_dev);
 /* dense update of up to MML_MAX_OPT_TENSORS whole tensors in one launch (tables included: the reference's
  * optimizer touches every row of every table every step) */
 int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, const mml_opt_hyper* hyper, mml_stream_t stream);

@@ -196,6 +196,11 @@ class OptHyper(C.Structure):
                 ("cold_loop", i32)]
 
 
+class OptStepConsts(C.Structure):
+    """mml_opt_step_consts: what mml_opt_step_begin leaves on the device (16 bytes, 16-byte aligned)."""
+    _fields_ = [("step", i32), ("step_size", C.c_float), ("inv_bc2s", C.c_float), ("pad_", i32)]
+
+
 _PP = C.POINTER
 _SIGS = {
     "mml_version": (C.c_int, []),
@@ -313,6 +318,8 @@ _SIGS = {
     "mml_index_unique": (C.c_int, [_PP(i64), _PP(i32), i32, i32, fp, i64, i64, _PP(fp), _PP(i64), fp, fp, i32, fp, fp,
                                    fp]),
     "mml_counter_update": (C.c_int, [fp, i32, i32, fp]),
+    "mml_opt_step_begin": (C.c_int, [fp, i32, _PP(OptHyper), fp, fp]),
+    "mml_opt_step_unbind": (C.c_int, [fp]),
     "mml_gather_pool_wgmax_len": (i64, [_PP(PoolDesc), i32, i64]),
     "mml_gather_pool_fwd": (C.c_int, [_PP(PoolDesc), fp, i64, i32, i32, i64, fp, i64, fp, i64, fp, i64, fp, fp]),
     "mml_scatter_pool_bwd": (C.c_int, [_PP(PoolDesc), fp, i64, i64, fp, i64, fp, i64, _PP(fp), _PP(i64), fp, fp, i32,

@@ -7,6 +7,9 @@
 
 #include <stdlib.h>
 
+#include <mutex>
+#include <vector>
+
 // chunks whose mark / warm bytes a thread of the mostly-cold table stream reads before it looks at any of them (lab builds:
 // -DMML_OPT_COLD_CB=2 / 4 / 16, tools/lab/opt_cold_rows.py; DESIGN_HISTORY.md has the numbers)
 #ifndef MML_OPT_COLD_CB
@@ -24,7 +27,10 @@ struct OptLaunch {
   // streaming kernel over MANY tensors (round 6: every table of the model in one marked launch): a 1-D grid whose
   // workgroups are dealt to the tensors in proportion to their sizes; blk0[i] = first workgroup of tensor i (prop != 0)
   int32_t blk0[MML_MAX_OPT_TENSORS + 1];
+  // 2: one grid over the 256-row spans of ALL tensors (cold_resident); blk0[i] = first span of tensor i instead
   int32_t prop;
+  // the step's constants where mml_opt_step_begin keeps them for h.step_dev (null: every workgroup computes them)
+  const mml_opt_step_consts* sc;
 };
 static_assert(sizeof(OptLaunch) <= 4096, "OptLaunch travels by value: the kernel-argument block holds 4 KB");
 
@@ -33,21 +39,40 @@ struct StepConsts {
   float inv_bc2s;   // Adam: 1 / sqrt(1 - beta2^t)
 };
 
-// Computed by ONE lane per workgroup (double-precision pow is hundreds of instructions) and broadcast through LDS.
-__device__ __forceinline__ StepConsts step_consts(const mml_opt_hyper& h) {
-  __shared__ StepConsts sc;
-  if (threadIdx.x == 0) {
-    StepConsts c{h.lr, 1.f};
-    if (h.kind == MML_OPT_ADAM) {
-      const int t = h.step_dev ? *h.step_dev : h.step;
-      // torch computes the bias corrections in double precision on the host (python floats)
-      const double bc1 = 1.0 - pow((double)h.beta1, (double)t);
-      const double bc2 = 1.0 - pow((double)h.beta2, (double)t);
-      c.step_size = (float)((double)h.lr / bc1);
-      c.inv_bc2s = (float)(1.0 / sqrt(bc2));
-    }
-    sc = c;
+// The constants of step t (one copy of the expressions: the same double operations in the same order wherever they run).
+__device__ __forceinline__ StepConsts step_consts_of(const mml_opt_hyper& h, int t) {
+  StepConsts c{h.lr, 1.f};
+  if (h.kind == MML_OPT_ADAM) {
+    // torch computes the bias corrections in double precision on the host (python floats)
+    const double bc1 = 1.0 - pow((double)h.beta1, (double)t);
+    const double bc2 = 1.0 - pow((double)h.beta2, (double)t);
+    c.step_size = (float)((double)h.lr / bc1);
+    c.inv_bc2s = (float)(1.0 / sqrt(bc2));
   }
+  return c;
+}
+
+// bound: the buffer mml_opt_step_begin filled for h.step_dev with this optimizer's lr / beta1 / beta2 at the start of the
+// step (the host looked the binding up) -- two uniform loads, no barrier; the buffer names the step it was computed for,
+// and a counter that somebody else has moved since sends the workgroup down the path below.
+// Else computed by ONE lane per workgroup (double-precision pow is hundreds of instructions) and broadcast through LDS.
+__device__ __forceinline__ StepConsts step_consts(const mml_opt_hyper& h, const mml_opt_step_consts* bound = nullptr) {
+  // (one exit for the bound path: with a return per case the compiler keeps the whole kernel-argument block in scratch)
+  bool have = false;
+  StepConsts r{h.lr, 1.f};
+  if (bound) {  // (workgroup-uniform, as is what it reads)
+    if (h.kind != MML_OPT_ADAM) {
+      have = true;
+    } else if (bound->step == *h.step_dev) {
+      r.step_size = bound->step_size;
+      r.inv_bc2s = bound->inv_bc2s;
+      have = true;
+    }
+  }
+  if (have) return r;
+  __shared__ StepConsts sc;
+  if (threadIdx.x == 0)  // (only Adam reads the step)
+    sc = step_consts_of(h, h.kind != MML_OPT_ADAM ? 0 : h.step_dev ? *h.step_dev : h.step);
   __syncthreads();
   return sc;
 }
@@ -84,6 +109,255 @@ __device__ __forceinline__ float reg_grad(float g, float p, float l1, float l2) 
   return g;
 }
 
+// ---- the wave-compacted loop over a warm map: one span of one tensor ---------------------------------------------------
+// Mostly-cold stream (forms 3 and 4 of opt_dense_kernel, tensors with a warm map whose map pointers are 4-byte aligned).
+// A wave owns spans of SPAN consecutive rows; lane l reads the marks and the warm bytes of rows [4 l, 4 l + 4) of the span
+// with one aligned dword load each (the next span's are in flight while this one is worked on) and is the only reader and
+// writer of those map bytes in the launch.  The live rows (marked or warm) are listed in the wave's LDS list -- exclusive
+// prefix sum of the lanes' counts from ballots of the counts' bits, no atomics, no workgroup barrier -- and the list's
+// 16-byte chunks are shared out 128 at a time, two per lane in flight, every load of a lane before its first store: a wave
+// pays one round trip for the maps (hidden behind the previous span) and one per 128 live chunks, wherever in the span
+// they lie.  A span with no live row costs nothing more; one with more than a few live rows skips the list (DENSE_PCT).
+// (Four dwords of each map per lane, spans of 1 024 rows, lost at every warm share: DESIGN_HISTORY.md, "Cold rows".)
+// Which wave takes which span is the caller's business: opt_dense_kernel deals a tensor's spans to the waves of the
+// tensor's workgroups, or -- cold_resident, OptLaunch.prop = 2 -- the spans of all tensors to the waves of one grid.
+typedef float vf4 __attribute__((ext_vector_type(4)));
+typedef long long vl2 __attribute__((ext_vector_type(2)));
+constexpr int COLD_RPL = 4, COLD_SPAN = 64 * COLD_RPL;  // rows per lane (one dword of each map), rows per wave trip
+// Live rows, in per cent of a span, from which the span is walked row by row instead of listed.  Measured with 1, 15,
+// 33, 50 and 100: listing spans that are 15-50 % live cost 8-12 us of ~500 at 60-76 % warm rows, at 15 the launch is
+// level with the loop before from there on and keeps the list's whole gain below (DESIGN_HISTORY.md).
+constexpr int COLD_DENSE_PCT = 15;
+constexpr int COLD_WAVES = 4;  // per workgroup: every launch of these kernels has 256 threads (__launch_bounds__(256))
+
+struct ColdTensor {  // what the loop needs of one tensor (wave-uniform)
+  vf4 *P, *G, *S1, *S2;
+  vl2* A64;  // the deferred totals (form 4), or null
+  uint8_t *gm, *wr;
+  int64_t rows;
+  int csh;   // log2(chunks per row): row_elems / 4 is a power of two (mml_opt_step_dense checks)
+  int emax, acc_shift;
+  bool zg;
+};
+
+template <int WITH_ACC>
+__device__ __forceinline__ ColdTensor cold_tensor(const mml_opt_tensor& T) {
+  ColdTensor X;
+  X.P = reinterpret_cast<vf4*>(T.param);
+  X.G = reinterpret_cast<vf4*>(const_cast<float*>(T.grad));
+  X.S1 = reinterpret_cast<vf4*>(T.state1);
+  X.S2 = reinterpret_cast<vf4*>(T.state2);
+  X.A64 = WITH_ACC ? reinterpret_cast<vl2*>(T.acc64) : nullptr;
+  X.gm = T.grad_marks;
+  X.wr = T.warm_rows;
+  const int rsh = __builtin_ctz((unsigned)T.row_elems);
+  X.rows = T.n >> rsh;
+  X.csh = rsh - 2;
+  X.emax = 1;
+  if (WITH_ACC && X.A64) {  // the unit's exponent as scatter_det_finalize_kernel takes it
+    uint32_t m = 0;
+    for (int w = 0; w < MML_AMAX_WORDS; ++w) m = T.acc_amax[w] > m ? T.acc_amax[w] : m;
+    X.emax = (int)(m >> 23);
+    X.emax = X.emax < 1 ? 1 : (X.emax > 254 ? 254 : X.emax);
+  }
+  X.acc_shift = T.acc_shift;
+  X.zg = T.zero_grads != 0;
+  return X;
+}
+
+// the lane's map bytes of span s: the whole words where all four rows exist, else the bytes below `rows` one by one
+__device__ __forceinline__ void cold_scan(const uint8_t* gm, const uint8_t* wr, int64_t rows, int64_t s, int lane,
+                                          uint32_t& mk, uint32_t& wk) {
+  const int64_t r0 = s * COLD_SPAN + lane * COLD_RPL;
+  mk = wk = 0u;
+  if (r0 + COLD_RPL <= rows) {
+    mk = *reinterpret_cast<const uint32_t*>(gm + r0);
+    wk = *reinterpret_cast<const uint32_t*>(wr + r0);
+  } else {
+#pragma unroll
+    for (int k = 0; k < COLD_RPL; ++k)
+      if (r0 + k < rows) {
+        mk |= (uint32_t)gm[r0 + k] << (8 * k);
+        wk |= (uint32_t)wr[r0 + k] << (8 * k);
+      }
+  }
+}
+
+// Span s of tensor X from the map dwords (mk, wk) cold_scan read for it: map upkeep and the update of its live rows.
+// lst = the wave's list of COLD_SPAN entries in LDS (entry: bits 0-13 row of the span, 14 marked, 15 was warm).
+template <int WITH_ACC>
+__device__ __forceinline__ void cold_span(const mml_opt_hyper& h, const StepConsts& c, bool nt, const ColdTensor& X,
+                                          int64_t s, int lane, uint16_t* lst, uint32_t mk, uint32_t wk) {
+  constexpr int RPL = COLD_RPL, SPAN = COLD_SPAN;
+  const vf4 zero = {0.f, 0.f, 0.f, 0.f};
+  const vl2 lzero = {0, 0};
+  // 0x80 in every byte of x that is not zero
+  auto nz80 = [](uint32_t x) { return (x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u; };
+  auto pack4 = [](uint32_t t) { return ((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u); };
+  const uint32_t lm = pack4(nz80(mk)), wm = pack4(nz80(wk));  // bit k: row k of this lane is marked / warm
+  const uint32_t act = lm | wm;
+  if (__builtin_amdgcn_ballot_w64(act != 0) == 0) return;
+  auto ld = [&](const vf4* q) { return nt ? __builtin_nontemporal_load(q) : *q; };
+  auto st = [&](vf4* q, const vf4& v) {
+    if (nt) __builtin_nontemporal_store(v, q);
+    else *q = v;
+  };
+  const int csh = X.csh;
+  const int64_t rows = X.rows, row0 = s * SPAN;
+  // live rows of the span and, per lane, of the lanes below it: ballots of the bits of the lanes' counts
+  const uint32_t cnt = (uint32_t)__builtin_popcount(act);
+  uint32_t pre = 0;
+  int nlive = 0;
+#pragma unroll
+  for (int bit = 0; (1 << bit) <= RPL; ++bit) {
+    const uint64_t bal = __builtin_amdgcn_ballot_w64(((cnt >> bit) & 1u) != 0);
+    pre += __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u)) << bit;
+    nlive += __builtin_popcountll(bal) << bit;
+  }
+  // A span with that many live rows is walked row by row without the list, dead chunks passed over (the 100 %-warm
+  // stream pays no compaction)
+  const bool dense = nlive * 100 >= SPAN * COLD_DENSE_PCT;
+  if (!dense) {
+    // (the lanes' reads of the previous span's list come before these writes, and these before the reads below:
+    // the LDS serves a wave's instructions in order)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int k = 0; k < RPL; ++k)
+      if ((act >> k) & 1u)
+        lst[pre++] = (uint16_t)((lane * RPL + k) | (((lm >> k) & 1u) << 14) | (((wm >> k) & 1u) << 15));
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  // map upkeep by the bytes' only reader: marks cleared, the marked rows that were cold now warm
+  if (lm) {
+    const int64_t r0 = row0 + lane * RPL;
+    if (r0 + RPL <= rows) {
+      *reinterpret_cast<uint32_t*>(X.gm + r0) = 0u;
+      const uint32_t set = (nz80(mk) & ~nz80(wk)) >> 7;  // 1 in the byte of every marked row that was cold
+      if (set) *reinterpret_cast<uint32_t*>(X.wr + r0) = wk | set;
+    } else {
+#pragma unroll
+      for (int k = 0; k < RPL; ++k)
+        if ((lm >> k) & 1u) {  // (only rows below `rows` were read)
+          X.gm[r0 + k] = 0;
+          if (!((wm >> k) & 1u)) X.wr[r0 + k] = 1;
+        }
+    }
+  }
+  const int items = (dense ? SPAN : nlive) << csh;
+#pragma unroll 1
+  for (int b0 = 0; b0 < items; b0 += 128) {
+    vf4 p[2], a[2], b[2], g[2];
+    vl2 t0[2], t1[2];
+    int64_t jj[2];
+    bool on[2], lv[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int it = b0 + 64 * k + lane;
+      const int ent = it >> csh;
+      on[k] = it < items;
+      uint32_t e;
+      if (dense) {  // (all 256 rows in order; the live and marked bits from the lane that read the row's bytes)
+        const uint32_t src = (uint32_t)__shfl((int)(lm | (act << 16)), (ent / RPL) & 63);
+        on[k] = on[k] && ((src >> (16 + (ent & (RPL - 1)))) & 1u);
+        e = (uint32_t)ent | (((src >> (ent & (RPL - 1))) & 1u) << 14);
+      } else {
+        e = on[k] ? lst[ent] : 0u;
+      }
+      lv[k] = on[k] && ((e >> 14) & 1u);
+      const int64_t j = ((row0 + (int64_t)(e & 0x3fffu)) << csh) | (int64_t)(it & ((1 << csh) - 1));
+      jj[k] = j;
+      p[k] = a[k] = b[k] = g[k] = zero;
+      t0[k] = t1[k] = lzero;
+      if (on[k]) {
+        p[k] = ld(X.P + j);
+        if (X.S1) a[k] = ld(X.S1 + j);
+        if (X.S2) b[k] = ld(X.S2 + j);
+      }
+      if (lv[k]) {
+        if (!X.zg) g[k] = ld(X.G + j);
+        if (WITH_ACC && X.A64) {
+          t0[k] = X.A64[2 * j];
+          t1[k] = X.A64[2 * j + 1];
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      if (!on[k]) continue;
+      const int64_t j = jj[k];
+      vf4 gs = g[k];
+      if (WITH_ACC && X.A64 && lv[k]) {
+        // g + from_fixed(total) for the non-zero totals (the expression of the finalize launch's dst[e] += ...), the
+        // totals it used zeroed again
+        const vl2 u0 = t0[k], u1 = t1[k];
+        if (u0.x) gs.x += from_fixed(u0.x, X.emax, X.acc_shift);
+        if (u0.y) gs.y += from_fixed(u0.y, X.emax, X.acc_shift);
+        if (u1.x) gs.z += from_fixed(u1.x, X.emax, X.acc_shift);
+        if (u1.y) gs.w += from_fixed(u1.y, X.emax, X.acc_shift);
+        if (u0.x | u0.y) X.A64[2 * j] = lzero;
+        if (u1.x | u1.y) X.A64[2 * j + 1] = lzero;
+      }
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {  // (a tensor with a warm map carries no regulariser)
+        float pe = p[k][e], ae = a[k][e], be = b[k][e];
+        opt_update(h, c, pe, gs[e], ae, be);
+        p[k][e] = pe;
+        a[k][e] = ae;
+        b[k][e] = be;
+      }
+      st(X.P + j, p[k]);
+      if (X.S1) st(X.S1 + j, a[k]);
+      if (X.S2) st(X.S2 + j, b[k]);
+      if (h.zero_grad && (g[k].x != 0.f || g[k].y != 0.f || g[k].z != 0.f || g[k].w != 0.f)) X.G[j] = zero;
+    }
+  }
+}
+
+// One grid sized for the chip over the spans of ALL tensors of a marked launch whose tensors all take the loop above
+// (L.blk0[i] = first span of tensor i): wave w of the grid's W takes spans w, w + W, w + 2 W, ... of that index space --
+// strided, so that the hot head of a Zipf table is spread over all waves -- and finds (tensor, span) with scalar code;
+// the tensor's values are loaded again only when the tensor changes.  The next span's map dwords are in flight while
+// this one is worked on, also across a tensor change.  No workgroup waits for another.  The grid is two rounds of the
+// workgroups the chip holds (mml_opt_step_dense): with one, the waves dealt the warm head finish last with nothing behind them.
+template <int WITH_ACC>
+__device__ __forceinline__ void cold_resident(const OptLaunch& L, const StepConsts& c, uint16_t (*live_rows)[COLD_SPAN]) {
+  const mml_opt_hyper& h = L.h;
+  const bool nt = (L.variant & 1) != 0;
+  const int lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (scalar: the span loop is wave-uniform)
+  uint16_t* const lst = live_rows[wv];
+  const int nspan = L.blk0[L.n], nwv = (int)gridDim.x * COLD_WAVES;
+  int s = (int)blockIdx.x * COLD_WAVES + wv;
+  if (s >= nspan) return;
+  int ti = 0;
+  while (s >= L.blk0[ti + 1]) ++ti;  // (s < blk0[n]: stops at a tensor that has spans)
+  ColdTensor X = cold_tensor<WITH_ACC>(L.t[ti]);
+  uint32_t mk, wk;
+  cold_scan(X.gm, X.wr, X.rows, s - L.blk0[ti], lane, mk, wk);
+  for (;;) {  // (wave-uniform)
+    const int sn = s + nwv;
+    int tn = ti;
+    uint32_t mkn = 0, wkn = 0;
+    if (sn < nspan) {
+      while (sn >= L.blk0[tn + 1]) ++tn;
+      const mml_opt_tensor& Tn = L.t[tn];
+      cold_scan(Tn.grad_marks, Tn.warm_rows, Tn.n >> __builtin_ctz((unsigned)Tn.row_elems), sn - L.blk0[tn], lane, mkn,
+                wkn);
+    }
+    cold_span<WITH_ACC>(h, c, nt, X, s - L.blk0[ti], lane, lst, mk, wk);
+    if (sn >= nspan) break;
+    if (tn != ti) {
+      ti = tn;
+      X = cold_tensor<WITH_ACC>(L.t[ti]);
+    }
+    s = sn;
+    mk = mkn;
+    wk = wkn;
+  }
+}
+
 // blockIdx.y = tensor, blockIdx.x strides over that tensor in float4 chunks.
 // STREAM only names the launch (profilers see two symbols): true = a launch that streams >= 2^24 parameters through
 // HBM (the dense table update), false = everything else (MLP parameters, small tables).  Same code.
@@ -101,7 +375,7 @@ template <bool STREAM, int PATH, int U>
 __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
   // (workgroup-uniform: scalar loads and compares)
   int ti = blockIdx.y, nblk = gridDim.x, lblk = blockIdx.x;
-  if (L.prop) {
+  if (L.prop == 1) {
     ti = 0;
     while (ti + 1 < L.n && (int)blockIdx.x >= L.blk0[ti + 1]) ++ti;
     nblk = L.blk0[ti + 1] - L.blk0[ti];
@@ -109,7 +383,13 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
   }
   const mml_opt_tensor& T = L.t[ti];
   const mml_opt_hyper& h = L.h;
-  const StepConsts c = step_consts(h);
+  const StepConsts c = step_consts(h, L.sc);
+  // the wave-compacted loop's lists of live rows, one per wave (cold_span)
+  __shared__ uint16_t live_rows[(PATH == OPT_MARK_U || PATH == OPT_MARK_ACC_U) ? COLD_WAVES : 1][COLD_SPAN];
+  if ((PATH == OPT_MARK_U || PATH == OPT_MARK_ACC_U) && L.prop == 2) {  // (the launch's switch)
+    cold_resident<PATH == OPT_MARK_ACC_U>(L, c, live_rows);
+    return;
+  }
   const int64_t n4 = T.n >> 2;
   const bool vec = aligned16(T.param) && aligned16(T.grad) && (!T.state1 || aligned16(T.state1)) &&
                    (!T.state2 || aligned16(T.state2));
@@ -237,150 +517,20 @@ __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
     const bool compact = !(L.variant & 8) && wr &&
                          ((reinterpret_cast<uintptr_t>(gm) | reinterpret_cast<uintptr_t>(wr)) & 3) == 0;
     if ((PATH == OPT_MARK_U || PATH == OPT_MARK_ACC_U) && compact && !skip) {
-      // Mostly-cold stream, wave-compacted.  A wave owns spans of SPAN consecutive rows, dealt by its number in the tensor's
-      // workgroups; lane l reads the marks and the warm bytes of rows [4 l, 4 l + 4) of the span with one aligned dword
-      // load each (the next span's are in flight while this one is worked on) and is the only reader and writer of those map
-      // bytes in the launch.  The live rows (marked or warm) are listed in the wave's LDS list -- exclusive prefix sum of
-      // the lanes' counts from ballots of the counts' bits, no atomics, no workgroup barrier -- and the list's 16-byte
-      // chunks are shared out 128 at a time, two per lane in flight, every load of a lane before its first store: a wave
-      // pays one round trip for the maps (hidden behind the previous span) and one per 128 live chunks, wherever in the
-      // span they lie.  A span with no live row costs nothing more; one with more than a few live rows skips the list (DENSE_PCT).
-      // (Four dwords of each map per lane, spans of 1 024 rows, lost at every warm share: DESIGN_HISTORY.md, "Cold rows".)
-      constexpr int RPL = 4, SPAN = 64 * RPL;  // rows per lane (one dword of each map), rows per wave trip
-      // Live rows, in per cent of a span, from which the span is walked row by row instead of listed.  Measured with 1, 15,
-      // 33, 50 and 100: listing spans that are 15-50 % live cost 8-12 us of ~500 at 60-76 % warm rows, at 15 the launch is
-      // level with the loop before from there on and keeps the list's whole gain below (DESIGN_HISTORY.md).
-      constexpr int DENSE_PCT = 15;
-      constexpr int WAVES = 4;  // per workgroup: every launch of this kernel has 256 threads (__launch_bounds__(256))
-      __shared__ uint16_t live_rows[WAVES][SPAN];  // entry: bits 0-13 row of the span, 14 marked, 15 was warm
+      // The wave-compacted loop (cold_span, above) on this tensor's own workgroups: its spans are dealt to their waves by the
+      // wave's number among them.  (The grid of a launch some tensor of which does not qualify for cold_resident, and
+      // the A/B arm mml_opt_hyper.cold_loop = 2.)
       const int lane = threadIdx.x & 63;
       const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (scalar: the span loop is wave-uniform)
-      uint16_t* const lst = live_rows[wv];
-      const int csh = rsh - 2;  // log2(chunks per row): row_elems / 4 is a power of two (mml_opt_step_dense checks)
-      const int64_t rows = T.n >> rsh;
-      const int64_t nspan = (rows + SPAN - 1) / SPAN, nwv = (int64_t)nblk * WAVES;
-      // 0x80 in every byte of x that is not zero
-      auto nz80 = [](uint32_t x) { return (x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u; };
-      auto pack4 = [](uint32_t t) { return ((t >> 7) & 1u) | ((t >> 14) & 2u) | ((t >> 21) & 4u) | ((t >> 28) & 8u); };
-      // the lane's map bytes of span s: the whole words where all four rows exist, else the bytes below `rows` one by one
-      auto scan = [&](int64_t s, uint32_t& mk, uint32_t& wk) {
-        const int64_t r0 = s * SPAN + lane * RPL;
-        mk = wk = 0u;
-        if (r0 + RPL <= rows) {
-          mk = *reinterpret_cast<const uint32_t*>(gm + r0);
-          wk = *reinterpret_cast<const uint32_t*>(wr + r0);
-        } else {
-#pragma unroll
-          for (int k = 0; k < RPL; ++k)
-            if (r0 + k < rows) {
-              mk |= (uint32_t)gm[r0 + k] << (8 * k);
-              wk |= (uint32_t)wr[r0 + k] << (8 * k);
-            }
-        }
-      };
-      int64_t s = (int64_t)lblk * WAVES + wv;
+      const ColdTensor X = cold_tensor<PATH == OPT_MARK_ACC_U>(T);
+      const int64_t nspan = (X.rows + COLD_SPAN - 1) / COLD_SPAN, nwv = (int64_t)nblk * COLD_WAVES;
+      int64_t s = (int64_t)lblk * COLD_WAVES + wv;
       uint32_t mk = 0, wk = 0;
-      if (s < nspan) scan(s, mk, wk);
+      if (s < nspan) cold_scan(gm, wr, X.rows, s, lane, mk, wk);
       for (; s < nspan; s += nwv) {  // (wave-uniform)
         uint32_t mkn = 0, wkn = 0;
-        if (s + nwv < nspan) scan(s + nwv, mkn, wkn);
-        const uint32_t lm = pack4(nz80(mk)), wm = pack4(nz80(wk));  // bit k: row k of this lane is marked / warm
-        const uint32_t act = lm | wm;
-        if (__builtin_amdgcn_ballot_w64(act != 0) != 0) {
-          const int64_t row0 = s * SPAN;
-          // live rows of the span and, per lane, of the lanes below it: ballots of the bits of the lanes' counts
-          const uint32_t cnt = (uint32_t)__builtin_popcount(act);
-          uint32_t pre = 0;
-          int nlive = 0;
-#pragma unroll
-          for (int bit = 0; (1 << bit) <= RPL; ++bit) {
-            const uint64_t bal = __builtin_amdgcn_ballot_w64(((cnt >> bit) & 1u) != 0);
-            pre += __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u)) << bit;
-            nlive += __builtin_popcountll(bal) << bit;
-          }
-          // A span with that many live rows is walked row by row without the list, dead chunks passed over (the 100 %-warm
-          // stream pays no compaction)
-          const bool dense = nlive * 100 >= SPAN * DENSE_PCT;
-          if (!dense) {
-            // (the lanes' reads of the previous span's list come before these writes, and these before the reads below:
-            // the LDS serves a wave's instructions in order)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int k = 0; k < RPL; ++k)
-              if ((act >> k) & 1u)
-                lst[pre++] = (uint16_t)((lane * RPL + k) | (((lm >> k) & 1u) << 14) | (((wm >> k) & 1u) << 15));
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-          }
-          // map upkeep by the bytes' only reader: marks cleared, the marked rows that were cold now warm
-          if (lm) {
-            const int64_t r0 = row0 + lane * RPL;
-            if (r0 + RPL <= rows) {
-              *reinterpret_cast<uint32_t*>(gm + r0) = 0u;
-              const uint32_t set = (nz80(mk) & ~nz80(wk)) >> 7;  // 1 in the byte of every marked row that was cold
-              if (set) *reinterpret_cast<uint32_t*>(wr + r0) = wk | set;
-            } else {
-#pragma unroll
-              for (int k = 0; k < RPL; ++k)
-                if ((lm >> k) & 1u) {  // (only rows below `rows` were read)
-                  gm[r0 + k] = 0;
-                  if (!((wm >> k) & 1u)) wr[r0 + k] = 1;
-                }
-            }
-          }
-          const int items = (dense ? SPAN : nlive) << csh;
-#pragma unroll 1
-          for (int b0 = 0; b0 < items; b0 += 128) {
-            f4 p[2], a[2], b[2], g[2];
-            l2 t0[2], t1[2];
-            int64_t jj[2];
-            bool on[2], lv[2];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-              const int it = b0 + 64 * k + lane;
-              const int ent = it >> csh;
-              on[k] = it < items;
-              uint32_t e;
-              if (dense) {  // (all 256 rows in order; the live and marked bits from the lane that read the row's bytes)
-                const uint32_t src = (uint32_t)__shfl((int)(lm | (act << 16)), (ent / RPL) & 63);
-                on[k] = on[k] && ((src >> (16 + (ent & (RPL - 1)))) & 1u);
-                e = (uint32_t)ent | (((src >> (ent & (RPL - 1))) & 1u) << 14);
-              } else {
-                e = on[k] ? lst[ent] : 0u;
-              }
-              lv[k] = on[k] && ((e >> 14) & 1u);
-              const int64_t j = ((row0 + (int64_t)(e & 0x3fffu)) << csh) | (int64_t)(it & ((1 << csh) - 1));
-              jj[k] = j;
-              p[k] = a[k] = b[k] = g[k] = zero;
-              t0[k] = t1[k] = lzero;
-              if (on[k]) {
-                p[k] = ld(P + j);
-                if (S1) a[k] = ld(S1 + j);
-                if (S2) b[k] = ld(S2 + j);
-              }
-              if (lv[k]) {
-                if (!zg) g[k] = ld(G + j);
-                if (PATH == OPT_MARK_ACC_U && A64) {
-                  t0[k] = A64[2 * j];
-                  t1[k] = A64[2 * j + 1];
-                }
-              }
-            }
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-              if (!on[k]) continue;
-              const int64_t j = jj[k];
-              f4 gs = g[k];
-              if (PATH == OPT_MARK_ACC_U && A64 && lv[k]) add_totals(gs, t0[k], t1[k], j);
-              one(p[k], gs, a[k], b[k]);
-              st(P + j, p[k]);
-              if (S1) st(S1 + j, a[k]);
-              if (S2) st(S2 + j, b[k]);
-              if (h.zero_grad && (g[k].x != 0.f || g[k].y != 0.f || g[k].z != 0.f || g[k].w != 0.f)) G[j] = zero;
-            }
-          }
-        }
+        if (s + nwv < nspan) cold_scan(gm, wr, X.rows, s + nwv, lane, mkn, wkn);
+        cold_span<PATH == OPT_MARK_ACC_U>(h, c, nt, X, s, lane, live_rows[wv], mk, wk);
         mk = mkn;
         wk = wkn;
       }
@@ -578,7 +728,8 @@ __global__ __launch_bounds__(256) void opt_flat_kernel(const OptLaunch L) {
   for (int i = threadIdx.x; i < L.n; i += 256) ts[i] = L.t[i];
   for (int i = threadIdx.x; i <= L.n; i += 256) pre[i] = L.chunk0[i];
   const mml_opt_hyper& h = L.h;
-  const StepConsts c = step_consts(h);  // (contains the __syncthreads that also publishes ts / pre)
+  __syncthreads();  // (publishes ts / pre)
+  const StepConsts c = step_consts(h, L.sc);
   const int64_t total = pre[L.n];
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t ch = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; ch < total; ch += stride) {
@@ -645,6 +796,7 @@ struct RowsLaunch {
   int32_t cap;
   int32_t pad_;
   mml_opt_hyper h;
+  const mml_opt_step_consts* sc;  // as OptLaunch.sc
 };
 
 // field of a global row id: bisection of an LDS copy of rowbase (a per-lane scan of the kernel-argument array is a
@@ -677,7 +829,8 @@ __global__ __launch_bounds__(256) void opt_rows_kernel(const RowsLaunch L) {
     tab_l[i] = L.tab[i]; grad_l[i] = L.grad[i]; s1_l[i] = L.s1[i]; s2_l[i] = L.s2[i]; seen_l[i] = L.seen[i];
     last_l[i] = L.last[i];
   }
-  const StepConsts c = step_consts(h);  // (contains the __syncthreads that publishes rb_lds)
+  __syncthreads();  // (publishes rb_lds and the descriptors)
+  const StepConsts c = step_consts(h, L.sc);
   int32_t cnt = *L.touched_count;
   if (cnt > L.cap) cnt = L.cap;
   const int per_row = L.E / VEC;
@@ -827,6 +980,20 @@ __global__ __launch_bounds__(256) void opt_catchup_kernel(const CatchupLaunch L)
 
 __global__ void counter_kernel(int32_t* c, int32_t delta, int32_t reset) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *c = reset ? 0 : (*c + delta);
+}
+
+// the counter's bump and the new step's constants in one launch (mml_opt_step_begin); the step is written last: it is
+// what tells a reader whose constants these are
+__global__ void step_begin_kernel(int32_t* c, int32_t delta, const mml_opt_hyper h, mml_opt_step_consts* out) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const int t = *c + delta;
+    *c = t;
+    const StepConsts k = step_consts_of(h, t);
+    out->step_size = k.step_size;
+    out->inv_bc2s = k.inv_bc2s;
+    out->pad_ = 0;
+    out->step = t;
+  }
 }
 
 // ---- elementwise -------------------------------------------------------------------------------------
@@ -1107,15 +1274,83 @@ static int check_hyper(const mml_opt_hyper* h, const char* who) {
   return MML_OK;
 }
 
+// ---- step constants kept on the device (mml_opt_step_begin) ----------------------------------------------------------
+// step counter -> the buffer its constants are in and the hyper values they were computed under.  A handful of entries
+// (one per optimizer alive in the process), looked up on the host by every optimizer launch.
+namespace {
+struct StepBinding {
+  const int32_t* step_dev;
+  const mml_opt_step_consts* consts;
+  int32_t kind;
+  float lr, beta1, beta2;
+};
+std::mutex g_step_mu;
+std::vector<StepBinding> g_step_bindings;
+
+void step_unbind(const int32_t* step_dev) {
+  std::lock_guard<std::mutex> lk(g_step_mu);
+  for (size_t i = 0; i < g_step_bindings.size(); ++i)
+    if (g_step_bindings[i].step_dev == step_dev) {
+      g_step_bindings[i] = g_step_bindings.back();
+      g_step_bindings.pop_back();
+      return;
+    }
+}
+
+// the constants' buffer for a launch under `h`, or null (then every workgroup computes them)
+const mml_opt_step_consts* step_bound(const mml_opt_hyper& h) {
+  if (!h.step_dev) return nullptr;
+  std::lock_guard<std::mutex> lk(g_step_mu);
+  for (const StepBinding& b : g_step_bindings)
+    if (b.step_dev == h.step_dev)
+      return (b.kind == h.kind && b.lr == h.lr && b.beta1 == h.beta1 && b.beta2 == h.beta2) ? b.consts : nullptr;
+  return nullptr;
+}
+
+int device_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, nn = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
+      nn = 256;
+    cus = nn;
+  }
+  return cus;
+}
+}  // namespace
+
+extern "C" int mml_opt_step_begin(int32_t* step_dev, int32_t delta, const mml_opt_hyper* hyper,
+                                  mml_opt_step_consts* consts, mml_stream_t stream) {
+  MML_REQUIRE(hyper, "mml_opt_step_begin: null hyper");
+  MML_REQUIRE(hyper->kind >= MML_OPT_SGD && hyper->kind <= MML_OPT_RMSPROP, "mml_opt_step_begin: unknown optimizer kind %d",
+              hyper->kind);
+  MML_REQUIRE(step_dev && consts && aligned16(consts), "mml_opt_step_begin: needs a counter and a 16-byte aligned buffer");
+  MML_LAUNCH(step_begin_kernel, dim3(1), dim3(64), 0, to_stream(stream), step_dev, delta, *hyper, consts);
+  const int rc = check_launch("mml_opt_step_begin");
+  if (rc) return rc;
+  step_unbind(step_dev);
+  std::lock_guard<std::mutex> lk(g_step_mu);
+  g_step_bindings.push_back(StepBinding{step_dev, consts, hyper->kind, hyper->lr, hyper->beta1, hyper->beta2});
+  return MML_OK;
+}
+
+extern "C" int mml_opt_step_unbind(const int32_t* step_dev) {
+  step_unbind(step_dev);
+  return MML_OK;
+}
+
 extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, const mml_opt_hyper* hyper,
                                   mml_stream_t stream) {
   int rc = check_hyper(hyper, "mml_opt_step_dense");
   if (rc) return rc;
+  const mml_opt_step_consts* const bound = step_bound(*hyper);
   MML_REQUIRE(n >= 0 && (n == 0 || tensors), "mml_opt_step_dense: bad tensor array");
   int i = 0;
   while (i < n) {
     OptLaunch L{};
     L.h = *hyper;
+    L.sc = bound;
     int64_t total = 0, chunks = 0;
     while (i < n && L.n < MML_MAX_OPT_TENSORS) {
       const mml_opt_tensor& t = tensors[i];
@@ -1183,8 +1418,9 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
       if (hyper->max_blocks > 0 && bx * L.n > hyper->max_blocks) bx = cdiv(hyper->max_blocks, L.n);
       dim3 grid((unsigned)bx, (unsigned)L.n);
       // Workgroups per tensor at most.  With a warm map on every tensor most of the stream is passed over and a workgroup's
-      // fixed cost (tensor search, bias corrections, magnitude words) is what is left of a short one: MMLREC_OPT_COLD_WGS
-      // (lab knob) caps them lower.
+      // fixed cost (tensor search, magnitude words, unbound bias corrections) is what is left of a short one:
+      // MMLREC_OPT_COLD_WGS (lab knob) caps them lower.  Measured side by side at 3.8 % warm rows, 2 048 / 1 024 / 512:
+      // 129.8 / 119.2 / 116.1 us -- which is why a launch that qualifies leaves this grid altogether (`resident`, below).
       bool all_warm = true;
       for (int k = 0; k < L.n; ++k) all_warm = all_warm && L.t[k].warm_rows;
       static int cold_wgs = -1;
@@ -1193,7 +1429,21 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
         cold_wgs = e ? atoi(e) : 256 * 8;
         if (cold_wgs < 1 || cold_wgs > 256 * 8) cold_wgs = 256 * 8;
       }
-      const int64_t wg_cap = all_warm ? cold_wgs : 256 * 8;
+      // One resident grid (cold_resident): the launch runs a kernel with the wave-compacted loop (forms 3 / 4), every
+      // tensor carries a warm map with word-aligned map pointers, and the switch asks for it.  Sized for the chip -- twice
+      // the kernel's workgroups that fit a compute unit (4 at its register count: two rounds, so that a workgroup whose
+      // spans hold the warm head of a Zipf table is made up for by the late starters; cold_loop = 3: one round; lab knob
+      // MMLREC_OPT_RESIDENT_PER_CU) x compute units -- and never above what the launch gets otherwise (max_blocks
+      // included).  MMLREC_OPT_COLD_WGS means nothing here.
+      bool resident = all_warm && all_gm && (any_acc || (L.variant & 4)) && (hyper->cold_loop == 0 || hyper->cold_loop == 3);
+      int64_t nspan = 0;
+      for (int k = 0; k < L.n && resident; ++k) {
+        const mml_opt_tensor& t = L.t[k];
+        resident = ((reinterpret_cast<uintptr_t>(t.grad_marks) | reinterpret_cast<uintptr_t>(t.warm_rows)) & 3) == 0;
+        nspan += cdiv(t.n / t.row_elems, COLD_SPAN);
+      }
+      resident = resident && nspan < ((int64_t)1 << 30);  // (span numbers are 32-bit in the kernel)
+      const int64_t wg_cap = (all_warm && !resident) ? cold_wgs : 256 * 8;
       if (many) {
         // every tensor gets what a launch of its own would give it (one workgroup per 256 chunks, at most 2 048): the huge
         // tables stream exactly as in their four-tensor launch, the small ones add a few hundred workgroups (the caller
@@ -1218,6 +1468,25 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
         L.blk0[L.n] = (int32_t)at;
         L.prop = 1;
         grid = dim3((unsigned)at, 1);
+      }
+      if (resident) {
+        int64_t wgs = (int64_t)grid.x * grid.y;
+        static int per_cu = -1;
+        if (per_cu < 0) {
+          const char* e = getenv("MMLREC_OPT_RESIDENT_PER_CU");
+          per_cu = e ? atoi(e) : 8;
+          if (per_cu < 1 || per_cu > 64) per_cu = 8;
+        }
+        const int64_t fit = (int64_t)(hyper->cold_loop == 3 ? 4 : per_cu) * device_cus();
+        if (wgs > fit) wgs = fit;
+        int64_t at = 0;
+        for (int k = 0; k < L.n; ++k) {
+          L.blk0[k] = (int32_t)at;
+          at += cdiv(L.t[k].n / L.t[k].row_elems, COLD_SPAN);
+        }
+        L.blk0[L.n] = (int32_t)at;
+        L.prop = 2;
+        grid = dim3((unsigned)(wgs < 1 ? 1 : wgs), 1);
       }
       static int u_mark = -1;
       if (u_mark < 0) {
@@ -1318,6 +1587,7 @@ extern "C" int mml_opt_step_rows(float* const* tables, float* const* grad_tables
   }
   L.rowbase[F] = rowbase[F];
   L.F = F; L.E = E; L.touched = touched; L.touched_count = touched_count; L.cap = touched_cap; L.h = *hyper;
+  L.sc = step_bound(*hyper);
   // the row count lives on the device: size the grid for the capacity, surplus workgroups exit at once
   bool vec = (E % 4 == 0);
   for (int f = 0; f < F && vec; ++f)
@@ -1331,6 +1601,7 @@ extern "C" int mml_opt_step_rows(float* const* tables, float* const* grad_tables
 
 extern "C" int mml_counter_update(int32_t* counter, int32_t delta, int32_t reset, mml_stream_t stream) {
   MML_REQUIRE(counter, "mml_counter_update: null counter");
+  step_unbind(counter);  // (constants kept for this counter by mml_opt_step_begin would go stale)
   MML_LAUNCH(counter_kernel, dim3(1), dim3(64), 0, to_stream(stream), counter, delta, reset);
   return check_launch("mml_counter_update");
 }

@@ -1036,6 +1036,24 @@ def counter_update(counter, delta=1, reset=False):
     L.check(L.load().mml_counter_update(counter.data_ptr(), int(delta), int(reset), _stream()), "mml_counter_update")
 
 
+def step_counter(device):
+    """(step_dev, consts): a device step counter and, in the same allocation (so neither outlives the other), the 16
+    aligned bytes mml_opt_step_begin keeps the step's constants in (mml_opt_step_consts)."""
+    buf = torch.zeros(8, dtype=torch.int32, device=device)
+    return buf[:1], buf[4:8]
+
+
+def opt_step_begin(step_dev, hyper, consts, delta=1):
+    """*step_dev += delta and the new step's constants into `consts` in one launch; from here on the optimizer launches
+    under step_dev and hyper's kind / lr / betas read them there (include/mmlrec.h: mml_opt_step_begin)."""
+    L.check(L.load().mml_opt_step_begin(step_dev.data_ptr(), int(delta), C.byref(hyper), consts.data_ptr(), _stream()),
+            "mml_opt_step_begin")
+
+
+def opt_step_unbind(step_dev):
+    L.check(L.load().mml_opt_step_unbind(step_dev.data_ptr()), "mml_opt_step_unbind")
+
+
 def auc_segments(pred, y, seg):
     """AUC of every (segment of `seg` rows, column) pair of device matrices pred / y [n, C] -> float64 [ceil(n/seg), C]
     (NaN where a segment holds one class).  Device counterpart of the per-step sklearn roc_auc_score of the reference

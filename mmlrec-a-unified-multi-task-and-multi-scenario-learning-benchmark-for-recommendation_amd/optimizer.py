@@ -57,6 +57,14 @@ class OptKnobs:
     # MMLREC_OPT_COLD_COMPACT=0: the launch walks a warm map byte by byte, chunk by chunk, as before the wave-compacted loop
     # (mml_opt_hyper.cold_loop = 1; A/B switch, the same bits either way)
     cold_compact: bool = True
+    # MMLREC_OPT_RESIDENT: the grid of the wave-compacted loop when every tensor of the launch qualifies for it.  1 = one
+    # grid sized for the chip, the spans of all tensors dealt to its waves (mml_opt_hyper.cold_loop = 0); 0 = the
+    # workgroups of each tensor, as before that grid (cold_loop = 2); 2 = the chip-sized grid with half the workgroups,
+    # one round of them (cold_loop = 3).  A/B switch, the same bits in all three.
+    resident: int = 1
+    # MMLREC_OPT_STEP_CONSTS=0: the step starts with the plain counter bump and every workgroup of the optimizer launches
+    # computes Adam's bias terms itself, as before mml_opt_step_begin (A/B switch, the same bits either way)
+    step_consts: bool = True
 
     @classmethod
     def from_env(cls, env=None):
@@ -71,7 +79,9 @@ class OptKnobs:
                    variant=int(env.get("MMLREC_OPT_VARIANT", "0")),
                    scatter_old=bool(env.get("MMLREC_SCATTER_OLD")),
                    cold_rows=env.get("MMLREC_OPT_COLD_ROWS", "1") != "0",
-                   cold_compact=env.get("MMLREC_OPT_COLD_COMPACT", "1") != "0")
+                   cold_compact=env.get("MMLREC_OPT_COLD_COMPACT", "1") != "0",
+                   resident=int(env.get("MMLREC_OPT_RESIDENT", "1")),
+                   step_consts=env.get("MMLREC_OPT_STEP_CONSTS", "1") != "0")
 
 
 TABLE_UPDATES = ("dense_exact", "sparse_rows", "lazy_exact")
@@ -192,9 +202,23 @@ def launch_trusts_warm_map(kind, marked, table_reg, knobs, sharded=False):
 
 
 def cold_loop_of(knobs):
-    """mml_opt_hyper.cold_loop of the dense table launches: 0 = the wave-compacted loop over a warm map, 1 = the loop
-    before it (knobs.cold_compact off).  A launch without a warm map does not look at the field."""
-    return 0 if knobs.cold_compact else 1
+    """mml_opt_hyper.cold_loop of the dense table launches: 0 = the wave-compacted loop over a warm map on one grid sized
+    for the chip, 1 = the loop before it (knobs.cold_compact off), 2 = the compacted loop on each tensor's own
+    workgroups (knobs.resident = 0), 3 = as 0 with half the workgroups (knobs.resident = 2).  A launch without a warm
+    map does not look at the field."""
+    if not knobs.cold_compact:
+        return 1
+    return {0: 2, 2: 3}.get(knobs.resident, 0)
+
+
+def step_pre_entry(lib, step_dev_ptr, consts_ptr, hyper):
+    """The entry a step's call list starts with.  With a constants buffer (consts_ptr): mml_opt_step_begin, ONE launch
+    that bumps the device step counter and leaves the step's constants (Adam's bias terms) where the optimizer launches
+    under `hyper`'s kind / lr / betas read them; without one (None): the plain counter bump, and every workgroup
+    computes them.  One entry either way."""
+    if consts_ptr is None:
+        return (lib.mml_counter_update, (step_dev_ptr, 1, 0))
+    return (lib.mml_opt_step_begin, (step_dev_ptr, 1, C.byref(hyper), consts_ptr))
 
 
 class TableRows:
@@ -374,10 +398,17 @@ class Optimizer:
         self.last = None   # lazy_exact: per-table int32 [V] "row is current as of step"
         self.dirty = False
         dev = store.device
-        self.step_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.step_dev, self.step_consts = ops.step_counter(dev)  # (the counter and the step's constants: one allocation)
         self.state = _OptState(store, kind)  # moments are allocated when a tensor is first updated
         self.warm = self.state.warm          # table name -> byte per row: may the row's moments be non-zero?
         self.steps_done = 0
+
+    def __del__(self):
+        # the library's (counter -> constants) entry goes with the buffers it names
+        try:
+            ops.opt_step_unbind(self.step_dev)
+        except Exception:  # (interpreter shutdown: nothing left to tidy)
+            pass
 
     def warm_map(self, name):
         """The warm map of table `name` for a launch that honours it (launch_trusts_warm_map), or None when the table's
@@ -418,7 +449,10 @@ class Optimizer:
         update (may run beside the forward / backward), 'mlp': dense MLP update, 'tables': table update (+ touched-list
         reset)} so a trainer can put them on different streams."""
         knobs = OptKnobs.from_env()
-        pre = [(L.load().mml_counter_update, (self.step_dev.data_ptr(), 1, 0))]
+        hyper = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev, zero_grad=False)
+        plan.keep.append(hyper)
+        pre = [step_pre_entry(L.load(), self.step_dev.data_ptr(),
+                              self.step_consts.data_ptr() if knobs.step_consts else None, hyper)]
         if self.table_update == "lazy_exact":
             pre += self._lazy_pre_calls(plan)
         split_dense = bool(split_dense) and self.can_split_dense(plan)
@@ -430,8 +464,6 @@ class Optimizer:
         if treg and self.table_update != "dense_exact":
             raise NotImplementedError("l2_reg_embedding / l1 on the tables makes every row's gradient non-zero: use "
                                       "table_update='dense_exact' (the reference's own dense optimizer)")
-        hyper = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev, zero_grad=False)
-        plan.keep.append(hyper)
         mlp = self._mlp_calls(plan, reg, hyper)
         early, tables = [], []
         if names and self.table_update == "dense_exact":

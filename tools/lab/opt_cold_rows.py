@@ -6,7 +6,10 @@ row for the last line; the first line is the launch without a map (every row upd
 more batch, as the scatter of a step does, and runs behind a 1 GiB pass that empties the caches; HIP events around the
 launch, median of `reps` replays after `warm-up` ones.
 usage: python tools/lab/opt_cold_rows.py [reps [warm-up [lines]]]   lines: e.g. 4,every (default 4,30,300,1000,every);
-MMLREC_LIB=<library> times another build of the kernel (-DMML_OPT_COLD_CB=...) or the library of another commit."""
+MMLREC_LIB=<library> times another build of the kernel (-DMML_OPT_COLD_CB=...) or the library of another commit;
+MMLREC_OPT_COLD_COMPACT / MMLREC_OPT_RESIDENT pick the loop and its grid as they do in a training step (optimizer.cold_loop_of:
+RESIDENT=0 the workgroups of each tensor, 2 the chip-sized grid halved), MMLREC_OPT_STEP_CONSTS=0 has every workgroup compute
+Adam's bias terms."""
 import os
 import sys
 
@@ -14,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import torch  # noqa: E402
 
 import mmlrec_amd  # noqa: F401,E402
-from mmlrec_amd import ops, workloads as W  # noqa: E402
+from mmlrec_amd import ops, optimizer as O, workloads as W  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 25
 warmup = int(sys.argv[2]) if len(sys.argv) > 2 else 5
@@ -55,7 +58,12 @@ warm = [torch.zeros(v, dtype=torch.uint8, device=dev) for v in vocab]
 slot = ops.amax_slots(1, dev)[0]
 shift = ops.scatter_det_shift(B)
 junk = torch.empty(1 << 28, dtype=torch.float32, device=dev)
-hyper = ops.make_hyper("adam", 1e-3, step=7, zero_grad=True, max_blocks=1 << 20)
+knobs = O.OptKnobs.from_env()
+# as in a training step the launch reads the step's constants from the buffer mml_opt_step_begin fills before it (outside the
+# timed region); MMLREC_OPT_STEP_CONSTS=0: a host step, every workgroup computes them
+step_dev, consts = ops.step_counter(dev) if knobs.step_consts else (None, None)
+hyper = ops.make_hyper("adam", 1e-3, step=7, step_dev=step_dev, zero_grad=True, max_blocks=1 << 20,
+                       cold_loop=O.cold_loop_of(knobs))
 params = float(sum(vocab)) * E
 
 
@@ -72,6 +80,8 @@ def timed(with_map, maps):
                 warm[f].copy_(maps[f])
             marks[f][zipf_rows(v, B)] = 1
         junk.add_(1.0)
+        if step_dev is not None:
+            ops.opt_step_begin(step_dev, hyper, consts)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         launch(with_map)
