@@ -11,7 +11,7 @@ import torch  # noqa: F401,E402
 from . import build as _build
 
 MAX_FIELDS, MAX_GROUP, MAX_SRC, MAX_EXPERTS, MAX_GATES, MAX_HEADS, MAX_OPT_TENSORS = 64, 16, 8, 16, 8, 8, 32
-# mml_opt_step_dense's launch rule (csrc/optim_ew.hip), mirrored here ONCE for everything that predicts it: a call of at
+# mml_opt_step_dense's launch rule (csrc/opt_plan.hpp), mirrored here ONCE for everything that predicts it: a call of at
 # least OPT_STREAM_MIN_PARAMS parameters streams (opt_dense_kernel) when it holds at most OPT_STREAM_MAX_TENSORS tensors
 # or every tensor carries gradient marks; everything else is one opt_flat_kernel launch, which refuses marks.  A table
 # counts as huge -- worth a streaming launch of its own group -- from OPT_HUGE_MIN_PARAMS parameters on.

@@ -1,9 +1,9 @@
 // K8 optimizers (torch.optim.{SGD,Adam,Adagrad,RMSprop} with their defaults, as built by
-// BaseModel._get_optim, model/basemodel.py:569-584, and stepped at :313) and the K6/K7 elementwise helpers for
-// STAR (model/utils.py:214-218) and PepNet (model/pepnet.py:31-32, :72-78, :139-140).
+// BaseModel._get_optim, model/basemodel.py:569-584, and stepped at :313).
 // All of these are pure streaming kernels: 16-byte accesses per lane, grid-stride, HBM-bound.
 #include "common.hpp"
 #include "fold_fixed.hpp"
+#include "opt_plan.hpp"
 
 #include <stdlib.h>
 
@@ -123,7 +123,8 @@ __device__ __forceinline__ float reg_grad(float g, float p, float l1, float l2) 
 // tensor's workgroups, or -- cold_resident, OptLaunch.prop = 2 -- the spans of all tensors to the waves of one grid.
 typedef float vf4 __attribute__((ext_vector_type(4)));
 typedef long long vl2 __attribute__((ext_vector_type(2)));
-constexpr int COLD_RPL = 4, COLD_SPAN = 64 * COLD_RPL;  // rows per lane (one dword of each map), rows per wave trip
+// (COLD_RPL rows per lane -- one dword of each map -- and COLD_SPAN rows per wave trip: opt_plan.hpp, whose resident grid
+// counts spans)
 // Live rows, in per cent of a span, from which the span is walked row by row instead of listed.  Measured with 1, 15,
 // 33, 50 and 100: listing spans that are 15-50 % live cost 8-12 us of ~500 at 60-76 % warm rows, at 15 the launch is
 // level with the loop before from there on and keeps the list's whole gain below (DESIGN_HISTORY.md).
@@ -359,8 +360,8 @@ __device__ __forceinline__ void cold_resident(const OptLaunch& L, const StepCons
 }
 
 // blockIdx.y = tensor, blockIdx.x strides over that tensor in float4 chunks.
-// STREAM only names the launch (profilers see two symbols): true = a launch that streams >= 2^24 parameters through
-// HBM (the dense table update), false = everything else (MLP parameters, small tables).  Same code.
+// STREAM is only ever instantiated as true: everything that does not stream >= 2^24 parameters (MLP parameters, small
+// tables) goes through opt_flat_kernel.  The parameter stays because it is part of the symbol profiles and tests name.
 // PATH = the form of the vector loop, one instantiation each so that each keeps ITS register count (all forms in one
 // kernel: 170 VGPRs, two waves per SIMD -- and the plain loop, which needs 40, ran at that occupancy too):
 //   0 plain grid-stride loop (also the remainder loop of every other form)   1 two chunks per iteration
@@ -370,7 +371,7 @@ __device__ __forceinline__ void cold_resident(const OptLaunch& L, const StepCons
 // Forms 3 and 4 with a warm map (mml_opt_tensor.warm_rows, decided at run time inside the same instantiations): a row that
 // is neither marked nor warm has m = v = 0 and g = 0, the update leaves p, m and v as they are bit for bit, and the kernel
 // neither reads nor writes it -- it walks the two byte maps and touches the rows they name.
-enum { OPT_PLAIN = 0, OPT_UNROLL2 = 1, OPT_SKIP_U = 2, OPT_MARK_U = 3, OPT_MARK_ACC_U = 4 };
+// (the forms' names, OPT_PLAIN .. OPT_MARK_ACC_U: opt_plan.hpp)
 template <bool STREAM, int PATH, int U>
 __global__ __launch_bounds__(256) void opt_dense_kernel(const OptLaunch L) {
   // (workgroup-uniform: scalar loads and compares)
@@ -978,10 +979,6 @@ __global__ __launch_bounds__(256) void opt_catchup_kernel(const CatchupLaunch L)
   }
 }
 
-__global__ void counter_kernel(int32_t* c, int32_t delta, int32_t reset) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *c = reset ? 0 : (*c + delta);
-}
-
 // the counter's bump and the new step's constants in one launch (mml_opt_step_begin); the step is written last: it is
 // what tells a reader whose constants these are
 __global__ void step_begin_kernel(int32_t* c, int32_t delta, const mml_opt_hyper h, mml_opt_step_consts* out) {
@@ -994,273 +991,6 @@ __global__ void step_begin_kernel(int32_t* c, int32_t delta, const mml_opt_hyper
     out->pad_ = 0;
     out->step = t;
   }
-}
-
-// ---- elementwise -------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void ew_mul_kernel(const float* a, const float* b, float* out, int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = a[i] * b[i];
-}
-
-// act_a / act_b: the operand is the OUTPUT of that activation and this product is its only consumer, so the
-// activation's derivative (from the output value, like mml_act_bwd) is folded into the gradient written here
-__device__ __forceinline__ float act_deriv_from_output(float y, int act) {
-  if (act == MML_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  if (act == MML_ACT_SIGMOID) return y * (1.f - y);
-  if (act == MML_ACT_SIGMOID2) return y * (1.f - 0.5f * y);
-  return 1.f;
-}
-__global__ __launch_bounds__(256) void ew_mul_bwd_kernel(const float* dout, const float* a, const float* b, float* da,
-                                                         float* db, int acc_a, int acc_b, int64_t n, int act_a,
-                                                         int act_b) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float d = dout[i];
-    const float av = (db || act_a) ? a[i] : 0.f;
-    const float bv = (da || act_b) ? b[i] : 0.f;
-    if (da) {
-      const float v = d * bv * act_deriv_from_output(av, act_a);
-      da[i] = acc_a ? da[i] + v : v;
-    }
-    if (db) {
-      const float v = d * av * act_deriv_from_output(bv, act_b);
-      db[i] = acc_b ? db[i] + v : v;
-    }
-  }
-}
-
-struct AddN {
-  const float* in[16];
-  int32_t n_in;
-};
-__global__ __launch_bounds__(256) void ew_add_n_kernel(const AddN A, float* out, int64_t n) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float s = 0.f;
-    for (int k = 0; k < A.n_in; ++k) s += A.in[k][i];
-    out[i] = s;
-  }
-}
-
-// n independent items in ONE launch: out[i] (+)= sum_k x_k[i] * (y_k ? y_k[i] : 1).  STAR's derived parameters
-// (W_spec * W_shared, b_spec + b_shared for every head and layer, model/utils.py:214-216) and their gradients were
-// ~60 launches of a few KB each per step; they are two launches each way now.
-struct SumProdBatch {
-  mml_sumprod_desc d[MML_SUMPROD_BATCH];
-};
-// (act_deriv_from_output is defined further up with the mul_bwd kernel; deriv_of = the OUTPUT of the activation whose
-// derivative multiplies the sum -- PepNet's gate products, where the factor is 2*sigmoid(.) or relu(.) and this product
-// its only consumer)
-__global__ __launch_bounds__(256) void sumprod_batch_kernel(const SumProdBatch Bt) {
-  const mml_sumprod_desc& D = Bt.d[blockIdx.y];
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  bool vec = (D.n & 3) == 0 && aligned16(D.out) && (!D.deriv_of || aligned16(D.deriv_of));
-  for (int k = 0; k < D.n_terms; ++k) vec = vec && aligned16(D.x[k]) && (!D.y[k] || aligned16(D.y[k]));
-  float am = 0.f;  // operand magnitude of what this thread stores (D.amax_out)
-  if (vec) {  // 16 bytes per lane and operand
-    const int64_t n4 = D.n >> 2;
-    for (int64_t i = tid; i < n4; i += stride) {
-      float4 s = D.accumulate ? reinterpret_cast<const float4*>(D.out)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int k = 0; k < D.n_terms; ++k) {
-        const float4 x = reinterpret_cast<const float4*>(D.x[k])[i];
-        if (D.y[k]) {
-          const float4 y = reinterpret_cast<const float4*>(D.y[k])[i];
-          s.x += x.x * y.x; s.y += x.y * y.y; s.z += x.z * y.z; s.w += x.w * y.w;
-        } else {
-          s.x += x.x; s.y += x.y; s.z += x.z; s.w += x.w;
-        }
-      }
-      if (D.act != MML_ACT_NONE) {
-        const float4 o = reinterpret_cast<const float4*>(D.deriv_of)[i];
-        s.x *= act_deriv_from_output(o.x, D.act); s.y *= act_deriv_from_output(o.y, D.act);
-        s.z *= act_deriv_from_output(o.z, D.act); s.w *= act_deriv_from_output(o.w, D.act);
-      }
-      reinterpret_cast<float4*>(D.out)[i] = s;
-      amax_acc(am, s);
-    }
-    amax_flush(am, D.amax_out);
-    return;
-  }
-  for (int64_t i = tid; i < D.n; i += stride) {
-    float s = D.accumulate ? D.out[i] : 0.f;
-    for (int k = 0; k < D.n_terms; ++k) s += D.x[k][i] * (D.y[k] ? D.y[k][i] : 1.f);
-    if (D.act != MML_ACT_NONE) s *= act_deriv_from_output(D.deriv_of[i], D.act);
-    D.out[i] = s;
-    amax_acc(am, s);
-  }
-  amax_flush(am, D.amax_out);
-}
-
-__global__ __launch_bounds__(256) void copy2d_kernel(const float* src, int64_t lds_, float* dst, int64_t ldd, int64_t rows,
-                                                     int cols, int accumulate) {
-  const int64_t total = rows * cols;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t r = i / cols;
-    const int c = (int)(i - r * cols);
-    const float v = src[r * lds_ + c];
-    float* d = dst + r * ldd + c;
-    *d = accumulate ? *d + v : v;
-  }
-}
-
-constexpr int COPY2D_BATCH = 32;
-struct Copy2dBatch {
-  mml_copy2d_desc d[COPY2D_BATCH];
-};
-// blockIdx.y = item; blockIdx.x strides over that item's elements.  Round 6: 16-byte pieces, four in flight per thread, where
-// the item allows it (PepNet's [65 536, 64] concat blocks: one scalar element and a 64-bit division per trip before), and
-// an item that raises a magnitude slot is walked by at most 256 workgroups -- every workgroup ends with a look at (and
-// possibly an atomic on) the slot's one line, and 2 048 of them finishing together cost more than the magnitude pass the
-// slot replaces (measured: +25 us per copy launch).
-__global__ __launch_bounds__(256) void copy2d_batch_kernel(const Copy2dBatch Bt) {
-  const mml_copy2d_desc& D = Bt.d[blockIdx.y];
-  const int nb = D.amax_out ? ((int)gridDim.x < 256 ? (int)gridDim.x : 256) : (int)gridDim.x;
-  const bool mine = (int)blockIdx.x < nb;  // (uniform)
-  float amf = 0.f;
-  if (mine) {
-    const int64_t stride = (int64_t)nb * 256;
-    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool vec = D.cols % 4 == 0 && D.lds % 4 == 0 && D.ldd % 4 == 0 && aligned16(D.src) && aligned16(D.dst);
-    if (vec) {
-      const int c4 = D.cols >> 2;
-      const int64_t total = D.rows * c4;
-      const bool small = total < 0x7fffffff;
-      auto off = [&](int64_t i, int64_t& so, int64_t& dof) __attribute__((always_inline)) {
-        const int64_t r = small ? (int64_t)((uint32_t)i / (uint32_t)c4) : i / c4;
-        const int64_t c = (i - r * c4) << 2;
-        so = r * D.lds + c;
-        dof = r * D.ldd + c;
-      };
-      auto fin = [&](float4 v, int64_t dof) __attribute__((always_inline)) {
-        float4* q = reinterpret_cast<float4*>(D.dst + dof);
-        if (D.accumulate) {
-          const float4 o = *q;
-          v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w;
-        }
-        *q = v;
-        amax_acc(amf, v);
-      };
-      int64_t i = tid;
-      for (; i + 3 * stride < total; i += 4 * stride) {
-        int64_t s0, s1, s2, s3, d0, d1, d2, d3;
-        off(i, s0, d0); off(i + stride, s1, d1); off(i + 2 * stride, s2, d2); off(i + 3 * stride, s3, d3);
-        const float4 v0 = *reinterpret_cast<const float4*>(D.src + s0), v1 = *reinterpret_cast<const float4*>(D.src + s1);
-        const float4 v2 = *reinterpret_cast<const float4*>(D.src + s2), v3 = *reinterpret_cast<const float4*>(D.src + s3);
-        fin(v0, d0); fin(v1, d1); fin(v2, d2); fin(v3, d3);
-      }
-      for (; i < total; i += stride) {
-        int64_t s0, d0;
-        off(i, s0, d0);
-        fin(*reinterpret_cast<const float4*>(D.src + s0), d0);
-      }
-    } else {
-      const int64_t total = D.rows * D.cols;
-      for (int64_t i = tid; i < total; i += stride) {
-        const int64_t r = i / D.cols;
-        const int c = (int)(i - r * D.cols);
-        float v = D.src[r * D.lds + c];
-        float* q = D.dst + r * D.ldd + c;
-        if (D.accumulate) v += *q;
-        *q = v;
-        amax_acc(amf, v);
-      }
-    }
-  }
-  amax_flush<true>(amf, mine ? D.amax_out : nullptr);  // (uniform per workgroup; a null slot returns at once)
-}
-
-struct ColSegs {
-  const float* src[MML_MAX_FIELDS];
-  float* dst[MML_MAX_FIELDS];
-  int64_t lds_[MML_MAX_FIELDS], ldd[MML_MAX_FIELDS];
-  int32_t width[MML_MAX_FIELDS];
-  int32_t start[MML_MAX_FIELDS + 1];  // prefix sum of widths
-  int32_t n;
-};
-// One thread per (row, packed column): consecutive lanes walk the packed columns of one row, so each segment is
-// read and written in runs of `width` contiguous floats.
-__global__ __launch_bounds__(256) void copy_cols_kernel(const ColSegs S, int64_t rows, int accumulate) {
-  const int W = S.start[S.n];
-  const int64_t total = rows * W;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int64_t r = i / W;
-    const int c = (int)(i - r * W);
-    int s = 0;
-    while (c >= S.start[s + 1]) ++s;
-    const int cc = c - S.start[s];
-    const float v = S.src[s][r * S.lds_[s] + cc];
-    float* d = S.dst[s] + r * S.ldd[s] + cc;
-    *d = accumulate ? *d + v : v;
-  }
-}
-
-// The same copy in 16-byte pieces (every segment start, width, leading dimension and base pointer a multiple of four
-// floats -- the row / row-gradient exchange buffers with E % 4 == 0): segment tables and the column -> segment map are
-// staged in LDS once per workgroup, so the inner loop is one LDS lookup + one float4 load + one float4 store.
-constexpr int COPY_COLS_MAX_W4 = 1024;
-__global__ __launch_bounds__(256) void copy_cols_vec4_kernel(const ColSegs S, int64_t rows, int accumulate) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  __shared__ const float* s_src[MML_MAX_FIELDS];
-  __shared__ float* s_dst[MML_MAX_FIELDS];
-  __shared__ int64_t s_lds[MML_MAX_FIELDS], s_ldd[MML_MAX_FIELDS];
-  __shared__ int32_t s_start[MML_MAX_FIELDS + 1];
-  __shared__ uint8_t seg_of[COPY_COLS_MAX_W4];
-  const int W4 = S.start[S.n] >> 2;
-  for (int k = threadIdx.x; k < S.n; k += 256) {
-    s_src[k] = S.src[k]; s_dst[k] = S.dst[k]; s_lds[k] = S.lds_[k]; s_ldd[k] = S.ldd[k];
-  }
-  for (int k = threadIdx.x; k <= S.n; k += 256) s_start[k] = S.start[k];
-  __syncthreads();
-  for (int c = threadIdx.x; c < W4; c += 256) {
-    int lo = 0, hi = S.n - 1;  // last segment whose start <= 4c
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (s_start[mid] <= 4 * c) lo = mid; else hi = mid - 1;
-    }
-    seg_of[c] = (uint8_t)lo;
-  }
-  __syncthreads();
-  const int64_t total = rows * W4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    int64_t r;
-    int c;
-    if (total < 0x7fffffff) {  // 32-bit division when it fits
-      const uint32_t ri = (uint32_t)i / (uint32_t)W4;
-      r = ri;
-      c = (int)((uint32_t)i - ri * (uint32_t)W4);
-    } else {
-      r = i / W4;
-      c = (int)(i - r * W4);
-    }
-    const int sg = seg_of[c];
-    const int cc = 4 * c - s_start[sg];
-    const f4 v = *reinterpret_cast<const f4*>(s_src[sg] + r * s_lds[sg] + cc);
-    f4* d = reinterpret_cast<f4*>(s_dst[sg] + r * s_ldd[sg] + cc);
-    *d = accumulate ? *d + v : v;
-  }
-}
-
-__global__ __launch_bounds__(256) void act_bwd_kernel(const float* y, const float* dy, float* dst, int64_t n, int act) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float v = y[i];
-    float d = 1.f;
-    if (act == MML_ACT_RELU) d = v > 0.f ? 1.f : 0.f;
-    else if (act == MML_ACT_SIGMOID) d = v * (1.f - v);
-    else if (act == MML_ACT_SIGMOID2) d = v * (1.f - 0.5f * v);  // y = 2s: dy/dx = 2 s (1-s) = y (1 - y/2)
-    dst[i] = d * dy[i];
-  }
-}
-
-static unsigned ew_grid(int64_t n) {
-  int64_t b = cdiv(n, 256);
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (unsigned)b;
 }
 
 }  // namespace mml
@@ -1340,6 +1070,76 @@ extern "C" int mml_opt_step_unbind(const int32_t* step_dev) {
   return MML_OK;
 }
 
+namespace {
+// the lab knobs of the launch rule (opt_plan.hpp), read once
+const OptEnv& opt_env() {
+  static const OptEnv env = [] {
+    auto num = [](const char* name, int dflt) {
+      const char* e = getenv(name);
+      return e ? atoi(e) : dflt;
+    };
+    OptEnv v = OPT_ENV_DEFAULT;
+    v.variant = num("MMLREC_OPT_VARIANT", v.variant);
+    v.cold_wgs = num("MMLREC_OPT_COLD_WGS", v.cold_wgs);
+    if (v.cold_wgs < 1 || v.cold_wgs > 256 * 8) v.cold_wgs = 256 * 8;
+    v.resident_per_cu = num("MMLREC_OPT_RESIDENT_PER_CU", v.resident_per_cu);
+    if (v.resident_per_cu < 1 || v.resident_per_cu > 64) v.resident_per_cu = 8;
+    v.u_mark = num("MMLREC_OPT_U", v.u_mark);  // (a value without an instantiation: the plan falls back to 2)
+    return v;
+  }();
+  return env;
+}
+
+// every instantiation of opt_dense_kernel (DensePlan.form, .u)
+typedef void (*DenseKernel)(const OptLaunch);
+const struct {
+  int form, u;
+  DenseKernel kernel;
+} DENSE_KERNELS[] = {
+    {OPT_PLAIN, 1, opt_dense_kernel<true, OPT_PLAIN, 1>},
+    {OPT_UNROLL2, 1, opt_dense_kernel<true, OPT_UNROLL2, 1>},
+    {OPT_SKIP_U, 4, opt_dense_kernel<true, OPT_SKIP_U, 4>},
+    {OPT_MARK_U, 2, opt_dense_kernel<true, OPT_MARK_U, 2>},
+    {OPT_MARK_U, 4, opt_dense_kernel<true, OPT_MARK_U, 4>},
+    {OPT_MARK_U, 8, opt_dense_kernel<true, OPT_MARK_U, 8>},
+    {OPT_MARK_ACC_U, 2, opt_dense_kernel<true, OPT_MARK_ACC_U, 2>},
+    {OPT_MARK_ACC_U, 4, opt_dense_kernel<true, OPT_MARK_ACC_U, 4>},
+};
+
+int check_dense_tensor(const mml_opt_tensor& t, int i, const mml_opt_hyper* hyper) {
+  MML_REQUIRE(t.param && t.grad && t.n >= 0, "mml_opt_step_dense: tensor %d malformed", i);
+  MML_REQUIRE(hyper->kind == MML_OPT_SGD || t.state1, "mml_opt_step_dense: tensor %d needs state1", i);
+  MML_REQUIRE(hyper->kind != MML_OPT_ADAM || t.state2, "mml_opt_step_dense: tensor %d needs state2 (Adam)", i);
+  // (both kernels decide per 16-byte chunk by the row of its first element: a chunk must not straddle two rows)
+  MML_REQUIRE(!t.skip_rows || (t.row_elems > 0 && t.row_elems % 4 == 0 && t.n % t.row_elems == 0 &&
+                               aligned16(t.param)),
+              "mml_opt_step_dense: tensor %d: skip_rows needs row_elems %% 4 == 0 dividing n and a 16-byte aligned "
+              "parameter (16-byte chunks must lie inside one row)", i);
+  if (t.acc64) {
+    MML_REQUIRE(t.grad_marks && !t.skip_rows && t.acc_amax && aligned16(t.acc64) && t.acc_shift >= 4 &&
+                    t.acc_shift <= 28,
+                "mml_opt_step_dense: tensor %d: acc64 (deferred totals of mml_scatter_bwd_det) needs grad_marks, no "
+                "skip_rows, a 16-byte aligned int64 array, acc_amax and acc_shift = mml_scatter_det_shift(B)", i);
+  }
+  if (t.grad_marks) {
+    const int cpr = t.row_elems / 4;
+    MML_REQUIRE(t.row_elems > 0 && t.row_elems % 4 == 0 && cpr <= 64 && (cpr & (cpr - 1)) == 0 &&
+                    t.n % t.row_elems == 0 && !t.skip_rows && aligned16(t.param) && aligned16(t.grad) &&
+                    (!t.state1 || aligned16(t.state1)) && (!t.state2 || aligned16(t.state2)),
+                "mml_opt_step_dense: tensor %d: grad_marks needs 16-byte aligned [rows, row_elems] tensors with "
+                "row_elems / 4 a power of two <= 64 and no skip_rows", i);
+  }
+  if (t.warm_rows) {
+    MML_REQUIRE(t.grad_marks && t.l1 == 0.f && t.l2 == 0.f,
+                "mml_opt_step_dense: tensor %d: warm_rows needs grad_marks and no regulariser (a regulariser moves a "
+                "row whose moments and gradient are zero)", i);
+  }
+  return MML_OK;
+}
+}  // namespace
+
+// Per group of at most MML_MAX_OPT_TENSORS tensors: validate each descriptor, plan the group (opt_plan.hpp), fill
+// OptLaunch from the plan, launch from the table.
 extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, const mml_opt_hyper* hyper,
                                   mml_stream_t stream) {
   int rc = check_hyper(hyper, "mml_opt_step_dense");
@@ -1353,169 +1153,30 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
     L.sc = bound;
     int64_t total = 0, chunks = 0;
     while (i < n && L.n < MML_MAX_OPT_TENSORS) {
-      const mml_opt_tensor& t = tensors[i];
-      MML_REQUIRE(t.param && t.grad && t.n >= 0, "mml_opt_step_dense: tensor %d malformed", i);
-      MML_REQUIRE(hyper->kind == MML_OPT_SGD || t.state1, "mml_opt_step_dense: tensor %d needs state1", i);
-      MML_REQUIRE(hyper->kind != MML_OPT_ADAM || t.state2, "mml_opt_step_dense: tensor %d needs state2 (Adam)", i);
-      // (both kernels decide per 16-byte chunk by the row of its first element: a chunk must not straddle two rows)
-      MML_REQUIRE(!t.skip_rows || (t.row_elems > 0 && t.row_elems % 4 == 0 && t.n % t.row_elems == 0 &&
-                                   aligned16(t.param)),
-                  "mml_opt_step_dense: tensor %d: skip_rows needs row_elems %% 4 == 0 dividing n and a 16-byte aligned "
-                  "parameter (16-byte chunks must lie inside one row)", i);
-      if (t.acc64) {
-        MML_REQUIRE(t.grad_marks && !t.skip_rows && t.acc_amax && aligned16(t.acc64) && t.acc_shift >= 4 &&
-                        t.acc_shift <= 28,
-                    "mml_opt_step_dense: tensor %d: acc64 (deferred totals of mml_scatter_bwd_det) needs grad_marks, no "
-                    "skip_rows, a 16-byte aligned int64 array, acc_amax and acc_shift = mml_scatter_det_shift(B)", i);
-      }
-      if (t.grad_marks) {
-        const int cpr = t.row_elems / 4;
-        MML_REQUIRE(t.row_elems > 0 && t.row_elems % 4 == 0 && cpr <= 64 && (cpr & (cpr - 1)) == 0 &&
-                        t.n % t.row_elems == 0 && !t.skip_rows && aligned16(t.param) && aligned16(t.grad) &&
-                        (!t.state1 || aligned16(t.state1)) && (!t.state2 || aligned16(t.state2)),
-                    "mml_opt_step_dense: tensor %d: grad_marks needs 16-byte aligned [rows, row_elems] tensors with "
-                    "row_elems / 4 a power of two <= 64 and no skip_rows", i);
-      }
-      if (t.warm_rows) {
-        MML_REQUIRE(t.grad_marks && t.l1 == 0.f && t.l2 == 0.f,
-                    "mml_opt_step_dense: tensor %d: warm_rows needs grad_marks and no regulariser (a regulariser moves a "
-                    "row whose moments and gradient are zero)", i);
-      }
+      rc = check_dense_tensor(tensors[i], i, hyper);
+      if (rc) return rc;
       L.chunk0[L.n] = chunks;
-      L.t[L.n++] = t;
-      total += t.n;
-      chunks += cdiv(t.n, 4);
+      L.t[L.n++] = tensors[i];
+      total += tensors[i].n;
+      chunks += cdiv(tensors[i].n, 4);
       ++i;
     }
     L.chunk0[L.n] = chunks;
     if (total == 0) continue;
-    static int variant = -1;
-    if (variant < 0) {
-      const char* e = getenv("MMLREC_OPT_VARIANT");
-      variant = e ? atoi(e) : 0;
-    }
-    L.variant = variant | (hyper->max_blocks > 0 ? 4 : 0) | (hyper->cold_loop == 1 ? 8 : 0);
-    // A group dominated by one huge tensor (the dense table update) streams with the per-tensor kernel (blockIdx.y =
-    // tensor: no index search on the 2.7 GB stream); everything else (dozens of tensors from 64 B to a few MB) goes
-    // through the flat kernel, where every workgroup has the same amount of work.
-    int64_t nmax = 0;
-    for (int k = 0; k < L.n; ++k) nmax = L.t[k].n > nmax ? L.t[k].n : nmax;
-    // the loop form (see opt_dense_kernel): decided for the launch, so every tensor of it must qualify
-    bool all_gm = true, all_skip = true, none = true, any_acc = false;
-    for (int k = 0; k < L.n; ++k) {
-      any_acc = any_acc || L.t[k].acc64;
-      all_gm = all_gm && L.t[k].grad_marks && !L.t[k].skip_rows;
-      all_skip = all_skip && L.t[k].skip_rows;
-      none = none && !L.t[k].grad_marks && !L.t[k].skip_rows;
-    }
-    // Round 6: a model's tables in ONE marked streaming launch (AE-30: 4 huge + 26 small; the small ones were a second
-    // launch of the flat kernel, 31-34 us behind the stream): workgroups dealt in proportion to the tensors' sizes.
-    const bool many = L.n > 4 && all_gm;
-    MML_REQUIRE(!any_acc || all_gm, "mml_opt_step_dense: a launch with acc64 tensors takes grad_marks on every tensor");
-    if (total >= ((int64_t)1 << 24) && (L.n <= 4 || many)) {
-      int64_t bx = cdiv(cdiv(nmax, 4), 256);
-      if (bx > 256 * 8) bx = 256 * 8;
-      if (hyper->max_blocks > 0 && bx * L.n > hyper->max_blocks) bx = cdiv(hyper->max_blocks, L.n);
-      dim3 grid((unsigned)bx, (unsigned)L.n);
-      // Workgroups per tensor at most.  With a warm map on every tensor most of the stream is passed over and a workgroup's
-      // fixed cost (tensor search, magnitude words, unbound bias corrections) is what is left of a short one:
-      // MMLREC_OPT_COLD_WGS (lab knob) caps them lower.  Measured side by side at 3.8 % warm rows, 2 048 / 1 024 / 512:
-      // 129.8 / 119.2 / 116.1 us -- which is why a launch that qualifies leaves this grid altogether (`resident`, below).
-      bool all_warm = true;
-      for (int k = 0; k < L.n; ++k) all_warm = all_warm && L.t[k].warm_rows;
-      static int cold_wgs = -1;
-      if (cold_wgs < 0) {
-        const char* e = getenv("MMLREC_OPT_COLD_WGS");
-        cold_wgs = e ? atoi(e) : 256 * 8;
-        if (cold_wgs < 1 || cold_wgs > 256 * 8) cold_wgs = 256 * 8;
-      }
-      // One resident grid (cold_resident): the launch runs a kernel with the wave-compacted loop (forms 3 / 4), every
-      // tensor carries a warm map with word-aligned map pointers, and the switch asks for it.  Sized for the chip -- twice
-      // the kernel's workgroups that fit a compute unit (4 at its register count: two rounds, so that a workgroup whose
-      // spans hold the warm head of a Zipf table is made up for by the late starters; cold_loop = 3: one round; lab knob
-      // MMLREC_OPT_RESIDENT_PER_CU) x compute units -- and never above what the launch gets otherwise (max_blocks
-      // included).  MMLREC_OPT_COLD_WGS means nothing here.
-      bool resident = all_warm && all_gm && (any_acc || (L.variant & 4)) && (hyper->cold_loop == 0 || hyper->cold_loop == 3);
-      int64_t nspan = 0;
-      for (int k = 0; k < L.n && resident; ++k) {
-        const mml_opt_tensor& t = L.t[k];
-        resident = ((reinterpret_cast<uintptr_t>(t.grad_marks) | reinterpret_cast<uintptr_t>(t.warm_rows)) & 3) == 0;
-        nspan += cdiv(t.n / t.row_elems, COLD_SPAN);
-      }
-      resident = resident && nspan < ((int64_t)1 << 30);  // (span numbers are 32-bit in the kernel)
-      const int64_t wg_cap = (all_warm && !resident) ? cold_wgs : 256 * 8;
-      if (many) {
-        // every tensor gets what a launch of its own would give it (one workgroup per 256 chunks, at most 2 048): the huge
-        // tables stream exactly as in their four-tensor launch, the small ones add a few hundred workgroups (the caller
-        // lists them FIRST: they start with the launch instead of trailing it).  Under a workgroup cap: in proportion.
-        int64_t want = 0;
-        for (int k = 0; k < L.n; ++k) {
-          const int64_t need = cdiv(cdiv(L.t[k].n, 4), 256);
-          want += need > wg_cap ? wg_cap : (need < 1 ? 1 : need);
-        }
-        const bool capped = hyper->max_blocks > 0 && want > hyper->max_blocks;
-        int64_t tb = capped ? hyper->max_blocks : want;
-        if (tb < L.n) tb = L.n;
-        int64_t at = 0;
-        for (int k = 0; k < L.n; ++k) {
-          L.blk0[k] = (int32_t)at;
-          const int64_t need = cdiv(cdiv(L.t[k].n, 4), 256);
-          int64_t nb = capped ? tb * L.t[k].n / total : (need > wg_cap ? wg_cap : need);
-          if (nb > need) nb = need;
-          if (nb < 1) nb = 1;
-          at += nb;
-        }
-        L.blk0[L.n] = (int32_t)at;
-        L.prop = 1;
-        grid = dim3((unsigned)at, 1);
-      }
-      if (resident) {
-        int64_t wgs = (int64_t)grid.x * grid.y;
-        static int per_cu = -1;
-        if (per_cu < 0) {
-          const char* e = getenv("MMLREC_OPT_RESIDENT_PER_CU");
-          per_cu = e ? atoi(e) : 8;
-          if (per_cu < 1 || per_cu > 64) per_cu = 8;
-        }
-        const int64_t fit = (int64_t)(hyper->cold_loop == 3 ? 4 : per_cu) * device_cus();
-        if (wgs > fit) wgs = fit;
-        int64_t at = 0;
-        for (int k = 0; k < L.n; ++k) {
-          L.blk0[k] = (int32_t)at;
-          at += cdiv(L.t[k].n / L.t[k].row_elems, COLD_SPAN);
-        }
-        L.blk0[L.n] = (int32_t)at;
-        L.prop = 2;
-        grid = dim3((unsigned)(wgs < 1 ? 1 : wgs), 1);
-      }
-      static int u_mark = -1;
-      if (u_mark < 0) {
-        const char* e = getenv("MMLREC_OPT_U");  // lab knob: chunks in flight per thread of the marked form (2, 4, 8)
-        u_mark = e ? atoi(e) : 2;
-      }
-      hipStream_t st = to_stream(stream);
-      if (any_acc) {  // (capped grid or not: the totals are only read by this form)
-        if (u_mark == 4) MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_ACC_U, 4>), grid, dim3(256), 0, st, L);
-        else MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_ACC_U, 2>), grid, dim3(256), 0, st, L);
-      } else if ((L.variant & 4) && all_gm) {
-        if (u_mark == 4) MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_U, 4>), grid, dim3(256), 0, st, L);
-        else if (u_mark == 8) MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_U, 8>), grid, dim3(256), 0, st, L);
-        else MML_LAUNCH((opt_dense_kernel<true, OPT_MARK_U, 2>), grid, dim3(256), 0, st, L);
-      } else if ((L.variant & 4) && all_skip) {
-        MML_LAUNCH((opt_dense_kernel<true, OPT_SKIP_U, 4>), grid, dim3(256), 0, st, L);
-      } else if ((L.variant & 2) && none) {
-        MML_LAUNCH((opt_dense_kernel<true, OPT_UNROLL2, 1>), grid, dim3(256), 0, st, L);
-      } else {
-        MML_LAUNCH((opt_dense_kernel<true, OPT_PLAIN, 1>), grid, dim3(256), 0, st, L);
-      }
+    DensePlan P;
+    const char* const refused = opt_plan_dense(L.t, L.n, *hyper, opt_env(), device_cus(), P);
+    MML_REQUIRE(!refused, "%s", refused);
+    L.variant = P.variant;
+    L.prop = P.prop;
+    memcpy(L.blk0, P.blk0, sizeof(L.blk0));
+    if (P.form == OPT_FLAT) {
+      MML_LAUNCH(opt_flat_kernel, dim3(P.grid_x), dim3(256), 0, to_stream(stream), L);
     } else {
-      for (int k = 0; k < L.n; ++k)
-        MML_REQUIRE(!L.t[k].grad_marks, "mml_opt_step_dense: grad_marks (and acc64) is only honoured by the streaming "
-                    "launch (>= 2^24 parameters in <= 4 tensors, or any number of marked tensors)");
-      int64_t bx = cdiv(chunks, 256);
-      if (bx > 256 * 8) bx = 256 * 8;
-      if (hyper->max_blocks > 0 && bx > hyper->max_blocks) bx = hyper->max_blocks;
-      MML_LAUNCH(opt_flat_kernel, dim3((unsigned)bx), dim3(256), 0, to_stream(stream), L);
+      DenseKernel kernel = nullptr;
+      for (const auto& k : DENSE_KERNELS)
+        if (k.form == P.form && k.u == P.u) kernel = k.kernel;
+      MML_REQUIRE(kernel, "mml_opt_step_dense: no opt_dense_kernel<true, %d, %d>", P.form, P.u);
+      MML_LAUNCH(kernel, dim3(P.grid_x, P.grid_y), dim3(256), 0, to_stream(stream), L);
     }
     rc = check_launch("mml_opt_step_dense");
     if (rc) return rc;
@@ -1599,152 +1260,3 @@ extern "C" int mml_opt_step_rows(float* const* tables, float* const* grad_tables
   return check_launch("mml_opt_step_rows");
 }
 
-extern "C" int mml_counter_update(int32_t* counter, int32_t delta, int32_t reset, mml_stream_t stream) {
-  MML_REQUIRE(counter, "mml_counter_update: null counter");
-  step_unbind(counter);  // (constants kept for this counter by mml_opt_step_begin would go stale)
-  MML_LAUNCH(counter_kernel, dim3(1), dim3(64), 0, to_stream(stream), counter, delta, reset);
-  return check_launch("mml_counter_update");
-}
-
-extern "C" int mml_ew_mul(const float* a, const float* b, float* out, int64_t n, mml_stream_t stream) {
-  MML_REQUIRE(n >= 0 && (n == 0 || (a && b && out)), "mml_ew_mul: null argument");
-  if (n == 0) return MML_OK;
-  MML_LAUNCH(ew_mul_kernel, dim3(ew_grid(n)), dim3(256), 0, to_stream(stream), a, b, out, n);
-  return check_launch("mml_ew_mul");
-}
-
-extern "C" int mml_ew_mul_bwd_act(const float* dout, const float* a, const float* b, float* da, float* db,
-                                  int32_t acc_a, int32_t acc_b, int64_t n, int32_t act_a, int32_t act_b,
-                                  mml_stream_t stream) {
-  MML_REQUIRE(n >= 0 && (n == 0 || dout), "mml_ew_mul_bwd: null dout");
-  MML_REQUIRE(!da || b, "mml_ew_mul_bwd: da needs b");
-  MML_REQUIRE(!db || a, "mml_ew_mul_bwd: db needs a");
-  MML_REQUIRE(act_a >= MML_ACT_NONE && act_a <= MML_ACT_SIGMOID2 && act_b >= MML_ACT_NONE && act_b <= MML_ACT_SIGMOID2,
-              "mml_ew_mul_bwd: unknown activation");
-  MML_REQUIRE((!act_a || (a && da && !acc_a)) && (!act_b || (b && db && !acc_b)),
-              "mml_ew_mul_bwd: a folded activation derivative needs the operand, its gradient, and no accumulation");
-  if (n == 0) return MML_OK;
-  MML_LAUNCH(ew_mul_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, to_stream(stream), dout, a, b, da, db, acc_a,
-                     acc_b, n, act_a, act_b);
-  return check_launch("mml_ew_mul_bwd");
-}
-
-extern "C" int mml_ew_mul_bwd(const float* dout, const float* a, const float* b, float* da, float* db, int32_t acc_a,
-                              int32_t acc_b, int64_t n, mml_stream_t stream) {
-  return mml_ew_mul_bwd_act(dout, a, b, da, db, acc_a, acc_b, n, MML_ACT_NONE, MML_ACT_NONE, stream);
-}
-
-extern "C" int mml_ew_add_n(const float* const* in, int32_t n_in, float* out, int64_t n, mml_stream_t stream) {
-  MML_REQUIRE(in && n_in >= 1 && n_in <= 16 && out && n >= 0, "mml_ew_add_n: bad arguments");
-  if (n == 0) return MML_OK;
-  AddN A{};
-  A.n_in = n_in;
-  for (int i = 0; i < n_in; ++i) {
-    MML_REQUIRE(in[i], "mml_ew_add_n: input %d null", i);
-    A.in[i] = in[i];
-  }
-  MML_LAUNCH(ew_add_n_kernel, dim3(ew_grid(n)), dim3(256), 0, to_stream(stream), A, out, n);
-  return check_launch("mml_ew_add_n");
-}
-
-extern "C" int mml_copy2d(const float* src, int64_t lds_, float* dst, int64_t ldd, int64_t rows, int32_t cols,
-                          int32_t accumulate, mml_stream_t stream) {
-  MML_REQUIRE(rows >= 0 && cols >= 0, "mml_copy2d: negative extent");
-  if (rows == 0 || cols == 0) return MML_OK;
-  MML_REQUIRE(src && dst && lds_ >= cols && ldd >= cols, "mml_copy2d: null pointer or leading dimension < cols");
-  MML_LAUNCH(copy2d_kernel, dim3(ew_grid(rows * cols)), dim3(256), 0, to_stream(stream), src, lds_, dst, ldd,
-                     rows, cols, accumulate);
-  return check_launch("mml_copy2d");
-}
-
-extern "C" int mml_copy2d_batch(const mml_copy2d_desc* d, int32_t n, mml_stream_t stream) {
-  MML_REQUIRE(n >= 0 && (n == 0 || d), "mml_copy2d_batch: null descriptor array");
-  for (int i0 = 0; i0 < n; i0 += COPY2D_BATCH) {
-    Copy2dBatch Bt{};
-    int m = 0;
-    int64_t most = 0;
-    for (int i = i0; i < n && m < COPY2D_BATCH; ++i) {
-      const mml_copy2d_desc& D = d[i];
-      MML_REQUIRE(D.rows >= 0 && D.cols >= 0, "mml_copy2d_batch: item %d has a negative extent", i);
-      if (D.rows == 0 || D.cols == 0) continue;
-      MML_REQUIRE(D.src && D.dst && D.lds >= D.cols && D.ldd >= D.cols,
-                  "mml_copy2d_batch: item %d: null pointer or leading dimension < cols", i);
-      Bt.d[m++] = D;
-      most = D.rows * D.cols > most ? D.rows * D.cols : most;
-    }
-    if (m == 0) continue;
-    MML_LAUNCH(copy2d_batch_kernel, dim3(ew_grid(most), (unsigned)m), dim3(256), 0, to_stream(stream), Bt);
-    int rc = check_launch("mml_copy2d_batch");
-    if (rc) return rc;
-  }
-  return MML_OK;
-}
-
-extern "C" int mml_copy_cols(const float* const* src, const int64_t* lds_, float* const* dst, const int64_t* ldd,
-                             const int32_t* width, int32_t n_seg, int64_t rows, int32_t accumulate,
-                             mml_stream_t stream) {
-  MML_REQUIRE(n_seg >= 0 && rows >= 0, "mml_copy_cols: negative extent");
-  if (n_seg == 0 || rows == 0) return MML_OK;
-  MML_REQUIRE(src && lds_ && dst && ldd && width, "mml_copy_cols: null array");
-  for (int i0 = 0; i0 < n_seg; i0 += MML_MAX_FIELDS) {
-    ColSegs S{};
-    S.n = (n_seg - i0 < MML_MAX_FIELDS) ? (n_seg - i0) : MML_MAX_FIELDS;
-    int acc = 0;
-    for (int s = 0; s < S.n; ++s) {
-      const int k = i0 + s;
-      MML_REQUIRE(src[k] && dst[k] && width[k] > 0 && lds_[k] >= width[k] && ldd[k] >= width[k],
-                  "mml_copy_cols: segment %d malformed", k);
-      S.src[s] = src[k]; S.dst[s] = dst[k]; S.lds_[s] = lds_[k]; S.ldd[s] = ldd[k]; S.width[s] = width[k];
-      S.start[s] = acc;
-      acc += width[k];
-    }
-    S.start[S.n] = acc;
-    bool v4 = (acc >> 2) <= COPY_COLS_MAX_W4;
-    for (int s = 0; s < S.n && v4; ++s)
-      v4 = S.width[s] % 4 == 0 && S.lds_[s] % 4 == 0 && S.ldd[s] % 4 == 0 && aligned16(S.src[s]) && aligned16(S.dst[s]);
-    if (v4)
-      MML_LAUNCH(copy_cols_vec4_kernel, dim3(ew_grid(rows * (acc >> 2))), dim3(256), 0, to_stream(stream), S, rows,
-                 accumulate);
-    else
-      MML_LAUNCH(copy_cols_kernel, dim3(ew_grid(rows * acc)), dim3(256), 0, to_stream(stream), S, rows, accumulate);
-    int rc = check_launch("mml_copy_cols");
-    if (rc) return rc;
-  }
-  return MML_OK;
-}
-
-extern "C" int mml_act_bwd(const float* y, const float* dy, float* dst, int64_t n, int32_t act, mml_stream_t stream) {
-  MML_REQUIRE(n >= 0 && (n == 0 || (y && dy && dst)), "mml_act_bwd: null argument");
-  MML_REQUIRE(act >= MML_ACT_NONE && act <= MML_ACT_SIGMOID2, "mml_act_bwd: unknown activation %d", act);
-  if (n == 0) return MML_OK;
-  MML_LAUNCH(act_bwd_kernel, dim3(ew_grid(n)), dim3(256), 0, to_stream(stream), y, dy, dst, n, act);
-  return check_launch("mml_act_bwd");
-}
-
-extern "C" int mml_sumprod_batch(const mml_sumprod_desc* d, int32_t n, mml_stream_t stream) {
-  MML_REQUIRE(n >= 0 && (n == 0 || d), "mml_sumprod_batch: bad descriptor array");
-  for (int i0 = 0; i0 < n; i0 += MML_SUMPROD_BATCH) {
-    SumProdBatch Bt{};
-    const int m = (n - i0 < MML_SUMPROD_BATCH) ? n - i0 : MML_SUMPROD_BATCH;
-    int64_t nmax = 0;
-    for (int i = 0; i < m; ++i) {
-      const mml_sumprod_desc& D = d[i0 + i];
-      MML_REQUIRE(D.out && D.n >= 0 && D.n_terms >= 0 && D.n_terms <= MML_SUMPROD_TERMS, "mml_sumprod_batch: item %d malformed", i0 + i);
-      for (int k = 0; k < D.n_terms; ++k) MML_REQUIRE(D.x[k], "mml_sumprod_batch: item %d term %d is null", i0 + i, k);
-      MML_REQUIRE(D.act >= MML_ACT_NONE && D.act <= MML_ACT_SIGMOID2 && (D.act == MML_ACT_NONE || (D.deriv_of && !D.accumulate)),
-                  "mml_sumprod_batch: item %d: a folded activation derivative needs deriv_of and no accumulation", i0 + i);
-      Bt.d[i] = D;
-      nmax = D.n > nmax ? D.n : nmax;
-    }
-    if (nmax == 0) continue;
-    // about 2048 workgroups in all (8 per CU: every wave slot) walking their item grid-stride: items that publish their
-    // magnitude end with one atomic per workgroup, and 30 000 of those on eight words cost more than the pass itself
-    unsigned gx = ew_grid(nmax);
-    const unsigned cap = (unsigned)(2048 / m > 64 ? 2048 / m : 64);
-    if (gx > cap) gx = cap;
-    MML_LAUNCH(sumprod_batch_kernel, dim3(gx, (unsigned)m), dim3(256), 0, to_stream(stream), Bt);
-    int rc = check_launch("mml_sumprod_batch");
-    if (rc) return rc;
-  }
-  return MML_OK;
-}

@@ -17,7 +17,7 @@ namespace mml {
 
 constexpr int PRELU_BATCH = 32;    // items per launch (the descriptors travel as kernel arguments: 32 x 96 B backward)
 constexpr int PRELU_MAX_GX = 2048; // most workgroups per item: the partials of one item in the workspace
-constexpr int PRELU_AMAX_GX = 256; // an item that raises a magnitude slot: see copy2d_batch_kernel (csrc/optim_ew.hip)
+constexpr int PRELU_AMAX_GX = 256; // an item that raises a magnitude slot: see copy2d_batch_kernel (csrc/ew.hip)
 
 struct PreluFwdBatch {
   mml_prelu_desc d[PRELU_BATCH];

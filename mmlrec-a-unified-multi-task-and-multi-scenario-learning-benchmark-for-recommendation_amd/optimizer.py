@@ -35,7 +35,7 @@ class OptKnobs:
     early_blocks: int = 0
     # MMLREC_TAIL_BLOCKS (workgroup cap of the unsplit update, 0 = plain loop) / MMLREC_OPT_U (chunks in flight per thread
     # of the marked form).  Round 3: the single marked launch runs beside the weight-gradient GEMMs of the side stream.
-    # Every loop form is its own kernel (csrc/optim_ew.hip: the plain loop at 54 VGPRs / 8 waves per SIMD, two chunks per
+    # Every loop form is its own kernel (csrc/optim.hip: the plain loop at 54 VGPRs / 8 waves per SIMD, two chunks per
     # thread at 100 / 4, four at 172 / 2, eight at 256 / 1).  Alone (same box, ms): two chunks 0.39-0.44, plain 0.43-0.49,
     # four chunks 0.47-0.50, eight 0.85.  In the step (three interleaved repetitions on a quiet box): plain 1.928, two
     # chunks 1.912, four chunks under a 3072-workgroup cap 1.883 -- the two-wave form leaves the GEMMs their registers --
@@ -114,13 +114,13 @@ def resolve_table_update(kind, requested, widths, one_table_per_field, table_par
 
 
 def opt_dense_symbol(numel, ntensors, form=0, opt_u=None):
-    """Kernel symbol of a dense optimizer launch (csrc/optim_ew.hip: mml_opt_step_dense's choice).  form: the loop form
+    """Kernel symbol of a dense optimizer launch (csrc/opt_plan.hpp: mml_opt_step_dense's choice).  form: the loop form
     of the streaming kernel -- 0 plain, 1 two chunks per iteration (MMLREC_OPT_VARIANT bit 1), 2 untouched rows of the
     split update under a capped grid, 3 marked gradients under a capped grid, 4 marked gradients plus the deferred totals
-    of the deterministic scatter (any grid).  opt_u: OptKnobs.opt_u."""
+    of the deterministic scatter (any grid).  opt_u: OptKnobs.opt_u; a value without an instantiation runs two chunks."""
     if not L.opt_dense_streams(numel, ntensors, form in (3, 4)):
         return "opt_flat_kernel"
-    u = {0: 1, 1: 1, 2: 4, 3: 2 if opt_u is None else opt_u, 4: 4 if opt_u == 4 else 2}[form]
+    u = {0: 1, 1: 1, 2: 4, 3: opt_u if opt_u in (4, 8) else 2, 4: 4 if opt_u == 4 else 2}[form]
     return "opt_dense_kernel<true, %d, %d>" % (form, u)
 
 

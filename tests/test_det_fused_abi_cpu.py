@@ -27,7 +27,7 @@ def test_opt_tensor_mirror_matches_the_header_and_fits_a_launch():
     assert C.sizeof(L.OptTensor) == size
     assert L.OptTensor.acc64.offset == off_acc and L.OptTensor.acc_shift.offset == off_shift
     assert (f1, f2, f4) == (L.SCATTER_DET_CLEAR_MARKS, L.SCATTER_DET_AMAX_SUPPLIED, L.SCATTER_DET_DEFER_TOTALS)
-    # csrc/optim_ew.hip's OptLaunch (passed by value): the tensors, the hyper-parameters, n / variant / prop and the two
+    # csrc/optim.hip's OptLaunch (passed by value): the tensors, the hyper-parameters, n / variant / prop and the two
     # prefix tables -- under the 4 KB of a kernel-argument block
     launch = L.MAX_OPT_TENSORS * size + hyper + 3 * 4 + (L.MAX_OPT_TENSORS + 1) * (8 + 4)
     assert launch + 16 <= 4096, launch

@@ -1,4 +1,4 @@
-"""The wave-compacted loop of the marked streaming table update over a warm map (mml_opt_hyper.cold_loop = 0, csrc/optim_ew.hip):
+"""The wave-compacted loop of the marked streaming table update over a warm map (mml_opt_hyper.cold_loop = 0, csrc/optim.hip):
 a lane reads a dword of marks and a dword of warm bytes, the wave lists its live rows and shares their chunks out.
 
 Every case is ONE launch over seven small tables (1 .. 1 025 rows: smaller than a span, one row more or less than a span
@@ -12,7 +12,7 @@ Which cases run the compacted loop: form 4 with either cap, and form 3 with max_
 launched as the plain loop form (mml_opt_step_dense picks the marked form 3 only under a workgroup cap), whose remainder loop
 reads the maps byte by byte: those cases, the odd-address cases and the cold_loop = 1 cases check the other loops against the
 same reference.  The comparison is bitwise and all loops give the same bits, so no case can tell which loop ran; that the
-compacted loop is the one the capped and form-4 launches take is read from the code (csrc/optim_ew.hip: `compact`)."""
+compacted loop is the one the capped and form-4 launches take is read from the code (csrc/optim.hip: `compact`)."""
 import functools
 
 import pytest

@@ -1,4 +1,4 @@
-"""The marked streaming table update on ONE grid sized for the chip (csrc/optim_ew.hip: cold_resident, mml_opt_hyper.cold_loop
+"""The marked streaming table update on ONE grid sized for the chip (csrc/optim.hip: cold_resident, mml_opt_hyper.cold_loop
 = 0): the 256-row spans of all tensors of the launch form one index space and wave w of the grid takes spans w, w + W, ...;
 and the step's constants read from the buffer mml_opt_step_begin fills instead of computed by every workgroup.
 

@@ -1,7 +1,7 @@
 """The optimizer's planning rules, which need no GPU: dense_table_launches (the mml_opt_step_dense calls of the dense table
 update), resolve_table_update (the table-update mode) and OptKnobs.from_env.  Every expectation is the rule list of the
 functions' docstrings written out; every launch planned here is also held against the C side's size rule
-(csrc/optim_ew.hip, mml_opt_step_dense), written out in c_side_streams below."""
+(csrc/opt_plan.hpp, which mml_opt_step_dense launches by), asked of the compiled rule itself in c_side_streams below."""
 import pytest
 
 E8 = 8
@@ -19,8 +19,12 @@ def mod():
 
 
 def c_side_streams(total, n, all_marked):
-    """optim_ew.hip: `many = n > 4 && all_gm; if (total >= 2^24 && (n <= 4 || many))` streaming, else the flat kernel."""
-    return total >= (1 << 24) and (n <= 4 or (n > 4 and all_marked))
+    """Whether the C rule streams `total` parameters in `n` tensors (csrc/opt_plan.hpp through the stand-alone driver of
+    test_opt_plan_cpu.py); a marked group the flat kernel would get is refused there: it does not stream."""
+    from test_opt_plan_cpu import run_plans
+    sizes = [total - (n - 1)] + [1] * (n - 1)
+    marks = (1 << 20) if all_marked else 0
+    return isinstance(run_plans([([(s, E8, marks, 0, 0, 0) for s in sizes], CAP, 0, {})])[0], dict)
 
 
 def plan(O, rows, marks=True, kind="adam", split=False, cap=CAP, deferred=False, E=E8, **knobs):
