@@ -22,6 +22,18 @@ int check_launch(const char* what) {
   return MML_OK;
 }
 
+int device_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0, nn = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
+      nn = 256;
+    cus = nn;
+  }
+  return cus;
+}
+
 }  // namespace mml
 
 extern "C" int mml_version(void) { return 100; }

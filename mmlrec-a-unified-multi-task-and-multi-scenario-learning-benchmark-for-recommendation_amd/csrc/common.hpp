@@ -18,6 +18,9 @@ inline hipStream_t to_stream(mml_stream_t s) { return reinterpret_cast<hipStream
 // Check a launch without synchronising (capturable).
 int check_launch(const char* what);
 
+// Compute units of the current device (asked once, then cached); 256 when the query fails.
+int device_cus();
+
 __host__ __device__ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -15,6 +15,7 @@
 // conflict-free ds_read_b128 per 16-lane group); otherwise as [k][row] (pitch 132) and read with ds_read_b32.
 // k <-> (lane half h, step j) mapping inside an 8-deep group: k = 8q + 4h + j for BOTH operands.
 #include "common.hpp"
+#include "gemm_route.hpp"
 #include "lds_async.hpp"
 #include "reduce.hpp"
 
@@ -26,8 +27,7 @@ namespace mml {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-constexpr int BM = 128;
-constexpr int BK = 32;
+// (BM, BK, GK, MAX_SOURCES and the EPI_* kinds: gemm_route.hpp)
 constexpr int PITCH_RC = BK + 4;    // [row][k] layout
 constexpr int PITCH_NRC = 128 + 4;  // [k][row] layout (row extent always 128 slots; BN=64 uses half)
 
@@ -42,10 +42,6 @@ struct Source {
   const uint32_t* amaxA;
   const uint32_t* amaxB;
 };
-
-enum { EPI_FWD = 0, EPI_DGRAD = 1, EPI_SLAB = 2 };
-
-constexpr int MAX_SOURCES = 24;  // per launch, over all problems (kernel-argument block stays < 4 KiB)
 
 struct Problem {
   int32_t src0, nsrc;  // sources [src0, src0 + nsrc) of Launch::src
@@ -302,7 +298,6 @@ __device__ __forceinline__ void stash_tile(const float4 (&r)[ROWS / 32], float* 
   }
 }
 
-
 // fragment for 8-deep group q: 4 values (j = 0..3) for row `row` (tile-local), lane half h.
 template <bool RC>
 __device__ __forceinline__ float4 read_frag(const float* lds, int row, int q, int h) {
@@ -374,7 +369,6 @@ __device__ __forceinline__ void tile_mainloop(f32x16 (&acc)[2][BN / 64], const L
     }
   }
 }
-
 
 // BN = 64 tiles need <= 128 VGPRs, so four workgroups (one wave each per SIMD) fit a CU; the images take
 // 36 KiB of LDS per workgroup (4 x 36 = 144 KiB <= 160 KiB).
@@ -498,9 +492,7 @@ __global__ __launch_bounds__(256, (BN == 64 ? 4 : 2)) void gemm_kernel(const Lau
 // epilogue discards), so no zero-fill is needed.  Eligibility (checked on the host, else gemm_kernel runs): every
 // reduction extent a multiple of 16, 16-byte aligned operands with ld % 4 == 0, row-contiguous extents % 4 == 0.
 // ====================================================================================================
-constexpr int GK = 16;
 constexpr int GA = 128 * GK;  // floats per A stage
-
 
 // The lane's 8 k-values of one 32-row sub-tile for one k-step, as the LDS reads deliver them:
 //   reduction-contiguous image: two ds_read_b128 (k-groups 0 and 1);
@@ -538,7 +530,6 @@ __device__ __forceinline__ void read_frag_nrc(uint32_t a, RawFrag<false>& r) {
   r.p3 = ds_read2st64<U1 + 2 * SU, U1 + 3 * SU>(a);
 }
 
-
 // ====================================================================================================
 // Software-pipelined direct-to-LDS kernel ("pipe"): same tiles, operand images and MFMA map as gemm_glds_kernel,
 // different schedule.
@@ -554,7 +545,6 @@ __device__ __forceinline__ void read_frag_nrc(uint32_t a, RawFrag<false>& r) {
 //   block 2: acc01 += A0 x B1   ||  prepare A1          block 4: acc11 += A1 x B1  ||  prepare next A0
 // ====================================================================================================
 constexpr int PSTAGES = 4;
-
 
 template <int EMU>
 struct Prep {
@@ -1659,239 +1649,125 @@ __global__ __launch_bounds__(256, ((BN == 64 && EPI != EPI_DGRAD && !K7) ? 3 : 2
   }
 }
 
-// host-side eligibility of a whole launch for the direct-to-LDS path
-static bool pipe_ok(const Launch& L, bool arc, bool brc, int bn, int epi) {
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("MMLREC_GEMM_GLDS");
-    enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!enabled) return false;
-  for (int i = 0; i < L.n; ++i) {
-    const Problem& P = L.p[i];
-    if (!arc && (P.M % 4 != 0 || P.M < 4)) return false;
-    if (!brc && (P.N % 4 != 0 || P.N < 4)) return false;
-    if (P.M < 1 || P.N < 1) return false;
-    for (int s = 0; s < P.nsrc; ++s) {
-      const Source& S = L.src[P.src0 + s];
-      if (S.Kred % GK != 0 || S.Kred < GK || !S.vecA || !S.vecB) return false;
-    }
-  }
-  if (epi == EPI_SLAB && L.chunk % GK != 0) return false;
-  return true;
+// ---- host side: the dispatch rule is gemm_route.hpp; what follows reads the switches, fills the kernels' argument
+// blocks from the descriptors and launches what the rule planned ----
+// The process-wide switches: the environment is read once, the mml_gemm_set_* setters write here; MMLREC_GEMM_OS alone is
+// read on every call (a test switches it inside one process).
+static GemmEnv& gemm_env() {
+  static GemmEnv env = [] {
+    auto num = [](const char* name, int dflt) {
+      const char* e = getenv(name);
+      return e ? atoi(e) : dflt;
+    };
+    auto off = [](const char* name) {  // "0..." switches off, anything else leaves on
+      const char* e = getenv(name);
+      return (e && e[0] == '0') ? 0 : 1;
+    };
+    GemmEnv v = GEMM_ENV_DEFAULT;
+    // 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32) on every launch
+    // 1 = bf16 operands (round-to-nearest-even in registers), fp32 accumulation: ONE v_mfma_f32_32x32x16_bf16 per 16-k
+    //     block.  Opt-in reduced precision (~3e-3 relative per product; BASELINE's KuaiRec configuration names bf16).
+    // 3 = three bf16 planes per operand (six v_mfma_f32_32x32x16_bf16 per 16-k block) on every LDS-DMA launch
+    // 4 = auto (default): the three-plane form where it is faster, the fp32 MFMA elsewhere.  Both give fp32-equivalent
+    //     results (max-norm error vs float64 4.7e-7 vs 4.3e-7, tools/bench_gemm.py).
+    const char* m = getenv("MMLREC_GEMM_MODE");
+    v.mode = (m && m[0] >= '0' && m[0] <= '3') ? m[0] - '0' : 4;
+    v.panel_on = off("MMLREC_GEMM_PANEL");
+    v.ws_on = off("MMLREC_GEMM_WS");
+    v.nt_mode = num("MMLREC_GEMM_NT", 1);
+    if (v.nt_mode < 0 || v.nt_mode > 3) v.nt_mode = 1;
+    // Workgroups of gemm_nt_kernel per CU.  Two fill the register file (2 x 4 waves x 248 VGPRs): nothing else becomes
+    // resident beside them, so a launch forked beside this one (the table scatter, the table optimizer: HBM-bound, idle
+    // matrix pipe) waits for it.  One per CU leaves half of every SIMD's registers and 76 KiB of LDS to the other branch.
+    v.nt_per_cu = num("MMLREC_NT_PER_CU", 2) == 1 ? 1 : 2;
+    v.glds_on = off("MMLREC_GEMM_GLDS");
+    v.planes_on = num("MMLREC_GEMM_PLANES", 1);  // 0: ignore pre-cut weights (A/B switch)
+    v.force_bn = num("MMLREC_GEMM_BN", 0);
+    v.wgrad_pad = num("MMLREC_WGRAD_LDS_PAD", 0);
+    return v;
+  }();
+  const char* e = getenv("MMLREC_GEMM_OS");
+  env.os_on = (e && e[0] == '0') ? 0 : 1;
+  return env;
 }
-
-static inline int32_t vec_ok(const float* p, int64_t ld) { return (aligned16(p) && (ld % 4 == 0)) ? 1 : 0; }
-
-// 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32) on every launch
-// 1 = bf16 operands (round-to-nearest-even in registers), fp32 accumulation: ONE v_mfma_f32_32x32x16_bf16 per 16-k
-//     block.  Opt-in reduced precision (~3e-3 relative per product; BASELINE's KuaiRec configuration names bf16).
-// 3 = three bf16 planes per operand (six v_mfma_f32_32x32x16_bf16 per 16-k block) on every LDS-DMA launch
-// 4 = auto (default): the three-plane form where it is faster, the fp32 MFMA elsewhere.  Both give fp32-equivalent
-//     results (max-norm error vs float64 4.7e-7 vs 4.3e-7, tools/bench_gemm.py).
-static int g_gemm_mode = -1;
-static int g_wgrad_pad = -1;  // unused dynamic LDS requested by wgrad launches (caps their residency, see launch_tiles)
-static int gemm_mode() {
-  if (g_gemm_mode < 0) {
-    const char* e = getenv("MMLREC_GEMM_MODE");
-    g_gemm_mode = (e && (e[0] == '0' || e[0] == '1' || e[0] == '2' || e[0] == '3')) ? e[0] - '0' : 4;
-  }
-  return g_gemm_mode;
-}
-
-struct TileChoice {
-  int bn, emu;
-};
 
 static thread_local char g_last_kernel[96] = "";
-static void note_kernel(const char* fam, bool arc, bool brc, int bn, int epi, int mode, int bcols = -1,
-                        bool bpl = false) {
-  if (bcols < 0)
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "%s<%s, %s, %d, %d>", fam, arc ? "true" : "false",
-             brc ? "true" : "false", bn, epi);
-  else  // (the symbol as a profiler prints it: every template argument, the defaulted ones too)
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "%s<%s, %s, %d, %d, %d, %s, %s>", fam, arc ? "true" : "false",
-             brc ? "true" : "false", bn, epi, mode, bcols ? "true" : "false", bpl ? "true" : "false");
+// a launch that went out becomes the thread's reported symbol (mml_gemm_last_kernel)
+static int noted(int rc, const GemmLaunch& g, bool report) {
+  if (rc == MML_OK && report) memcpy(g_last_kernel, g.symbol, sizeof(g_last_kernel));
+  return rc;
+}
+static_assert(sizeof(g_last_kernel) == sizeof(GemmLaunch::symbol), "symbol buffers");
+
+template <int EPI, bool A_, bool B_, int N_, bool C_>
+static void launch_pipe(const GemmLaunch& G, const Launch& L, hipStream_t st) {
+  const dim3 g(G.grid), b(256);
+  const size_t dyn = (size_t)G.dyn_lds;
+#ifdef MML_LAB  // ablation builds (tools/lab): one tile width / arithmetic only, to keep compile times short
+  if (G.bpl) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, MML_LAB_EMU, false, (EPI != EPI_SLAB && MML_LAB_EMU == 2)>), g, b, dyn, st, L);
+  else MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, MML_LAB_EMU, false>), g, b, dyn, st, L);
+#else
+  // (K7: nn.Linear weights [N, K] only, gate mode on 128 x 64 tiles only, the two-plane and three-plane forms only)
+  if constexpr (EPI != EPI_SLAB && ((EPI == EPI_FWD) == (B_)) && (EPI == EPI_FWD || N_ == 64)) {
+    if (G.k7) {
+      if (G.emu == 2 && G.bpl) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 2, false, true, true>), g, b, dyn, st, L);
+      else if (G.emu == 2) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 2, false, false, true>), g, b, dyn, st, L);
+      else MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 3, false, false, true>), g, b, dyn, st, L);
+      return;
+    }
+  }
+  if (G.emu == 0) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 0, C_>), g, b, dyn, st, L);
+  else if (G.emu == 1) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 1, C_>), g, b, dyn, st, L);
+  else if (G.emu == 2 && G.bpl) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 2, C_, (EPI != EPI_SLAB)>), g, b, dyn, st, L);
+  else if (G.emu == 2) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 2, C_>), g, b, dyn, st, L);
+  else MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 3, C_>), g, b, dyn, st, L);
+#endif
 }
 
-// planes / kexps (or null): per source of the launch, the pre-cut image of its column operand and the exponent slot
-// (mml_gemm_planes_cut); used when EVERY source has them and the launch runs the two-plane arithmetic on the LDS-DMA path
+// The template dispatch of a planned tile launch (the instantiations live in this file).  Weight-gradient launches are
+// always row-contiguous on both operands, the others reduction-contiguous on A.
 template <int EPI>
-static int launch_tiles(const Launch& Lin, bool arc, bool brc, TileChoice tc, int64_t nblocks, hipStream_t st,
-                        const char* who, const uint32_t* const* planes = nullptr, const int32_t* const* kexps = nullptr,
-                        bool k7 = false) {
-  Launch Lcopy;
-  const Launch* Lp = &Lin;
-  const int bn = tc.bn;
-  if (nblocks <= 0) return MML_OK;
-  if (nblocks > 0x7fffffff) {
-    set_error("%s: grid too large", who);
-    return MML_ERR_ARG;
-  }
-  dim3 g((unsigned)nblocks), b(256);
-  int emu = tc.emu;  // 0 = fp32 MFMA, 1 = bf16 operands, 2 = two scaled fp16 planes, 3 = three bf16 planes
-  if (emu == 3 && gemm_mode() != 3) {  // every operand of the launch comes with its magnitude: two fp16 planes
-    bool all = true;
-    for (int i = 0; i < Lin.n && all; ++i)
-      for (int s = 0; s < Lin.p[i].nsrc && all; ++s)
-        all = Lin.src[Lin.p[i].src0 + s].amaxA != nullptr && Lin.src[Lin.p[i].src0 + s].amaxB != nullptr;
-    if (all) emu = 2;
-  }
-  bool bpl = false;
-  if (EPI != EPI_SLAB && emu == 2 && planes && kexps && pipe_ok(Lin, arc, brc, bn, EPI)) {
-    static int use = -1;
-    if (use < 0) {
-      const char* e = getenv("MMLREC_GEMM_PLANES");  // 0: ignore pre-cut weights (A/B switch)
-      use = e ? atoi(e) : 1;
-    }
-    bpl = use != 0;
-    for (int i = 0; i < Lin.n && bpl; ++i)
-      for (int s = 0; s < Lin.p[i].nsrc && bpl; ++s) {
-        const int si = Lin.p[i].src0 + s;
-        // (one exponent per problem: the kernel reads the first source's)
-        bpl = planes[si] && kexps[si] && aligned16(planes[si]) && kexps[si] == kexps[Lin.p[i].src0];
-      }
-    if (bpl) {
-      Lcopy = Lin;
-      for (int i = 0; i < Lin.n; ++i)
-        for (int s = 0; s < Lin.p[i].nsrc; ++s) {
-          const int si = Lin.p[i].src0 + s;
-          Lcopy.src[si].B = reinterpret_cast<const float*>(planes[si]);
-          Lcopy.src[si].amaxB = reinterpret_cast<const uint32_t*>(kexps[si]);
-        }
-      Lp = &Lcopy;
-    }
-  }
-  const Launch& L = *Lp;
-  const bool bcols = (EPI == EPI_SLAB) && L.n > 0 && L.p[0].bias_cols != 0;  // (uniform per launch: see the wgrad entry)
-  (void)bcols;
-  // The weight-gradient GEMMs run on a side stream next to the HBM-bound table optimizer (trainer.py).  An unused
-  // dynamic-LDS request (mml_gemm_set_wgrad_lds_pad) lowers their residency so that the optimizer's waves co-reside.
-  if (g_wgrad_pad < 0) {
-    const char* e = getenv("MMLREC_WGRAD_LDS_PAD");
-    g_wgrad_pad = e ? atoi(e) : 0;
-  }
-  const size_t dyn = (EPI == EPI_SLAB) ? (size_t)g_wgrad_pad : 0;
-  if (pipe_ok(L, arc, brc, bn, EPI)) {
-    note_kernel("gemm_pipe_kernel", arc, brc, bn, EPI, emu, bcols ? 1 : 0, bpl);
-    // persistent workgroups: one per resident slot (128 x 128 tiles: 2 per CU; 128 x 64: 3), each loops over tiles
-    static int cus = 0;
-    if (cus == 0) {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-        n = 256;
-      cus = n;
-    }
-    const int64_t slots = (int64_t)cus * ((bn == 64 && EPI != EPI_DGRAD && !k7) ? 3 : 2);
-    if (nblocks > slots) g = dim3((unsigned)slots);
-#ifdef MML_LAB  // ablation builds (tools/lab): one tile width / arithmetic only, to keep compile times short
-#define MML_GL(A_, B_)                                                                                            \
-  do {                                                                                                            \
-    if (bpl) MML_LAUNCH((gemm_pipe_kernel<A_, B_, MML_LAB_BN, EPI, MML_LAB_EMU, false, (EPI != EPI_SLAB && MML_LAB_EMU == 2)>), \
-                        g, b, dyn, st, L);                                                                        \
-    else MML_LAUNCH((gemm_pipe_kernel<A_, B_, MML_LAB_BN, EPI, MML_LAB_EMU, false>), g, b, dyn, st, L);           \
-  } while (0)
+static int launch_tiles(const Launch& L, const GemmLaunch& G, hipStream_t st, const char* who) {
+  if (G.family == GEMM_PIPE) {
+#ifdef MML_LAB
+#define MML_GL(A_, B_, C_) launch_pipe<EPI, A_, B_, MML_LAB_BN, false>(G, L, st)
 #else
-#define MML_GL3(A_, B_, N_, C_)                                                              \
-  do {                                                                                       \
-    /* (nn.Linear weights [N, K] only; gate mode on 128 x 64 tiles only: h, g and both gradients of a 128-wide */ \
-    /* tile do not fit the registers next to the accumulators -- the host picks the narrow tiles for it)       */ \
-    if constexpr (EPI != EPI_SLAB && ((EPI == EPI_FWD) == (B_)) && (EPI == EPI_FWD || N_ == 64)) {                 \
-      if (k7) { /* (the two-plane and three-plane forms only: what the engine runs) */            \
-        if (emu == 2 && bpl) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 2, false, true, true>), g, b, dyn, st, L);  \
-        else if (emu == 2) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 2, false, false, true>), g, b, dyn, st, L);   \
-        else if (emu == 3) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 3, false, false, true>), g, b, dyn, st, L);   \
-        else { set_error("%s: the K7 products run on the plane-emulated GEMM forms only", who); return MML_ERR_UNSUPPORTED; } \
-        break;                                                                                    \
-      }                                                                                           \
-    }                                                                                             \
-    if (k7) { set_error("%s: the K7 products need nn.Linear weights ([N, K])", who); return MML_ERR_UNSUPPORTED; }  \
-    if (emu == 0) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 0, C_>), g, b, dyn, st, L);       \
-    else if (emu == 1) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 1, C_>), g, b, dyn, st, L);  \
-    else if (emu == 2 && bpl)                                                                     \
-      MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 2, C_, (EPI != EPI_SLAB)>), g, b, dyn, st, L); \
-    else if (emu == 2) MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 2, C_>), g, b, dyn, st, L);  \
-    else MML_LAUNCH((gemm_pipe_kernel<A_, B_, N_, EPI, 3, C_>), g, b, dyn, st, L);                \
-  } while (0)
-#define MML_GL2(A_, B_, N_)                                  \
-  do {                                                       \
-    if (EPI == EPI_SLAB && bcols) MML_GL3(A_, B_, N_, (EPI == EPI_SLAB)); \
-    else MML_GL3(A_, B_, N_, false);                         \
-  } while (0)
-#define MML_GL(A_, B_)                  \
-  do {                                  \
-    if (bn == 64) MML_GL2(A_, B_, 64);  \
-    else MML_GL2(A_, B_, 128);          \
+#define MML_GL(A_, B_, C_)                                         \
+  do {                                                             \
+    if (G.bn == 64) launch_pipe<EPI, A_, B_, 64, C_>(G, L, st);    \
+    else launch_pipe<EPI, A_, B_, 128, C_>(G, L, st);              \
   } while (0)
 #endif
-    // (weight-gradient launches are always row-contiguous on both operands, the others reduction-contiguous on A)
     if constexpr (EPI == EPI_SLAB) {
-      if (!arc && !brc) MML_GL(false, false);
-      else { set_error("%s: unsupported operand layout", who); return MML_ERR_UNSUPPORTED; }
+      if (G.bcols) MML_GL(false, false, true);
+      else MML_GL(false, false, false);
     } else {
-      if (arc && brc) MML_GL(true, true);
-      else if (arc && !brc) MML_GL(true, false);
-      else { set_error("%s: unsupported operand layout", who); return MML_ERR_UNSUPPORTED; }
+      if (G.brc) MML_GL(true, true, false);
+      else MML_GL(true, false, false);
     }
 #undef MML_GL
-#ifndef MML_LAB
-#undef MML_GL2
-#undef MML_GL3
-#endif
     return check_launch(who);
   }
-#ifdef MML_LAB
-  set_error("%s: lab build has only the direct-to-LDS kernel", who);
-  return MML_ERR_UNSUPPORTED;
-#else
-  // shapes the LDS-DMA path cannot take (reduction extents not a multiple of 16, unaligned operands): register-staged
-  // fp32 MFMA kernel
-  note_kernel("gemm_kernel", arc, brc, bn, EPI, 0);
-#define MML_GO(A_, B_, N_) MML_LAUNCH((gemm_kernel<A_, B_, N_, EPI>), g, b, dyn, st, L)
-  if (arc && brc) { if (bn == 128) MML_GO(true, true, 128); else MML_GO(true, true, 64); }
-  else if (arc && !brc) { if (bn == 128) MML_GO(true, false, 128); else MML_GO(true, false, 64); }
-  else if (!arc && !brc) { if (bn == 128) MML_GO(false, false, 128); else MML_GO(false, false, 64); }
-  else {
-    set_error("%s: unsupported operand layout", who);
-    return MML_ERR_UNSUPPORTED;
-  }
+#ifndef MML_LAB
+  const dim3 g(G.grid), b(256);
+#define MML_GO(A_, B_)                                                                                       \
+  do {                                                                                                       \
+    if (G.bn == 128) MML_LAUNCH((gemm_kernel<A_, B_, 128, EPI>), g, b, (size_t)G.dyn_lds, st, L);            \
+    else MML_LAUNCH((gemm_kernel<A_, B_, 64, EPI>), g, b, (size_t)G.dyn_lds, st, L);                         \
+  } while (0)
+  if (G.arc && G.brc) MML_GO(true, true);
+  else if (G.arc) MML_GO(true, false);
+  else MML_GO(false, false);
 #undef MML_GO
-  return check_launch(who);
 #endif
+  return check_launch(who);
 }
 
-// Tile width and arithmetic of one grouped launch.  kind: 0 fwd, 1 dgrad, 2 wgrad; kred = longest reduction extent.
-// Measured on MI355X at M = 65536 with gemm_pipe_kernel (tools/gsweep.sh, us):
-//                                  fp32 MFMA 128x64 | 128x128     three planes 128x64 | 128x128
-//   L1 4x(240->256)+2x(240->64)  fwd 346|345 wgrad 618|400 dgrad 384|330     fwd 295|262 wgrad 488|286 dgrad 304|241
-//   L2 4x(256->128)              fwd 179|152 wgrad 267|201 dgrad 228|234     fwd 145|113 wgrad 209|154 dgrad 202|197
-//   towers 2x(128->64)           fwd  40| 46 wgrad  93| 70 dgrad  44| 34     fwd  32| 36 wgrad  75| 59 dgrad  34| 27
-// 128x128 tiles run two workgroups per CU (<= 256 VGPRs), 128x64 three.
-static TileChoice pick_tiles(const int32_t* Ns, int n, int kind, int64_t kred, int64_t row_tiles) {
-  static int force = -1;
-  if (force < 0) {
-    const char* e = getenv("MMLREC_GEMM_BN");
-    force = e ? atoi(e) : 0;
-  }
-  const int mode = gemm_mode();
-  TileChoice tc{64, 0};
-#ifdef MML_LAB
-  return TileChoice{MML_LAB_BN, MML_LAB_EMU};
-#endif
-  int64_t pad64 = 0, pad128 = 0;
-  for (int i = 0; i < n; ++i) {
-    pad64 += cdiv(Ns[i], 64) * 64;
-    pad128 += cdiv(Ns[i], 128) * 128;
-  }
-  tc.bn = (pad128 * 100 <= pad64 * 150) ? 128 : 64;  // wide tiles unless > 1/3 of their columns would be padding
-  if (row_tiles * (pad128 / 128) < 1024) tc.bn = 64;  // ... or they would not fill the 512 resident slots twice
-  if (force == 64 || force == 128) tc.bn = force;
-  tc.emu = (mode == 0) ? 0 : (mode == 1 ? 1 : 3);  // (3 becomes 2 in launch_tiles when the magnitudes are there)
-  (void)kind;
-  (void)kred;
-  return tc;
+// the fields of Problem / Source that the rule derived (and decided by)
+static void put_shape(Problem& P, const TileProb& t) {
+  P.M = t.M; P.N = t.N; P.src0 = t.src0; P.nsrc = t.nsrc; P.tiles_n = t.tiles_n; P.tile0 = t.tile0; P.vec_out = t.vec_out;
 }
+static void put_shape(Source& S, const TileSrc& t) { S.Kred = t.Kred; S.vecA = t.vecA; S.vecB = t.vecB; }
 
 }  // namespace mml
 
@@ -1902,11 +1778,44 @@ extern "C" int mml_gemm_set_mode(int32_t mode) {
               "mml_gemm_set_mode: mode must be 0 (fp32 MFMA), 1 (bf16 operands, reduced precision), 2 / 4 (auto: fp32 "
               "emulated from two scaled fp16 planes where the operand magnitudes are given, else from three bf16 "
               "planes) or 3 (three bf16 planes on every LDS-DMA launch)");
-  g_gemm_mode = mode;
+  gemm_env().mode = mode;
   return MML_OK;
 }
 
-extern "C" int mml_gemm_get_mode(void) { return gemm_mode(); }
+extern "C" int mml_gemm_get_mode(void) { return gemm_env().mode; }
+
+extern "C" int mml_gemm_set_panel(int32_t on) {
+  gemm_env().panel_on = on ? 1 : 0;
+  return MML_OK;
+}
+
+extern "C" int mml_gemm_set_ws(int32_t on) {
+  gemm_env().ws_on = on ? 1 : 0;
+  return MML_OK;
+}
+
+extern "C" int mml_gemm_set_nt(int32_t on) {
+  MML_REQUIRE(on >= 0 && on <= 3, "mml_gemm_set_nt: 0 (off), 1 (every qualifying launch: default), 2 (launches of >= 16 tiles) "
+              "or 3 (lab: every qualifying launch on gemm_ntd_kernel)");
+  gemm_env().nt_mode = on;
+  return MML_OK;
+}
+
+extern "C" int mml_gemm_set_wgrad_lds_pad(int32_t bytes) {
+  MML_REQUIRE(bytes >= 0 && bytes <= 64 * 1024, "mml_gemm_set_wgrad_lds_pad: bytes outside [0, 65536]");
+  gemm_env().wgrad_pad = bytes;
+  return MML_OK;
+}
+
+extern "C" const char* mml_gemm_last_kernel(void) { return g_last_kernel; }
+
+// (the per-problem conditions of gemm_nt_kernel: the grouping pass of the host side asks the same question)
+extern "C" int mml_gemm_nt_serves(const mml_gemm_wgrad_desc* desc) { return (desc && nt_problem_ok(*desc)) ? 1 : 0; }
+
+// (the first kernel mml_gemm_grouped_dgrad tries: its mode gate and the kernel's own conditions)
+extern "C" int mml_gemm_os_serves(const mml_gemm_dgrad_desc* d, int32_t n) {
+  return (n > 0 && planes_kernels_on(gemm_env()) && os_serves(d, n, gemm_env())) ? 1 : 0;
+}
 
 extern "C" int mml_gemm_planes_cut(const mml_planes_desc* d, int32_t n, mml_stream_t stream) {
   MML_REQUIRE(n >= 0 && (n == 0 || d), "mml_gemm_planes_cut: bad descriptor array");
@@ -1949,215 +1858,105 @@ extern "C" int mml_gemm_planes_cut(const mml_planes_desc* d, int32_t n, mml_stre
   return MML_OK;
 }
 
-extern "C" const char* mml_gemm_last_kernel(void) { return g_last_kernel; }
+// The families' launchers: each fills its kernel's argument block from the descriptors and launches what the rule
+// planned (gemm_panel.hip, gemm_ws.hip, gemm_os.hip, gemm_nt.hip).
+int mml_gemm_panel_launch(const mml_gemm_fwd_desc* d, const GemmLaunch& g, hipStream_t st);
+int mml_gemm_ws_launch_fwd(const mml_gemm_fwd_desc* d, const GemmLaunch& g, hipStream_t st);
+int mml_gemm_ws_launch_dgrad(const mml_gemm_dgrad_desc* d, const GemmLaunch& g, hipStream_t st);
+int mml_gemm_os_launch(const mml_gemm_dgrad_desc* d, const GemmLaunch& g, hipStream_t st);
+int mml_gemm_nt_launch(const mml_gemm_wgrad_desc* d, const GemmLaunch& g, void* workspace, hipStream_t st);
 
-
-extern "C" int mml_gemm_set_wgrad_lds_pad(int32_t bytes) {
-  MML_REQUIRE(bytes >= 0 && bytes <= 64 * 1024, "mml_gemm_set_wgrad_lds_pad: bytes outside [0, 65536]");
-  g_wgrad_pad = bytes;
-  return MML_OK;
+// a refusal of the rule becomes the call's error text (a launcher's failure has set its own)
+static int routed(int rc, const GemmRefusal& why) {
+  if (rc != MML_OK && why.code) set_error("%s", why.msg);
+  return rc;
 }
 
-// gemm_panel.hip: the activation-stationary kernel for launches whose problems all read ONE input (first DNN layers)
-int mml_gemm_panel_try_fwd(const mml_gemm_fwd_desc* d, int32_t n, hipStream_t st);
-
-// gemm_ws.hip: the weight-stationary kernel for launches whose problems each stream their own input past a weight that
-// fits the LDS (second expert layers, towers, and their input gradients)
-int mml_gemm_ws_try_fwd(const mml_gemm_fwd_desc* d, int32_t n, hipStream_t st);
-int mml_gemm_ws_try_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, hipStream_t st);
-namespace mml { const char* mml_gemm_ws_last_symbol(); }
+static int tiles_fwd(const mml_gemm_fwd_desc* d, const GemmLaunch& g, hipStream_t st) {
+  Launch L{};
+  for (int k = 0; k < g.count; ++k) {
+    const mml_gemm_fwd_desc& q = d[g.first + k];
+    Problem& P = L.p[k];
+    Source& S0 = L.src[k];
+    put_shape(P, g.p[k]);
+    put_shape(S0, g.s[k]);
+    S0.A = q.A; S0.lda = q.lda; S0.B = q.W; S0.ldb = q.ldw;
+    S0.amaxA = q.amax_a; S0.amaxB = q.amax_w;
+    if (g.bpl) {  // the pre-cut image of the weight and its exponent slot ([K, N] weights: the MML_PLANES_COLS image, K6)
+      S0.B = reinterpret_cast<const float*>(q.w_planes);
+      S0.amaxB = reinterpret_cast<const uint32_t*>(q.w_kexp);
+    }
+    P.amax_out = q.amax_out;
+    P.C = q.C; P.ldc = q.ldc; P.bias = q.bias; P.act = q.act;
+    P.mask = (q.act == MML_ACT_RELU) ? q.relu_mask : nullptr; P.ldmask = q.ldmask;
+    if (q.mul || q.prod) {  // K7: prod = C * mul from the same epilogue (see Problem)
+      P.Y = q.mul; P.ldy = q.ldmul; P.bias_slab = q.prod; P.slab_off = q.ldprod; P.amax_out2 = q.amax_prod;
+    }
+  }
+  L.n = g.count;
+  L.total_ntiles = g.total_ntiles;
+  L.tiles_m = g.tiles_m;
+  return launch_tiles<EPI_FWD>(L, g, st, "mml_gemm_grouped_fwd");
+}
 
 extern "C" int mml_gemm_grouped_fwd(const mml_gemm_fwd_desc* d, int32_t n, mml_stream_t stream) {
   MML_REQUIRE(n >= 0 && (n == 0 || d), "mml_gemm_grouped_fwd: bad descriptor array");
-  if (n > 0 && gemm_mode() >= 2 && gemm_mode() != 3) {  // (auto / two-plane arithmetic only)
-    int rc = mml_gemm_panel_try_fwd(d, n, to_stream(stream));
-    if (rc != MML_ERR_UNSUPPORTED) {
-      if (rc == MML_OK) snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_panel_kernel");
-      return rc;
-    }
-    rc = mml_gemm_ws_try_fwd(d, n, to_stream(stream));
-    if (rc != MML_ERR_UNSUPPORTED) {
-      if (rc == MML_OK) snprintf(g_last_kernel, sizeof(g_last_kernel), "%s", mml::mml_gemm_ws_last_symbol());
-      return rc;
-    }
-  }
-  // split into runs of <= MML_MAX_GROUP problems with a uniform weight layout
-  int i = 0;
-  while (i < n) {
-    int j = i;
-    int32_t Ns[MML_MAX_GROUP];
-    Launch L{};
-    bool any_k7 = false;
-    const uint32_t* planes[MAX_SOURCES] = {};
-    const int32_t* kexps[MAX_SOURCES] = {};
-    while (j < n && j - i < MML_MAX_GROUP && d[j].w_kn == d[i].w_kn && d[j].M == d[i].M) {
-      const mml_gemm_fwd_desc& q = d[j];
-      MML_REQUIRE(q.A && q.W && q.C, "mml_gemm_grouped_fwd: null pointer in problem %d", j);
-      MML_REQUIRE(q.M >= 0 && q.N > 0 && q.K > 0, "mml_gemm_grouped_fwd: bad sizes in problem %d", j);
-      MML_REQUIRE(q.lda >= q.K && q.ldc >= q.N && q.ldw >= (q.w_kn ? q.N : q.K),
-                  "mml_gemm_grouped_fwd: leading dimension too small in problem %d", j);
-      Problem& P = L.p[j - i];
-      P.nsrc = 1;
-      P.src0 = j - i;
-      Source& S0 = L.src[j - i];
-      S0.A = q.A; S0.lda = q.lda; S0.B = q.W; S0.ldb = q.ldw; S0.Kred = q.K;
-      S0.vecA = vec_ok(q.A, q.lda); S0.vecB = vec_ok(q.W, q.ldw);
-      S0.amaxA = q.amax_a; S0.amaxB = q.amax_w;
-      planes[j - i] = q.w_planes;  // ([K, N] weights: the MML_PLANES_COLS image, K6)
-      kexps[j - i] = q.w_kexp;
-      P.amax_out = q.amax_out;
-      P.M = q.M; P.N = q.N; P.C = q.C; P.ldc = q.ldc; P.bias = q.bias; P.act = q.act;
-      MML_REQUIRE(!q.relu_mask || q.ldmask * 32 >= q.N, "mml_gemm_grouped_fwd: ldmask too small in problem %d", j);
-      P.mask = (q.act == MML_ACT_RELU) ? q.relu_mask : nullptr; P.ldmask = q.ldmask;
-      P.vec_out = (vec_ok(q.C, q.ldc) && q.N % 4 == 0 && (!q.bias || aligned16(q.bias))) ? 1 : 0;
-      if (q.mul || q.prod) {  // K7: prod = C * mul from the same epilogue (see Problem)
-        MML_REQUIRE(q.mul && q.prod && q.ldmul >= q.N && q.ldprod >= q.N,
-                    "mml_gemm_grouped_fwd: problem %d needs both mul and prod, with pitches >= N", j);
-        MML_REQUIRE(P.vec_out && vec_ok(q.mul, q.ldmul) && vec_ok(q.prod, q.ldprod),
-                    "mml_gemm_grouped_fwd: mul / prod of problem %d need 16-byte aligned operands and N %% 4 == 0", j);
-        P.Y = q.mul; P.ldy = q.ldmul; P.bias_slab = q.prod; P.slab_off = q.ldprod; P.amax_out2 = q.amax_prod;
-        any_k7 = true;
-      }
-      Ns[j - i] = q.N;
-      ++j;
-    }
-    L.n = j - i;
-    int64_t kred = 0;
-    for (int k = 0; k < L.n; ++k) kred = L.src[k].Kred > kred ? L.src[k].Kred : kred;
-    const TileChoice tc = pick_tiles(Ns, L.n, 0, kred, cdiv(d[i].M, BM));
-    const int bn = tc.bn;
-    int t = 0;
-    for (int k = 0; k < L.n; ++k) {
-      L.p[k].tiles_n = (int)cdiv(L.p[k].N, bn);
-      L.p[k].tile0 = t;
-      t += L.p[k].tiles_n;
-    }
-    L.total_ntiles = t;
-    L.tiles_m = (int)cdiv(d[i].M, BM);
-    if (any_k7 && !pipe_ok(L, true, d[i].w_kn == 0, bn, EPI_FWD)) {
-      set_error("mml_gemm_grouped_fwd: mul / prod need the LDS-DMA kernel (K %% 16 == 0, 16-byte aligned operands)");
-      return MML_ERR_UNSUPPORTED;
-    }
-    int rc = launch_tiles<EPI_FWD>(L, true, d[i].w_kn == 0, tc, (int64_t)L.tiles_m * t, to_stream(stream),
-                                   "mml_gemm_grouped_fwd", planes, kexps, any_k7);
-    if (rc) return rc;
-    i = j;
-  }
-  return MML_OK;
+  GemmRefusal why;
+  return routed(route_fwd(d, n, gemm_env(), device_cus(), why,
+                          [&](const GemmLaunch& g, const mml_gemm_fwd_desc* q) {
+                            const int rc = g.family == GEMM_PANEL ? mml_gemm_panel_launch(q, g, to_stream(stream))
+                                           : g.family == GEMM_WS  ? mml_gemm_ws_launch_fwd(q, g, to_stream(stream))
+                                                                  : tiles_fwd(q, g, to_stream(stream));
+                            // (a ragged batch reports the panel kernel, not its last rows' launch)
+                            return noted(rc, g, g.row0 == 0);
+                          }),
+                why);
 }
 
-// gemm_os.hip: the output-stationary kernel for ONE wide input gradient summed over many sources (d(dnn_input): every
-// expert's and gate's first layer feeds it)
-int mml_gemm_os_try_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, hipStream_t st);
-bool mml_gemm_os_takes(const mml_gemm_dgrad_desc* d, int32_t n);
-
-static bool planes_kernels_on() { return gemm_mode() >= 2 && gemm_mode() != 3; }  // (auto / two-plane arithmetic only)
-
-// (the first kernel mml_gemm_grouped_dgrad tries: its mode gate and the kernel's own conditions)
-extern "C" int mml_gemm_os_serves(const mml_gemm_dgrad_desc* d, int32_t n) {
-  return (n > 0 && planes_kernels_on() && mml_gemm_os_takes(d, n)) ? 1 : 0;
+static int tiles_dgrad(const mml_gemm_dgrad_desc* d, const GemmLaunch& g, hipStream_t st) {
+  Launch L{};
+  for (int k = 0; k < g.count; ++k) {
+    const mml_gemm_dgrad_desc& q = d[g.first + k];
+    Problem& P = L.p[k];
+    put_shape(P, g.p[k]);
+    for (int s = 0; s < q.n_src; ++s) {
+      Source& S = L.src[P.src0 + s];
+      put_shape(S, g.s[P.src0 + s]);
+      S.A = q.dC[s]; S.lda = q.lddc[s]; S.B = q.W[s]; S.ldb = q.ldw[s];
+      S.amaxA = q.amax_dc[s]; S.amaxB = q.amax_w[s];
+      if (g.bpl) {  // ([K, N] weights: the MML_PLANES_ROWS image, K6)
+        S.B = reinterpret_cast<const float*>(q.w_planes[s]);
+        S.amaxB = reinterpret_cast<const uint32_t*>(q.w_kexp[s]);
+      }
+    }
+    P.amax_out = q.amax_out;
+    P.C = q.dA; P.ldc = q.ldda; P.Y = q.Y; P.ldy = q.ldy; P.act = q.act;
+    P.mask = const_cast<uint32_t*>(q.relu_mask); P.ldmask = q.ldmask;
+    P.accumulate = q.accumulate;
+    if (q.gate_h) {  // K7 backward: the gradients of the two factors of the gated input (see Problem)
+      P.C = q.d_h; P.ldc = q.ld_dh; P.Y = q.gate_h; P.ldy = q.ld_h; P.act = q.act_h; P.accumulate = q.acc_h;
+      P.mask = nullptr; P.ldmask = q.ld_g;  // (ldmask carries the pitch of g in gate mode)
+      P.bias = q.gate_g; P.bias_slab = q.d_g; P.slab_off = q.ld_dg; P.tiles_m = q.act_g; P.bias_cols = q.acc_g;
+      P.amax_out = q.amax_dh; P.amax_out2 = q.amax_dg;
+    }
+  }
+  L.n = g.count;
+  L.total_ntiles = g.total_ntiles;
+  L.tiles_m = g.tiles_m;
+  return launch_tiles<EPI_DGRAD>(L, g, st, "mml_gemm_grouped_dgrad");
 }
 
 extern "C" int mml_gemm_grouped_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, mml_stream_t stream) {
   MML_REQUIRE(n >= 0 && (n == 0 || d), "mml_gemm_grouped_dgrad: bad descriptor array");
-  if (n > 0 && planes_kernels_on()) {
-    int rc = mml_gemm_os_try_dgrad(d, n, to_stream(stream));
-    if (rc != MML_ERR_UNSUPPORTED) {
-      if (rc == MML_OK) snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_os_kernel");
-      return rc;
-    }
-    rc = mml_gemm_ws_try_dgrad(d, n, to_stream(stream));
-    if (rc != MML_ERR_UNSUPPORTED) {
-      if (rc == MML_OK) snprintf(g_last_kernel, sizeof(g_last_kernel), "%s", mml::mml_gemm_ws_last_symbol());
-      return rc;
-    }
-  }
-  int i = 0;
-  while (i < n) {
-    int j = i;
-    int32_t Ns[MML_MAX_GROUP];
-    Launch L{};
-    const int32_t lay = d[i].n_src > 0 ? d[i].w_kn[0] : 0;
-    int nsources = 0;
-    bool any_k7 = false;
-    const uint32_t* planes[MAX_SOURCES] = {};
-    const int32_t* kexps[MAX_SOURCES] = {};
-    while (j < n && j - i < MML_MAX_GROUP && d[j].M == d[i].M) {
-      const mml_gemm_dgrad_desc& q = d[j];
-      MML_REQUIRE((q.dA || q.gate_h) && q.n_src >= 1 && q.n_src <= MML_MAX_SRC, "mml_gemm_grouped_dgrad: problem %d malformed", j);
-      MML_REQUIRE(q.M >= 0 && q.K > 0 && q.ldda >= q.K, "mml_gemm_grouped_dgrad: bad sizes in problem %d", j);
-      MML_REQUIRE(q.act == MML_ACT_NONE || q.Y || q.relu_mask, "mml_gemm_grouped_dgrad: act set but Y null in problem %d", j);
-      bool same = true;
-      for (int s = 0; s < q.n_src; ++s) same = same && (q.w_kn[s] == lay);
-      if ((!same || nsources + q.n_src > MAX_SOURCES) && j > i) break;
-      MML_REQUIRE(same, "mml_gemm_grouped_dgrad: mixed weight layouts inside problem %d", j);
-      Problem& P = L.p[j - i];
-      P.nsrc = q.n_src;
-      P.src0 = nsources;
-      for (int s = 0; s < q.n_src; ++s) {
-        MML_REQUIRE(q.dC[s] && q.W[s] && q.N[s] > 0, "mml_gemm_grouped_dgrad: null source %d in problem %d", s, j);
-        Source& S = L.src[nsources++];
-        S.A = q.dC[s]; S.lda = q.lddc[s]; S.B = q.W[s]; S.ldb = q.ldw[s];
-        S.Kred = q.N[s];
-        S.vecA = vec_ok(q.dC[s], q.lddc[s]); S.vecB = vec_ok(q.W[s], q.ldw[s]);
-        S.amaxA = q.amax_dc[s]; S.amaxB = q.amax_w[s];
-        planes[nsources - 1] = q.w_planes[s];  // ([K, N] weights: the MML_PLANES_ROWS image, K6)
-        kexps[nsources - 1] = q.w_kexp[s];
-      }
-      P.amax_out = q.amax_out;
-      P.M = q.M; P.N = q.K; P.C = q.dA; P.ldc = q.ldda; P.Y = q.Y; P.ldy = q.ldy; P.act = q.act;
-      MML_REQUIRE(!q.relu_mask || (q.act == MML_ACT_RELU && q.ldmask * 32 >= q.K),
-                  "mml_gemm_grouped_dgrad: relu_mask needs act == RELU and ldmask >= K/32 (problem %d)", j);
-      P.mask = const_cast<uint32_t*>(q.relu_mask); P.ldmask = q.ldmask;
-      P.vec_out = (vec_ok(q.dA, q.ldda) && q.K % 4 == 0 && (!q.Y || vec_ok(q.Y, q.ldy))) ? 1 : 0;
-      P.accumulate = q.accumulate;
-      if (q.gate_h) {  // K7 backward: the gradients of the two factors of the gated input (see Problem)
-        MML_REQUIRE(q.gate_g && q.d_h && q.d_g && q.ld_h >= q.K && q.ld_g >= q.K && q.ld_dh >= q.K && q.ld_dg >= q.K,
-                    "mml_gemm_grouped_dgrad: gate mode of problem %d needs gate_g, d_h, d_g and pitches >= K", j);
-        MML_REQUIRE(q.K % 4 == 0 && vec_ok(q.gate_h, q.ld_h) && vec_ok(q.gate_g, q.ld_g) && vec_ok(q.d_h, q.ld_dh) &&
-                        vec_ok(q.d_g, q.ld_dg),
-                    "mml_gemm_grouped_dgrad: gate mode of problem %d needs 16-byte aligned operands and K %% 4 == 0", j);
-        P.C = q.d_h; P.ldc = q.ld_dh; P.Y = q.gate_h; P.ldy = q.ld_h; P.act = q.act_h; P.accumulate = q.acc_h;
-        P.mask = nullptr; P.ldmask = q.ld_g;  // (ldmask carries the pitch of g in gate mode)
-        P.bias = q.gate_g; P.bias_slab = q.d_g; P.slab_off = q.ld_dg; P.tiles_m = q.act_g; P.bias_cols = q.acc_g;
-        P.amax_out = q.amax_dh; P.amax_out2 = q.amax_dg;
-        P.vec_out = 1;
-        any_k7 = true;
-      } else {
-        MML_REQUIRE(q.dA, "mml_gemm_grouped_dgrad: problem %d has no dA", j);
-      }
-      Ns[j - i] = q.K;
-      ++j;
-    }
-    L.n = j - i;
-    int64_t kred = 0;
-    for (int k = 0; k < L.n; ++k) {
-      int64_t sum = 0;
-      for (int s2 = 0; s2 < L.p[k].nsrc; ++s2) sum += L.src[L.p[k].src0 + s2].Kred;
-      kred = sum > kred ? sum : kred;
-    }
-    TileChoice tc = pick_tiles(Ns, L.n, 1, kred, cdiv(d[i].M, BM));
-    if (any_k7) tc.bn = 64;  // (gate mode: see launch_tiles)
-    const int bn = tc.bn;
-    int t = 0;
-    for (int k = 0; k < L.n; ++k) {
-      L.p[k].tiles_n = (int)cdiv(L.p[k].N, bn);
-      L.p[k].tile0 = t;
-      t += L.p[k].tiles_n;
-    }
-    L.total_ntiles = t;
-    L.tiles_m = (int)cdiv(d[i].M, BM);
-    if (any_k7 && !pipe_ok(L, true, lay == 1, bn, EPI_DGRAD)) {
-      set_error("mml_gemm_grouped_dgrad: gate mode needs the LDS-DMA kernel (N_s %% 16 == 0, 16-byte aligned operands)");
-      return MML_ERR_UNSUPPORTED;
-    }
-    // col operand = W: reduction index is W's row for [N,K] (not contiguous) and contiguous for [K,N]
-    int rc = launch_tiles<EPI_DGRAD>(L, true, lay == 1, tc, (int64_t)L.tiles_m * t, to_stream(stream),
-                                     "mml_gemm_grouped_dgrad", planes, kexps, any_k7);
-    if (rc) return rc;
-    i = j;
-  }
-  return MML_OK;
+  GemmRefusal why;
+  return routed(route_dgrad(d, n, gemm_env(), device_cus(), why,
+                            [&](const GemmLaunch& g, const mml_gemm_dgrad_desc* q) {
+                              return noted(g.family == GEMM_OS   ? mml_gemm_os_launch(q, g, to_stream(stream))
+                                           : g.family == GEMM_WS ? mml_gemm_ws_launch_dgrad(q, g, to_stream(stream))
+                                                                 : tiles_dgrad(q, g, to_stream(stream)),
+                                           g, true);
+                            }),
+                why);
 }
 
 extern "C" int mml_pep_gate_fwd(const mml_gemm_fwd_desc* d, int32_t n, mml_stream_t stream) {
@@ -2189,64 +1988,61 @@ extern "C" int mml_pep_gate_bwd(const mml_gemm_dgrad_desc* d, int32_t n, mml_str
   return mml_gemm_grouped_dgrad(d, n, stream);
 }
 
-// wgrad planning shared by the workspace query and the launch
-namespace {
-struct WgradPlan {
-  int bn, emu, S, chunk;
-  int64_t total_tiles;
-  int64_t slab_floats;  // all problems, all splits, incl. bias slabs
-};
-WgradPlan plan_wgrad(const mml_gemm_wgrad_desc* d, int i, int j) {
-  WgradPlan w{};
-  int32_t cols[MML_MAX_GROUP];
-  for (int k = i; k < j; ++k) cols[k - i] = d[k].w_kn ? d[k].N : d[k].K;
-  int64_t rt = 0;
-  for (int k = i; k < j; ++k) rt = cdiv(d[k].w_kn ? d[k].K : d[k].N, BM) > rt ? cdiv(d[k].w_kn ? d[k].K : d[k].N, BM) : rt;
-  const TileChoice tc = pick_tiles(cols, j - i, 2, d[i].M, rt * cdiv(d[i].M, 8 * BK));
-  w.bn = tc.bn;
-  w.emu = tc.emu;
-  int64_t tiles = 0, out_elems = 0, bias_elems = 0;
-  for (int k = i; k < j; ++k) {
-    const int rows = d[k].w_kn ? d[k].K : d[k].N, cls = d[k].w_kn ? d[k].N : d[k].K;
-    tiles += cdiv(rows, BM) * cdiv(cls, w.bn);
-    out_elems += (int64_t)d[k].N * d[k].K;
-    if (d[k].dbias) bias_elems += d[k].N;
-  }
-  w.total_tiles = tiles;
-  const int64_t M = d[i].M;
-  int64_t S = tiles > 0 ? (w.bn == 128 ? 512 : 768) / tiles : 1;  // one batch chunk per resident (persistent) workgroup
-  const int64_t maxS = cdiv(M, 8 * BK);      // at least 256 batch rows per split
-  if (S > maxS) S = maxS;
-  if (S < 1) S = 1;
-  int64_t chunk = cdiv(cdiv(M, S), BK) * BK;
-  if (chunk < BK) chunk = BK;
-  S = cdiv(M, chunk);
-  if (S < 1) S = 1;
-  w.S = (int)S;
-  w.chunk = (int)chunk;
-  w.slab_floats = S * (out_elems + bias_elems);
-  return w;
-}
-}  // namespace
-
 extern "C" int64_t mml_gemm_grouped_wgrad_workspace_bytes(const mml_gemm_wgrad_desc* d, int32_t n) {
-  if (n <= 0 || !d) return 0;
-  int64_t best = 0;
-  int i = 0;
-  while (i < n) {
-    int j = i;
-    while (j < n && j - i < MML_MAX_GROUP && d[j].M == d[i].M && d[j].w_kn == d[i].w_kn) ++j;
-    WgradPlan w = plan_wgrad(d, i, j);
-    best += ((w.slab_floats * 4 + 255) / 256) * 256;  // groups are laid out one after another (phased launches)
-    i = j;
-  }
-  return best + 256;
+  return wgrad_workspace_bytes(d, n, gemm_env());
 }
 
-// gemm_nt.hip: weight gradients cut once per workgroup, fragments through the transposing LDS read (large batches, both
-// operand magnitudes known)
-int mml_gemm_nt_try_wgrad(const mml_gemm_wgrad_desc* d, int32_t n, void* workspace, int64_t workspace_bytes, int32_t phase,
-                          hipStream_t st);
+// one run of a weight-gradient call on the tile kernel: the partial tiles into its piece of the workspace, their reduction
+static int tiles_wgrad(const mml_gemm_wgrad_desc* d, const GemmLaunch& g, void* workspace, hipStream_t st) {
+  Launch L{};
+  ReduceLaunch R{};
+  L.n = g.count;
+  L.splits = g.S;
+  L.chunk = g.chunk;
+  L.slab = reinterpret_cast<float*>(static_cast<char*>(workspace) + g.ws_off);
+  int64_t off = 0, rstart = 0;
+  for (int k = 0; k < g.count; ++k) {
+    const mml_gemm_wgrad_desc& q = d[g.first + k];
+    Problem& P = L.p[k];
+    Source& S = L.src[k];
+    put_shape(P, g.p[k]);
+    put_shape(S, g.s[k]);
+    P.tiles_m = g.p[k].tiles_m;
+    // rows of the output tile come from dC^T (n) unless the weight is stored [K,N]
+    if (!q.w_kn) {
+      S.A = q.dC; S.lda = q.lddc; S.B = q.A; S.ldb = q.lda;
+      S.amaxA = q.amax_dc; S.amaxB = q.amax_a;
+    } else {
+      S.A = q.A; S.lda = q.lda; S.B = q.dC; S.ldb = q.lddc;
+      S.amaxA = q.amax_a; S.amaxB = q.amax_dc;
+    }
+    P.slab_off = off;
+    P.bias_cols = q.w_kn ? 1 : 0;
+    const int64_t elems = (int64_t)q.N * q.K;
+    ReduceSeg& w = R.seg[R.n++];
+    w.slab = L.slab + off; w.out = q.dW; w.n = elems; w.cols = q.w_kn ? q.N : q.K; w.ldo = q.lddw;
+    w.S = g.S; w.sstride = elems;
+    w.accumulate = q.accumulate; w.start = rstart;
+    rstart += elems;
+    off += (int64_t)g.S * elems;
+    P.bias_slab = nullptr;
+    if (q.dbias) {
+      P.bias_slab = L.slab + off;
+      ReduceSeg& b = R.seg[R.n++];
+      b.slab = L.slab + off; b.out = q.dbias; b.n = q.N; b.cols = q.N; b.ldo = q.N;
+      b.S = g.S; b.sstride = q.N;
+      b.accumulate = q.accumulate; b.start = rstart;
+      rstart += q.N;
+      off += (int64_t)g.S * q.N;
+    }
+  }
+  L.total_ntiles = g.total_ntiles;
+  R.total = rstart;
+  int rc = MML_OK;
+  if (g.partials) rc = launch_tiles<EPI_SLAB>(L, g, st, "mml_gemm_grouped_wgrad");
+  if (rc == MML_OK && g.reduce) rc = launch_slab_reduce(R, st, "mml_gemm_grouped_wgrad(reduce)");
+  return rc;
+}
 
 extern "C" int mml_gemm_grouped_wgrad_phase(const mml_gemm_wgrad_desc* d, int32_t n, void* workspace,
                                             int64_t workspace_bytes, int32_t phase, mml_stream_t stream) {
@@ -2254,89 +2050,14 @@ extern "C" int mml_gemm_grouped_wgrad_phase(const mml_gemm_wgrad_desc* d, int32_
   MML_REQUIRE(phase >= 0 && phase <= 2, "mml_gemm_grouped_wgrad_phase: phase must be 0 (both), 1 (partials) or 2 (reduce)");
   if (n == 0) return MML_OK;
   MML_REQUIRE(workspace && aligned16(workspace), "mml_gemm_grouped_wgrad: workspace null or misaligned");
-  if (gemm_mode() >= 2 && gemm_mode() != 3) {  // (auto / two-plane arithmetic only)
-    const int rc = mml_gemm_nt_try_wgrad(d, n, workspace, workspace_bytes, phase, to_stream(stream));
-    if (rc != MML_ERR_UNSUPPORTED) {
-      if (rc == MML_OK && phase != 2) snprintf(g_last_kernel, sizeof(g_last_kernel), "gemm_nt_kernel");
-      return rc;
-    }
-  }
-  int i = 0;
-  int64_t ws_off = 0;  // bytes: every group of problems owns its own piece of the workspace
-  while (i < n) {
-    int j = i;
-    while (j < n && j - i < MML_MAX_GROUP && d[j].M == d[i].M && d[j].w_kn == d[i].w_kn) ++j;
-    WgradPlan w = plan_wgrad(d, i, j);
-    MML_REQUIRE(ws_off + w.slab_floats * 4 <= workspace_bytes, "mml_gemm_grouped_wgrad: workspace %lld < %lld bytes",
-                (long long)workspace_bytes, (long long)(ws_off + w.slab_floats * 4));
-    Launch L{};
-    ReduceLaunch R{};
-    L.n = j - i;
-    L.splits = w.S;
-    L.chunk = w.chunk;
-    L.slab = reinterpret_cast<float*>(static_cast<char*>(workspace) + ws_off);
-    ws_off += ((w.slab_floats * 4 + 255) / 256) * 256;
-    int64_t off = 0, rstart = 0;
-    int t = 0;
-    for (int k = i; k < j; ++k) {
-      const mml_gemm_wgrad_desc& q = d[k];
-      MML_REQUIRE(q.dC && q.A && q.dW, "mml_gemm_grouped_wgrad: null pointer in problem %d", k);
-      MML_REQUIRE(q.M >= 0 && q.N > 0 && q.K > 0, "mml_gemm_grouped_wgrad: bad sizes in problem %d", k);
-      MML_REQUIRE(q.lddc >= q.N && q.lda >= q.K && q.lddw >= (q.w_kn ? q.N : q.K),
-                  "mml_gemm_grouped_wgrad: leading dimension too small in problem %d", k);
-      Problem& P = L.p[k - i];
-      P.nsrc = 1;
-      P.src0 = k - i;
-      Source& S = L.src[k - i];
-      // rows of the output tile come from dC^T (n) unless the weight is stored [K,N]; both operands are
-      // batch-major in memory, i.e. NOT reduction-contiguous.
-      if (!q.w_kn) {
-        S.A = q.dC; S.lda = q.lddc; S.B = q.A; S.ldb = q.lda;
-        S.amaxA = q.amax_dc; S.amaxB = q.amax_a;
-        P.M = q.N; P.N = q.K;
-      } else {
-        S.A = q.A; S.lda = q.lda; S.B = q.dC; S.ldb = q.lddc;
-        S.amaxA = q.amax_a; S.amaxB = q.amax_dc;
-        P.M = q.K; P.N = q.N;
-      }
-      S.Kred = q.M;
-      S.vecA = vec_ok(S.A, S.lda); S.vecB = vec_ok(S.B, S.ldb);
-      P.tiles_m = (int)cdiv(P.M, BM);
-      P.tiles_n = (int)cdiv(P.N, w.bn);
-      P.tile0 = t;
-      t += P.tiles_m * P.tiles_n;
-      P.slab_off = off;
-      P.bias_cols = q.w_kn ? 1 : 0;
-      const int64_t elems = (int64_t)q.N * q.K;
-      ReduceSeg& g = R.seg[R.n++];
-      g.slab = L.slab + off; g.out = q.dW; g.n = elems; g.cols = q.w_kn ? q.N : q.K; g.ldo = q.lddw;
-      g.S = w.S; g.sstride = elems;
-      g.accumulate = q.accumulate; g.start = rstart;
-      rstart += elems;
-      off += (int64_t)w.S * elems;
-      P.bias_slab = nullptr;
-      if (q.dbias) {
-        P.bias_slab = L.slab + off;
-        ReduceSeg& b = R.seg[R.n++];
-        b.slab = L.slab + off; b.out = q.dbias; b.n = q.N; b.cols = q.N; b.ldo = q.N;
-        b.S = w.S; b.sstride = q.N;
-        b.accumulate = q.accumulate; b.start = rstart;
-        rstart += q.N;
-        off += (int64_t)w.S * q.N;
-      }
-    }
-    L.total_ntiles = t;
-    R.total = rstart;
-    int rc = MML_OK;
-    if (phase != 2)
-      rc = launch_tiles<EPI_SLAB>(L, false, false, TileChoice{w.bn, w.emu}, (int64_t)t * w.S, to_stream(stream),
-                                  "mml_gemm_grouped_wgrad");
-    if (rc) return rc;
-    if (phase != 1) rc = launch_slab_reduce(R, to_stream(stream), "mml_gemm_grouped_wgrad(reduce)");
-    if (rc) return rc;
-    i = j;
-  }
-  return MML_OK;
+  GemmRefusal why;
+  return routed(route_wgrad(d, n, workspace_bytes, phase, gemm_env(), device_cus(), why,
+                            [&](const GemmLaunch& g, const mml_gemm_wgrad_desc* q) {
+                              return noted(g.family == GEMM_NT ? mml_gemm_nt_launch(q, g, workspace, to_stream(stream))
+                                                               : tiles_wgrad(q, g, workspace, to_stream(stream)),
+                                           g, g.partials);
+                            }),
+                why);
 }
 
 extern "C" int mml_gemm_grouped_wgrad(const mml_gemm_wgrad_desc* d, int32_t n, void* workspace,

@@ -595,16 +595,6 @@ __global__ __launch_bounds__(256) void g16_reduce_kernel(const G16RedLaunch L) {
 }
 
 static thread_local const char* g16_last = "";
-static int g16_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
 
 }  // namespace mml
 
@@ -784,7 +774,7 @@ static int g16_wgrad_plan(const mml_g16_wgrad_desc* d, int32_t n, int* slabs_out
   const int steps = d[0].M / 64;
   // slabs: enough workgroups for two per CU, at least four 64-row steps each, at most 32 (the partial tiles are
   // written and read back: 64 KiB per tile and slab)
-  int64_t slabs = (2 * (int64_t)g16_cus()) / tiles;
+  int64_t slabs = (2 * (int64_t)device_cus()) / tiles;
   if (slabs > steps / 4) slabs = steps / 4;
   if (slabs > 32) slabs = 32;
   if (slabs < 1) slabs = 1;

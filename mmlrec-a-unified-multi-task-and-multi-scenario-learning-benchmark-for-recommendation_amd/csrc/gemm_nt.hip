@@ -19,9 +19,9 @@
 //   * partial tiles go to the caller's workspace, scaled back exactly, and are summed in slab order (bitwise
 //     reproducible) by nt_reduce_kernel.
 // Serves launches whose problems carry both magnitudes, nn.Linear weight layout, M % 32 == 0, M >= 16 384, N % 32 == 0,
-// K % 4 == 0 and 16-byte aligned rows; everything else stays on the tile kernel (mml_gemm_nt_try_wgrad returns
-// MML_ERR_UNSUPPORTED).
+// K % 4 == 0 and 16-byte aligned rows; everything else stays on the tile kernel (gemm_route.hpp: nt_serves).
 #include "common.hpp"
+#include "gemm_route.hpp"
 #include "lds_async.hpp"
 
 namespace mml {
@@ -33,8 +33,6 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4_t;
 
 // Problems per launch.  Round 6: 3 x MML_MAX_GROUP -- PepNet's 40-odd weight gradients were three launch + reduction pairs
 // (377 us of its 1.67 ms step); the launch descriptor is 3.9 KB of kernel arguments (limit 4 KB), read from device memory.
-constexpr int NT_MAX_GROUP = 48;
-constexpr int NT_STEP = 32;          // batch rows per step
 constexpr int NT_PLANE = NT_STEP * 128;   // fp16 elements of one plane image ([32 rows][128 columns])
 constexpr int NT_STAGE = 4 * NT_PLANE;    // dC h, dC l, A h, A l
 
@@ -561,92 +559,20 @@ __global__ __launch_bounds__(256) void nt_reduce_kernel(const NtRedLaunch L) {
 // steps): 8.8 VALU instructions per MFMA against 11.9, MFMA pipe busy 0.32 against 0.34, no LDS bank conflicts either way,
 // the same L2 requests and hit rate (70 %): neither kernel is bound by its cuts or by HBM; both wait on the short
 // dependent chain read -> MFMA -> next read at two to three waves per SIMD.
-constexpr int NT_MIN_TILES = 16;
-static int g_nt_on = -1;
-static int nt_mode() {
-  if (g_nt_on < 0) {
-    const char* e = getenv("MMLREC_GEMM_NT");
-    g_nt_on = e ? atoi(e) : 1;
-    if (g_nt_on < 0 || g_nt_on > 3) g_nt_on = 1;
-  }
-  return g_nt_on;
-}
-// Workgroups per CU.  Two fill the register file (2 x 4 waves x 248 VGPRs): nothing else becomes resident beside them, so a
-// launch forked beside this one (the table scatter, the table optimizer: HBM-bound, idle matrix pipe) waits for it.  One
-// workgroup per CU leaves half of every SIMD's registers and 76 KiB of LDS to the other branch.
-static int g_nt_per_cu = 0;
-static int nt_per_cu() {
-  if (!g_nt_per_cu) {
-    const char* e = getenv("MMLREC_NT_PER_CU");
-    g_nt_per_cu = (e && atoi(e) == 1) ? 1 : 2;
-  }
-  return g_nt_per_cu;
-}
-static int nt_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
-
 }  // namespace mml
 
 using namespace mml;
 
-// the per-problem conditions (mml_gemm_nt_serves: the grouping pass of the host side asks the same question)
-static bool nt_serves(const mml_gemm_wgrad_desc& q) {
-  if (q.M < 16384 || q.M % NT_STEP != 0) return false;
-  if (q.w_kn || !q.dC || !q.A || !q.dW || !q.amax_dc || !q.amax_a) return false;
-  if (q.N <= 0 || q.N % 32 != 0 || q.K <= 0 || q.K % 4 != 0) return false;
-  if (!aligned16(q.dC) || !aligned16(q.A) || q.lddc % 4 != 0 || q.lda % 4 != 0 || q.lddc < q.N || q.lda < q.K ||
-      q.lddw < q.K)
-    return false;
-  return true;
-}
-
-extern "C" int mml_gemm_nt_serves(const mml_gemm_wgrad_desc* desc) { return (desc && nt_serves(*desc)) ? 1 : 0; }
-
-extern "C" int mml_gemm_set_nt(int32_t on) {
-  MML_REQUIRE(on >= 0 && on <= 3, "mml_gemm_set_nt: 0 (off), 1 (every qualifying launch: default), 2 (launches of >= 16 tiles) "
-              "or 3 (lab: every qualifying launch on gemm_ntd_kernel)");
-  g_nt_on = on;
-  return MML_OK;
-}
-
-// MML_OK: the launch (phase 1 = partial tiles, 2 = their reduction, 0 = both) was served; MML_ERR_UNSUPPORTED (no error
-// text): not a launch this kernel serves -- the caller runs the tile kernel.  The decision depends on the descriptors and
-// the workspace size only, so phase 2 of a call pair decides like its phase 1.
-int mml_gemm_nt_try_wgrad(const mml_gemm_wgrad_desc* d, int32_t n, void* workspace, int64_t workspace_bytes, int32_t phase,
-                          hipStream_t st) {
-  if (nt_mode() == 0 || n < 1 || n > NT_MAX_GROUP || !workspace) return MML_ERR_UNSUPPORTED;
-  const int32_t M = d[0].M;
-  if (M < 16384 || M % NT_STEP != 0) return MML_ERR_UNSUPPORTED;
-  int64_t tiles = 0, elems = 0;
-  for (int i = 0; i < n; ++i) {
-    const mml_gemm_wgrad_desc& q = d[i];
-    if (q.M != M || !nt_serves(q)) return MML_ERR_UNSUPPORTED;
-    tiles += cdiv(q.N, 128) * cdiv(q.K, 128);
-    elems += (int64_t)q.N * q.K + q.N;
-  }
-  if (nt_mode() == 2 && tiles < NT_MIN_TILES) return MML_ERR_UNSUPPORTED;
-  const int steps = M / NT_STEP;
-  const int per_cu = nt_per_cu();
-  int64_t slabs = (per_cu * (int64_t)nt_cus()) / tiles;   // two workgroups per CU (64 KiB of LDS each), or one (see nt_per_cu)
-  if (slabs > steps / 8) slabs = steps / 8;           // at least 256 batch rows per slab
-  if (slabs > 64) slabs = 64;
-  const int64_t fit = workspace_bytes / (elems * 4);  // (the caller sized the workspace for the tile kernel's split)
-  if (slabs > fit) slabs = fit;
-  if (slabs < 1) return MML_ERR_UNSUPPORTED;
-
+// Fills the argument blocks of the launch the rule planned (gemm_route.hpp: nt_serves -- slabs, grid, dynamic LDS) and
+// launches the partial tiles (g.partials) and / or their reduction (g.reduce).
+int mml_gemm_nt_launch(const mml_gemm_wgrad_desc* d, const GemmLaunch& g, void* workspace, hipStream_t st) {
   NtLaunch L{};
   NtRedLaunch R{};
+  const int n = g.count;
+  const int64_t slabs = g.slabs;
   L.n_prob = R.n_prob = n;
-  L.steps = steps;
-  L.slabs = R.slabs = (int)slabs;
+  L.steps = d[0].M / NT_STEP;
+  L.slabs = R.slabs = g.slabs;
   float* ws = reinterpret_cast<float*>(workspace);
   int maxred = 1;
   for (int i = 0; i < n; ++i) {
@@ -666,15 +592,13 @@ int mml_gemm_nt_try_wgrad(const mml_gemm_wgrad_desc* d, int32_t n, void* workspa
     const int blocks = (int)cdiv((int64_t)q.N * q.K / 4, 64);
     maxred = blocks > maxred ? blocks : maxred;
   }
-  if (phase != 2) {
-    // (mode 3: the lab variant gemm_ntd_kernel, dC fragments straight from global memory -- measured 19-21 % slower)
-    // (one per CU: 20 KiB of unused dynamic LDS on top of the 64 KiB make a second workgroup not fit)
-    if (nt_mode() == 3) MML_LAUNCH(gemm_ntd_kernel, dim3((unsigned)(L.tiles * slabs)), dim3(256), 0, st, L);
-    else MML_LAUNCH(gemm_nt_kernel, dim3((unsigned)(L.tiles * slabs)), dim3(256), per_cu == 1 ? 20480 : 0, st, L);
+  if (g.partials) {
+    if (g.ntd) MML_LAUNCH(gemm_ntd_kernel, dim3(g.grid), dim3(256), (size_t)g.dyn_lds, st, L);
+    else MML_LAUNCH(gemm_nt_kernel, dim3(g.grid), dim3(256), (size_t)g.dyn_lds, st, L);
     const int rc = check_launch("mml_gemm_grouped_wgrad(nt)");
     if (rc != MML_OK) return rc;
   }
-  if (phase != 1) {
+  if (g.reduce) {
     if (maxred > 2048) maxred = 2048;
     MML_LAUNCH(nt_reduce_kernel, dim3((unsigned)maxred, (unsigned)n), dim3(256), 0, st, R);
     return check_launch("mml_gemm_grouped_wgrad(nt reduce)");

@@ -18,6 +18,7 @@
 // Same planes, same product order per 16-block (A_h B_l, A_l B_h, A_h B_h), same order of sources and of k as
 // gemm_pipe_kernel<.., EMU = 2, BPL>: the results are its bits (tests/test_gemm_os_gpu.py).
 #include "common.hpp"
+#include "gemm_route.hpp"
 #include "lds_async.hpp"
 
 #include <stdlib.h>
@@ -29,8 +30,6 @@ namespace mml {
 using of32x16 = __attribute__((ext_vector_type(16))) float;
 typedef uint32_t ou32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int OS_BM = 256;                   // rows of a workgroup's panel
-constexpr int OS_NC = 256;                   // output columns a workgroup holds
 constexpr int OS_DA = 5;                     // ring stages of the gradients (four k-steps in flight)
 constexpr int OS_DB = 3;                     // ... of the weights' planes (two in flight)
 constexpr int OS_A_STAGE = OS_BM * 64;       // bytes: 256 rows x 16 floats
@@ -374,35 +373,8 @@ __global__ __launch_bounds__(512, 1) void gemm_os_kernel(const OsLaunch Larg) {
 
 using namespace mml;
 
-// The launches this kernel takes (mml_gemm_os_serves in gemm.hip: the host side asks the same question).
-// MMLREC_GEMM_OS=0 (read on every call: a test switches it inside one process) turns the kernel off.
-bool mml_gemm_os_takes(const mml_gemm_dgrad_desc* d, int32_t n) {
-  const char* e = getenv("MMLREC_GEMM_OS");
-  if ((e && e[0] == '0') || !d || n != 1) return false;
-  const mml_gemm_dgrad_desc& q = d[0];
-  if (q.gate_h || q.Y || q.relu_mask || q.act != MML_ACT_NONE || !q.dA) return false;
-  if (q.n_src < 2 || q.n_src > MML_MAX_SRC) return false;  // (one source: the weight-stationary kernel's)
-  // (every workgroup computes OS_NC = 256 columns: a narrower gradient wastes the difference -- PLE's K = 128 launches
-  // measured 1 % slower per step with this kernel than with the tile kernel, so they stay there)
-  if (q.M < 16384 || q.K < 192 || q.K > OS_NC || q.K % 4 != 0) return false;
-  if (!aligned16(q.dA) || q.ldda % 4 != 0 || q.ldda < q.K) return false;
-  if ((int64_t)q.M * q.ldda >= (1ll << 40)) return false;
-  int64_t ntot = 0;
-  for (int s = 0; s < q.n_src; ++s) {
-    if (q.w_kn[s] != 0 || !q.dC[s] || !q.w_planes[s] || !q.w_kexp[s] || !q.amax_dc[s]) return false;
-    if (q.w_kexp[s] != q.w_kexp[0]) return false;  // (one group, one exponent)
-    if (q.N[s] <= 0 || q.N[s] % 16 != 0) return false;
-    if (!aligned16(q.dC[s]) || q.lddc[s] % 4 != 0 || q.lddc[s] < q.N[s]) return false;
-    if (!aligned16(q.w_planes[s]) || q.ldw[s] % 4 != 0 || q.ldw[s] < q.K) return false;
-    ntot += q.N[s];
-  }
-  return ntot >= 256;  // (short reductions: the ring would not fill)
-}
-
-// MML_OK: served; MML_ERR_UNSUPPORTED (no error text): not a launch of this kernel -- the caller goes on to the
-// weight-stationary and the tile kernel.
-int mml_gemm_os_try_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, hipStream_t st) {
-  if (!mml_gemm_os_takes(d, n)) return MML_ERR_UNSUPPORTED;
+// Fills the kernel's argument block for the launch the rule planned (gemm_route.hpp: os_serves) and launches.
+int mml_gemm_os_launch(const mml_gemm_dgrad_desc* d, const GemmLaunch& g, hipStream_t st) {
   const mml_gemm_dgrad_desc& q = d[0];
   OsLaunch L{};
   int64_t ntot = 0;
@@ -425,16 +397,7 @@ int mml_gemm_os_try_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, hipStream_t s
   L.nsrc = q.n_src;
   L.accumulate = q.accumulate;
   L.ksteps = (int32_t)(ntot / 16);
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, nn = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
-      nn = 256;
-    cus = nn;
-  }
-  const int npanels = (int)cdiv(L.M, OS_BM);
-  const dim3 grid((unsigned)(npanels < cus ? npanels : cus)), block(512);
+  const dim3 grid(g.grid), block(512);
 #ifdef MML_OS_LAB  // lab build only (MMLREC_BUILD_OS_LAB=1 python -m ...build; tools/lab/os_lab.sh): garbage-result variants
   const char* lab = getenv("MMLREC_OS_LAB");
   switch (lab ? atoi(lab) : 0) {

@@ -22,6 +22,7 @@
 // Results are bitwise those of gemm_pipe_kernel<.., EMU = 2, BPL> on the same operands (same planes, same product
 // order hl, lh, hh per 16-k block, same k order): tests/test_gemm_panel_gpu.py.
 #include "common.hpp"
+#include "gemm_route.hpp"
 #include "lds_async.hpp"
 
 #include <stdlib.h>
@@ -33,7 +34,6 @@ namespace mml {
 
 using pf32x16 = __attribute__((ext_vector_type(16))) float;
 
-constexpr int PN_BM = 128;               // panel rows (four waves x 32)
 constexpr int PN_STAGE = 8192;           // bytes of one 128-column x 16-k weight image
 #ifndef PN_D_LAB
 #define PN_D_LAB 12
@@ -41,7 +41,6 @@ constexpr int PN_STAGE = 8192;           // bytes of one 128-column x 16-k weigh
 constexpr int PN_D = PN_D_LAB;           // weight ring stages
 constexpr int PN_W = PN_D - 2;           // k-steps between the issue of a stage and the wait for it
 constexpr int PN_SCR = 4096;             // bytes of a wave's row-major turn area (32 rows x 128 B)
-constexpr int PN_MAXH = 64;              // half tiles per launch
 constexpr int PN_RING_OFF = 0;
 constexpr int PN_SCR_OFF = PN_RING_OFF + PN_D * PN_STAGE;
 constexpr int PN_BIAS_OFF = PN_SCR_OFF + 4 * PN_SCR;            // two buffers x 128 floats
@@ -594,80 +593,24 @@ __global__ __launch_bounds__(256, 1) void gemm_panel_kernel(const PanelLaunch La
   }
 }
 
-static int g_panel_on = -1;
-static int pn_enabled() {
-  if (g_panel_on < 0) {
-    const char* e = getenv("MMLREC_GEMM_PANEL");
-    g_panel_on = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_panel_on;
-}
-
 }  // namespace mml
 
 using namespace mml;
 
-extern "C" int mml_gemm_set_panel(int32_t on) {
-  g_panel_on = on ? 1 : 0;
-  return MML_OK;
-}
-
-// Returns MML_OK when the panel kernel took the launch, MML_ERR_UNSUPPORTED (without setting an error) when the launch
-// is not one it serves -- the caller (mml_gemm_grouped_fwd) then runs the tile kernel.
-int mml_gemm_panel_try_fwd(const mml_gemm_fwd_desc* d, int32_t n, hipStream_t st) {
-  if (!pn_enabled() || n < 1 || n > MML_MAX_GROUP) return MML_ERR_UNSUPPORTED;
+// Fills the kernel's argument block for the launch the rule planned (gemm_route.hpp: panel_rows) and launches: rows
+// [0, g.rows) of the batch (the last M % 128 rows of a ragged batch are a tile launch of their own).
+int mml_gemm_panel_launch(const mml_gemm_fwd_desc* d, const GemmLaunch& g, hipStream_t st) {
   const mml_gemm_fwd_desc& d0 = d[0];
-  // the instantiated panel widths: every K = 16 k from 160 to 320 (the caller pads other reduction lengths with zero
-  // columns on both operands -- engine.py, Val.kpad: AE with its 63 dense columns, K0 = 303, arrives here as 304)
-  if (d0.K % 16 != 0 || d0.K < 160 || d0.K > 320) return MML_ERR_UNSUPPORTED;
-  if (d0.M < PN_BM * 64) return MML_ERR_UNSUPPORTED;  // (small batches: the tile kernel)
-  if (d0.M % PN_BM != 0) {
-    // ragged batch: the whole panels here, the last M % 128 rows through the tile kernel (a row's result does not depend
-    // on the tile it is computed in: same planes, same product and k order -- tests/test_gemm_panel_gpu.py)
-    mml_gemm_fwd_desc head[MML_MAX_GROUP], tail[MML_MAX_GROUP];
-    const int64_t mh = d0.M - d0.M % PN_BM;
-    for (int i = 0; i < n; ++i) {
-      head[i] = tail[i] = d[i];
-      head[i].M = (int32_t)mh;
-      tail[i].M = d[i].M - (int32_t)mh;
-      tail[i].A = d[i].A + mh * d[i].lda;
-      tail[i].C = d[i].C + mh * d[i].ldc;
-      if (d[i].relu_mask) tail[i].relu_mask = d[i].relu_mask + mh * d[i].ldmask;
-      if (d[i].M != d0.M) return MML_ERR_UNSUPPORTED;
-    }
-    const int rc = mml_gemm_panel_try_fwd(head, n, st);
-    if (rc != MML_OK) return rc;
-    return mml_gemm_grouped_fwd(tail, n, (void*)st);  // (M < 128: never comes back here)
-  }
-  if (!d0.amax_a || !aligned16(d0.A) || d0.lda % 4 != 0) return MML_ERR_UNSUPPORTED;
-  int halves = 0, masks = 0, relus = 0;
-  for (int i = 0; i < n; ++i) {
-    const mml_gemm_fwd_desc& q = d[i];
-    if (q.mul || q.prod) return MML_ERR_UNSUPPORTED;  // (K7 products: the tile kernel's epilogue)
-    if (q.A != d0.A || q.lda != d0.lda || q.M != d0.M || q.K != d0.K || q.amax_a != d0.amax_a) return MML_ERR_UNSUPPORTED;
-    if (q.w_kn != 0 || !q.w_planes || !q.w_kexp || !aligned16(q.w_planes) || q.ldw % 4 != 0) return MML_ERR_UNSUPPORTED;
-    if (q.N % 64 != 0 || q.N < 64) return MML_ERR_UNSUPPORTED;
-    if (q.act != MML_ACT_RELU) return MML_ERR_UNSUPPORTED;
-    if (!aligned16(q.C) || q.ldc % 4 != 0 || (q.bias && !aligned16(q.bias))) return MML_ERR_UNSUPPORTED;
-    if ((int64_t)q.M * q.ldc >= (1ll << 30) || (int64_t)q.M * q.ldmask >= (1ll << 30)) return MML_ERR_UNSUPPORTED;  // (32-bit offsets)
-    const bool m = q.act == MML_ACT_RELU && q.relu_mask != nullptr;
-    if (m && q.ldmask * 32 < q.N) return MML_ERR_UNSUPPORTED;
-    masks += m ? 1 : 0;
-    relus += 1;
-    halves += q.N / 64;
-  }
-  if (halves > PN_MAXH || halves % 2 != 0) return MML_ERR_UNSUPPORTED;
-  if (masks != 0 && masks != relus) return MML_ERR_UNSUPPORTED;  // (the waits count the stores of a piece: all or none)
   PanelLaunch L{};
   L.A = d0.A;
   L.amaxA = d0.amax_a;
   L.lda = d0.lda;
-  L.M = d0.M;
+  L.M = g.rows;
   L.K = d0.K;
-  L.n_prob = n;
-  L.store_masks = masks != 0;
+  L.n_prob = g.count;
+  L.store_masks = g.masks;
   int hidx = 0;
-  for (int i = 0; i < n; ++i) {
+  for (int i = 0; i < g.count; ++i) {
     const mml_gemm_fwd_desc& q = d[i];
     PanelProblem& P = L.p[i];
     P.C = q.C;
@@ -687,20 +630,11 @@ int mml_gemm_panel_try_fwd(const mml_gemm_fwd_desc* d, int32_t n, hipStream_t st
     }
   }
   L.n_half = hidx;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, nn = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
-      nn = 256;
-    cus = nn;
-  }
-  const int npanels = (int)cdiv(L.M, PN_BM);
-  const dim3 g((unsigned)(npanels < cus ? npanels : cus)), b(256);
-#define PN_GO(KB_)                                                                    \
-  do {                                                                                \
-    if (L.store_masks) MML_LAUNCH((gemm_panel_kernel<KB_, true>), g, b, 0, st, L);    \
-    else MML_LAUNCH((gemm_panel_kernel<KB_, false>), g, b, 0, st, L);                 \
+  const dim3 grid(g.grid), b(256);
+#define PN_GO(KB_)                                                                       \
+  do {                                                                                   \
+    if (L.store_masks) MML_LAUNCH((gemm_panel_kernel<KB_, true>), grid, b, 0, st, L);    \
+    else MML_LAUNCH((gemm_panel_kernel<KB_, false>), grid, b, 0, st, L);                 \
   } while (0)
   switch (L.K / 16) {
     case 10: PN_GO(10); break;

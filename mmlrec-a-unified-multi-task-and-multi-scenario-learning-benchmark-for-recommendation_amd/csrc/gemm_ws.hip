@@ -27,6 +27,7 @@
 //     h (.) g is not stored; the turn reads h and g once and stores dH (+)= v g act_h'(h) and dG (+)= v h act_g'(g)
 //     (the expressions of gemm_pipe_kernel's gate mode) with one magnitude slot each.
 #include "common.hpp"
+#include "gemm_route.hpp"
 #include "lds_async.hpp"
 
 #include <stdlib.h>
@@ -35,13 +36,11 @@ namespace mml {
 
 using wf32x16 = __attribute__((ext_vector_type(16))) float;
 
-constexpr int WS_W_BYTES = 128 * 1024;              // the weight image
 constexpr int WS_BIAS_OFF = WS_W_BYTES;             // <= 256 bias values
 constexpr int WS_AMAX_OFF = WS_BIAS_OFF + 1024;     // the workgroup's magnitude word
 constexpr int WS_TURN_OFF = WS_AMAX_OFF + 64;       // eight waves x 2 KiB: 32 rows x 64 bytes turned row-major for the stores
 constexpr int WS_LDS_BYTES = WS_TURN_OFF + 8 * 2048;
 static_assert(WS_LDS_BYTES <= 160 * 1024, "weight-stationary kernel LDS budget");
-constexpr int WS_MIN_ROWS = 8192;                   // below: the tile kernel (a persistent grid would idle)
 __device__ __forceinline__ float ws_act_bwd(const float y, const int act) {  // (gemm.hip: act_bwd)
   if (act == MML_ACT_RELU) return y > 0.f ? 1.f : 0.f;
   if (act == MML_ACT_SIGMOID) return y * (1.f - y);
@@ -391,35 +390,11 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(const WsLaunch L) {
   }
 }
 
-static int g_ws_on = -1;
-static int ws_enabled() {
-  if (g_ws_on < 0) {
-    const char* e = getenv("MMLREC_GEMM_WS");
-    g_ws_on = (e && e[0] == '0') ? 0 : 1;
-  }
-  return g_ws_on;
-}
-static int ws_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, nn = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
-      nn = 256;
-    cus = nn;
-  }
-  return cus;
-}
-
-// symbol of the calling thread's most recent weight-stationary launch, as rocprofv3 prints it (mml_gemm_last_kernel)
-static thread_local char g_ws_last[64] = "gemm_ws_kernel";
-const char* mml_gemm_ws_last_symbol() { return g_ws_last; }
-
 template <int MODE>
-static int ws_launch(const WsLaunch& L, const int nout, const bool masks, const int dgroup, const bool k7, hipStream_t st) {
-  const dim3 g((unsigned)(L.wg_per_prob * L.n_prob)), b(512);
-  snprintf(g_ws_last, sizeof(g_ws_last), "gemm_ws_kernel<%d, %d, %s, %d, %s>", nout / 32, MODE, (masks && !k7) ? "true" : "false",
-           dgroup, k7 ? "true" : "false");
+static int ws_launch(const WsLaunch& L, const GemmLaunch& G, hipStream_t st) {
+  const dim3 g(G.grid), b(512);
+  const int nout = G.nout, dgroup = G.dgroup;
+  const bool masks = G.masks, k7 = G.k7;
 #define WS_GO2(NS_, D_)                                                                 \
   do {                                                                                  \
     if (k7) MML_LAUNCH((gemm_ws_kernel<NS_, MODE, false, D_, true>), g, b, 0, st, L);   \
@@ -443,182 +418,77 @@ static int ws_launch(const WsLaunch& L, const int nout, const bool masks, const 
   } while (0)
   if (nout == 64) WS_GO(2);
   else if (nout == 128) WS_GO(4);
-  else if (k7) return MML_ERR_UNSUPPORTED;  // (never reached: ws_fwd_ok / ws_dgrad_ok refuse 256-wide K7 problems --
-                                            //  eight sub-tiles of accumulators plus the factors' registers would spill)
   else WS_GO8();  // (256 output columns of an input gradient: eight sub-tiles at once -- swept in two passes of four the rows
-                  //  were read twice from HBM, PMC 300 MB against 138 algorithmic: 106 -> 93 us)
+                  //  were read twice from HBM, PMC 300 MB against 138 algorithmic: 106 -> 93 us.  Never K7: the rule
+                  //  refuses 256-wide K7 problems -- eight sub-tiles of accumulators plus the factors' registers would spill)
 #undef WS_GO
 #undef WS_GO8
 #undef WS_GO2
   return check_launch(MODE == 0 ? "mml_gemm_grouped_fwd(ws)" : "mml_gemm_grouped_dgrad(ws)");
 }
 
-// k-steps per group for a reduction of `kred` values: 4 (multiples of 64), 5 (other multiples of 80), 0 = not served
-static int ws_dgroup(const int kred) { return kred <= 0 ? 0 : (kred % 64 == 0 ? 4 : (kred % 80 == 0 ? 5 : 0)); }
-
 }  // namespace mml
 
 using namespace mml;
 
-extern "C" int mml_gemm_set_ws(int32_t on) {
-  g_ws_on = on ? 1 : 0;
-  return MML_OK;
-}
-
-// Both return MML_OK when the weight-stationary kernel took the launch and MML_ERR_UNSUPPORTED (no error text) when the
-// launch is not one it serves: the caller then runs the tile kernel.  A launch whose problems differ in shape (PepNet's
-// and PLE's layers: 128- and 64-wide siblings in one call) is served as one kernel launch per (output width, sign masks)
-// class -- all of its problems must qualify.
-static bool ws_fwd_ok(const mml_gemm_fwd_desc& q, const mml_gemm_fwd_desc& d0) {
-  if (q.M != d0.M || ws_dgroup(q.K) == 0) return false;
-  if (q.N != 256 && q.N != 128 && q.N != 64) return false;  // (the instantiated output widths)
-  if ((int64_t)q.N * q.K * 4 > WS_W_BYTES) return false;
-  if (!q.A || !q.C || !q.w_planes || !q.w_kexp || !q.amax_a) return false;
-  if (q.mul || q.prod) {  // K7: prod = act(..) (.) mul from the same turn
-    if (!q.mul || !q.prod || q.ldmul < q.N || q.ldprod < q.N) return false;
-    if (!aligned16(q.mul) || q.ldmul % 4 != 0 || !aligned16(q.prod) || q.ldprod % 4 != 0) return false;
-    if (q.act == MML_ACT_RELU && q.relu_mask) return false;  // (no instantiation with sign masks: gates end in a sigmoid)
-    if (q.N == 256) return false;                            // (nor with eight sub-tiles: registers)
-  }
-  if (q.act != MML_ACT_RELU && q.act != MML_ACT_NONE && q.act != MML_ACT_SIGMOID && q.act != MML_ACT_SIGMOID2) return false;
-  if (!aligned16(q.A) || q.lda % 4 != 0 || !aligned16(q.C) || q.ldc % 4 != 0) return false;
-  if (!q.w_kn && (!aligned16(q.w_planes) || q.ldw % 4 != 0)) return false;
-  if (q.act == MML_ACT_RELU && q.relu_mask && q.ldmask * 32 < q.N) return false;
-  return true;
-}
-
-int mml_gemm_ws_try_fwd(const mml_gemm_fwd_desc* d, int32_t n, hipStream_t st) {
-  if (!ws_enabled() || n < 1 || n > MML_MAX_GROUP) return MML_ERR_UNSUPPORTED;
-  const mml_gemm_fwd_desc& d0 = d[0];
-  if (d0.M < WS_MIN_ROWS) return MML_ERR_UNSUPPORTED;
-  for (int i = 0; i < n; ++i)
-    if (!ws_fwd_ok(d[i], d0)) return MML_ERR_UNSUPPORTED;
-  if (n > ws_cus()) return MML_ERR_UNSUPPORTED;  // (decided before the first launch, never between two of them)
-  bool done[MML_MAX_GROUP] = {};
-  for (int i = 0; i < n; ++i) {
-    if (done[i]) continue;
-    const bool mi = d[i].act == MML_ACT_RELU && d[i].relu_mask != nullptr;
-    const bool ki = d[i].mul != nullptr;
-    WsLaunch L{};
-    for (int j = i; j < n; ++j) {
-      const mml_gemm_fwd_desc& q = d[j];
-      const bool m = q.act == MML_ACT_RELU && q.relu_mask != nullptr;
-      if (done[j] || q.N != d[i].N || m != mi || (q.mul != nullptr) != ki || ws_dgroup(q.K) != ws_dgroup(d[i].K)) continue;
-      done[j] = true;
-      WsProblem& P = L.p[L.n_prob++];
-      P.A = q.A;
-      P.amaxA = q.amax_a;
-      P.planes = q.w_planes;
-      P.kexp = q.w_kexp;
-      P.C = q.C;
-      P.bias = q.bias;
-      P.mask = m ? q.relu_mask : nullptr;
-      P.amax_out = q.amax_out;
-      P.lda = q.lda;
-      P.ldp = q.ldw;
-      P.ldc = q.ldc;
-      P.ldmask = q.ldmask;
-      P.layout = q.w_kn ? MML_PLANES_COLS : MML_PLANES_ROWS;  // ([K, N]: the reduction runs down the rows)
-      P.act = q.act;
-      P.G = q.K / (16 * ws_dgroup(q.K));
-      if (ki) {
-        P.x1 = q.mul; P.ld1 = q.ldmul; P.c2 = q.prod; P.ldc2 = q.ldprod; P.amax_out2 = q.amax_prod;
-      }
+// Both fill the kernel's argument block with one class of the call's problems (g.member: gemm_route.hpp, ws_classes) and
+// launch it.
+int mml_gemm_ws_launch_fwd(const mml_gemm_fwd_desc* d, const GemmLaunch& g, hipStream_t st) {
+  WsLaunch L{};
+  for (int k = 0; k < g.n_prob; ++k) {
+    const mml_gemm_fwd_desc& q = d[g.member[k]];
+    WsProblem& P = L.p[L.n_prob++];
+    P.A = q.A;
+    P.amaxA = q.amax_a;
+    P.planes = q.w_planes;
+    P.kexp = q.w_kexp;
+    P.C = q.C;
+    P.bias = q.bias;
+    P.mask = g.masks ? q.relu_mask : nullptr;
+    P.amax_out = q.amax_out;
+    P.lda = q.lda;
+    P.ldp = q.ldw;
+    P.ldc = q.ldc;
+    P.ldmask = q.ldmask;
+    P.layout = q.w_kn ? MML_PLANES_COLS : MML_PLANES_ROWS;  // ([K, N]: the reduction runs down the rows)
+    P.act = q.act;
+    P.G = q.K / (16 * g.dgroup);
+    if (g.k7) {
+      P.x1 = q.mul; P.ld1 = q.ldmul; P.c2 = q.prod; P.ldc2 = q.ldprod; P.amax_out2 = q.amax_prod;
     }
-    L.M = d0.M;
-    L.wg_per_prob = ws_cus() / L.n_prob;
-    const int rc = ws_launch<0>(L, d[i].N, mi, ws_dgroup(d[i].K), ki, st);
-    if (rc != MML_OK) return rc;
   }
-  return MML_OK;
+  L.M = d[0].M;
+  L.wg_per_prob = g.wg_per_prob;
+  return ws_launch<0>(L, g, st);
 }
 
-static bool ws_dgrad_ok(const mml_gemm_dgrad_desc& q, const mml_gemm_dgrad_desc& d0) {
-  if (q.n_src != 1 || q.M != d0.M) return false;
-  if (q.gate_h) {  // K7 gate mode: dH / dG instead of dA
-    if (!q.gate_g || !q.d_h || !q.d_g || q.ld_h < q.K || q.ld_g < q.K || q.ld_dh < q.K || q.ld_dg < q.K) return false;
-    if (!aligned16(q.gate_h) || !aligned16(q.gate_g) || !aligned16(q.d_h) || !aligned16(q.d_g) || q.ld_h % 4 != 0 ||
-        q.ld_g % 4 != 0 || q.ld_dh % 4 != 0 || q.ld_dg % 4 != 0)
-      return false;
-  } else if (!q.dA) {
-    return false;
-  }
-  const int32_t kred = q.N[0];
-  if (ws_dgroup(kred) == 0) return false;
-  if (q.K != 64 && q.K != 128 && q.K != 256) return false;  // (the instantiated output widths)
-  if ((int64_t)q.K * kred * 4 > WS_W_BYTES) return false;
-  if (!q.dC[0] || !q.w_planes[0] || !q.w_kexp[0] || !q.amax_dc[0]) return false;
-  const bool m = q.act == MML_ACT_RELU && q.relu_mask != nullptr;
-  if (q.gate_h) {
-    if (m || q.Y || q.K == 256) return false;  // (gate mode: no derivative of the product itself; no 256-wide instantiation)
-    if (!aligned16(q.dC[0]) || q.lddc[0] % 4 != 0) return false;
-    if (q.w_kn[0] && (!aligned16(q.w_planes[0]) || q.ldw[0] % 4 != 0)) return false;
-    return true;
-  }
-  if (q.act != MML_ACT_NONE && !m) return false;  // (derivatives from the stored outputs: the tile kernel)
-  if (m && q.ldmask * 32 < q.K) return false;
-  if (!aligned16(q.dC[0]) || q.lddc[0] % 4 != 0 || !aligned16(q.dA) || q.ldda % 4 != 0) return false;
-  if (q.w_kn[0] && (!aligned16(q.w_planes[0]) || q.ldw[0] % 4 != 0)) return false;
-  return true;
-}
-
-int mml_gemm_ws_try_dgrad(const mml_gemm_dgrad_desc* d, int32_t n, hipStream_t st) {
-  if (!ws_enabled() || n < 1 || n > MML_MAX_GROUP) return MML_ERR_UNSUPPORTED;
-  const mml_gemm_dgrad_desc& d0 = d[0];
-  if (d0.M < WS_MIN_ROWS) return MML_ERR_UNSUPPORTED;
-  for (int i = 0; i < n; ++i)
-    if (!ws_dgrad_ok(d[i], d0)) return MML_ERR_UNSUPPORTED;
-  // Two problems of one call that write the same dA (an overwriting and an accumulating one) need an ORDER: the
-  // problems of a class run in one kernel launch on disjoint workgroup ranges, i.e. concurrently, and classes are
-  // launched in the order of their first members -- neither keeps the call's order.  Left to the tile kernel (the
-  // engine never builds such a call: chunks of one input go into different launches).
-  for (int i = 0; i < n; ++i)
-    for (int j = i + 1; j < n; ++j) {
-      const float* ti[2] = {d[i].gate_h ? d[i].d_h : d[i].dA, d[i].gate_h ? d[i].d_g : nullptr};
-      const float* tj[2] = {d[j].gate_h ? d[j].d_h : d[j].dA, d[j].gate_h ? d[j].d_g : nullptr};
-      for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b)
-          if (ti[a] && ti[a] == tj[b]) return MML_ERR_UNSUPPORTED;
+int mml_gemm_ws_launch_dgrad(const mml_gemm_dgrad_desc* d, const GemmLaunch& g, hipStream_t st) {
+  WsLaunch L{};
+  for (int k = 0; k < g.n_prob; ++k) {
+    const mml_gemm_dgrad_desc& q = d[g.member[k]];
+    WsProblem& P = L.p[L.n_prob++];
+    P.A = q.dC[0];
+    P.amaxA = q.amax_dc[0];
+    P.planes = q.w_planes[0];
+    P.kexp = q.w_kexp[0];
+    P.C = q.dA;
+    P.mask = g.masks ? const_cast<uint32_t*>(q.relu_mask) : nullptr;
+    P.amax_out = q.amax_out;
+    P.lda = q.lddc[0];
+    P.ldp = q.ldw[0];
+    P.ldc = q.ldda;
+    P.ldmask = q.ldmask;
+    P.layout = q.w_kn[0] ? MML_PLANES_ROWS : MML_PLANES_COLS;  // ([N, K]: the reduction runs down the rows)
+    P.accumulate = q.accumulate;
+    P.G = q.N[0] / (16 * g.dgroup);
+    if (g.k7) {
+      P.C = q.d_h; P.ldc = q.ld_dh; P.accumulate = q.acc_h; P.amax_out = q.amax_dh; P.mask = nullptr;
+      P.x1 = q.gate_h; P.ld1 = q.ld_h; P.act1 = q.act_h;
+      P.x2 = q.gate_g; P.ld2 = q.ld_g; P.act2 = q.act_g;
+      P.c2 = q.d_g; P.ldc2 = q.ld_dg; P.acc2 = q.acc_g; P.amax_out2 = q.amax_dg;
     }
-  if (n > ws_cus()) return MML_ERR_UNSUPPORTED;  // (every class gets >= 1 workgroup per problem: decided BEFORE the first launch)
-  bool done[MML_MAX_GROUP] = {};
-  for (int i = 0; i < n; ++i) {
-    if (done[i]) continue;
-    const bool mi = d[i].act == MML_ACT_RELU && d[i].relu_mask != nullptr;
-    const bool ki = d[i].gate_h != nullptr;
-    WsLaunch L{};
-    for (int j = i; j < n; ++j) {
-      const mml_gemm_dgrad_desc& q = d[j];
-      const bool m = q.act == MML_ACT_RELU && q.relu_mask != nullptr;
-      if (done[j] || q.K != d[i].K || m != mi || (q.gate_h != nullptr) != ki || ws_dgroup(q.N[0]) != ws_dgroup(d[i].N[0]))
-        continue;
-      done[j] = true;
-      WsProblem& P = L.p[L.n_prob++];
-      P.A = q.dC[0];
-      P.amaxA = q.amax_dc[0];
-      P.planes = q.w_planes[0];
-      P.kexp = q.w_kexp[0];
-      P.C = q.dA;
-      P.mask = m ? const_cast<uint32_t*>(q.relu_mask) : nullptr;
-      P.amax_out = q.amax_out;
-      P.lda = q.lddc[0];
-      P.ldp = q.ldw[0];
-      P.ldc = q.ldda;
-      P.ldmask = q.ldmask;
-      P.layout = q.w_kn[0] ? MML_PLANES_ROWS : MML_PLANES_COLS;  // ([N, K]: the reduction runs down the rows)
-      P.accumulate = q.accumulate;
-      P.G = q.N[0] / (16 * ws_dgroup(q.N[0]));
-      if (ki) {
-        P.C = q.d_h; P.ldc = q.ld_dh; P.accumulate = q.acc_h; P.amax_out = q.amax_dh; P.mask = nullptr;
-        P.x1 = q.gate_h; P.ld1 = q.ld_h; P.act1 = q.act_h;
-        P.x2 = q.gate_g; P.ld2 = q.ld_g; P.act2 = q.act_g;
-        P.c2 = q.d_g; P.ldc2 = q.ld_dg; P.acc2 = q.acc_g; P.amax_out2 = q.amax_dg;
-      }
-    }
-    L.M = d0.M;
-    L.wg_per_prob = ws_cus() / L.n_prob;  // (>= 1: n <= ws_cus() was checked before the first launch)
-    const int rc = ws_launch<1>(L, d[i].K, mi, ws_dgroup(d[i].N[0]), ki, st);
-    if (rc != MML_OK) return rc;
   }
-  return MML_OK;
+  L.M = d[0].M;
+  L.wg_per_prob = g.wg_per_prob;
+  return ws_launch<1>(L, g, st);
 }

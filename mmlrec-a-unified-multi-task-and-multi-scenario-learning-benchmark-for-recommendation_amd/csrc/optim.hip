@@ -1036,18 +1036,6 @@ const mml_opt_step_consts* step_bound(const mml_opt_hyper& h) {
       return (b.kind == h.kind && b.lr == h.lr && b.beta1 == h.beta1 && b.beta2 == h.beta2) ? b.consts : nullptr;
   return nullptr;
 }
-
-int device_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, nn = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
-      nn = 256;
-    cus = nn;
-  }
-  return cus;
-}
 }  // namespace
 
 extern "C" int mml_opt_step_begin(int32_t* step_dev, int32_t delta, const mml_opt_hyper* hyper,

@@ -242,23 +242,11 @@ __global__ __launch_bounds__(256) void pcgrad_stash_kernel(const PcgBatch Bt, in
       });
 }
 
-static int pcg_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, nn = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
-      nn = 256;
-    cus = nn;
-  }
-  return cus;
-}
-
 // workgroups per segment: enough 256-thread workgroups to fill every CU (8 each: 32 waves) over the m segments of a
 // launch, no more than the largest segment has 16-byte pieces for
 static unsigned pcg_grid(int64_t most, int m) {
   int64_t want = cdiv(most, (int64_t)256 * 4);
-  int64_t fill = cdiv((int64_t)pcg_cus() * 8, (int64_t)m);
+  int64_t fill = cdiv((int64_t)device_cus() * 8, (int64_t)m);
   if (fill < 16) fill = 16;
   if (want > fill) want = fill;
   if (want > PCG_MAX_GX) want = PCG_MAX_GX;

@@ -186,23 +186,11 @@ __global__ __launch_bounds__(256) void prelu_final_kernel(const PreluBwdBatch Bt
   }
 }
 
-static int prelu_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, nn = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
-      nn = 256;
-    cus = nn;
-  }
-  return cus;
-}
-
 // workgroups per item: enough 256-thread workgroups to fill every CU (8 each: 32 waves) over the m items of the launch,
 // no more than the largest item has 16-byte pieces for
 static unsigned prelu_grid(int64_t most, int m) {
   int64_t want = cdiv(most, (int64_t)256 * 4);
-  int64_t fill = cdiv((int64_t)prelu_cus() * 8, (int64_t)m);
+  int64_t fill = cdiv((int64_t)device_cus() * 8, (int64_t)m);
   if (fill < 32) fill = 32;
   if (want > fill) want = fill;
   if (want > PRELU_MAX_GX) want = PRELU_MAX_GX;

@@ -398,20 +398,8 @@ __global__ __launch_bounds__(512, 2) void tower_head_kernel(const ThLaunch L) {
   }
 }
 
-static int th_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, nn = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&nn, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || nn <= 0)
-      nn = 256;
-    cus = nn;
-  }
-  return cus;
-}
-
 static int th_wg_per_prob(const mml_tower_head_group* g) {
-  int w = th_cus() / g->n;
+  int w = device_cus() / g->n;
   const int64_t blocks = (g->M + 255) / 256;  // (one 32-row block per wave at least)
   if (w > blocks) w = (int)blocks;
   return w < 1 ? 1 : w;
@@ -442,7 +430,7 @@ extern "C" int mml_tower_head_serves(const mml_tower_head_group* g) {
 
 extern "C" int64_t mml_tower_head_workspace_bytes(const mml_tower_head_group* g) {
   if (!g || g->n < 1 || g->n > MML_MAX_HEADS) return -1;
-  return (int64_t)g->n * th_cus() * (g->t[0].N + 2) * 4 + 256;  // dw + dbias rows, then the loss arrays
+  return (int64_t)g->n * device_cus() * (g->t[0].N + 2) * 4 + 256;  // dw + dbias rows, then the loss arrays
 }
 
 // phase 1: the launch (prob, dH, dA; per-workgroup partial sums of dw / dbias / loss in the workspace); 2: their reduction; 0: both

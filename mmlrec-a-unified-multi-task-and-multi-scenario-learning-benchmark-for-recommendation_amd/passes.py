@@ -229,7 +229,7 @@ def wgrad_chunks(shapes, serves, B, nt_group):
     # into launches of 16 (2.21 -> 2.13 ms already as ONE call that fell to the tile kernel).
     steps = B // 32
     flat = [s for g in shapes for s in g]
-    # (what gemm_nt_kernel takes -- csrc/gemm_nt.hip, mml_gemm_nt_try_wgrad -- goes together: ONE problem it does
+    # (what gemm_nt_kernel takes -- csrc/gemm_route.hpp, nt_serves -- goes together: ONE problem it does
     # not take, e.g. a final layer with a single output row, would send its whole launch to the tile kernel)
     fits = [i for i, ok in enumerate(serves) if ok]
     other = [i for i, ok in enumerate(serves) if not ok]
