@@ -708,6 +708,21 @@ typedef struct {
   int64_t workspace_bytes;
 } mml_rows_reduce_item;
 int mml_rows_reduce_batch(const mml_rows_reduce_item* items, int32_t n, mml_stream_t stream);
+/* The kernel of this thread's last successful K4 / K5 row-kernel launch (mml_gate_mix_fwd, mml_gate_mix_bwd[_phase],
+ * mml_head_fwd, mml_head_bce_fwd_bwd[_phase]; the reductions are not reported) with its template arguments, as the launch
+ * site spells it -- "gate_bwd_fast_kernel<32, 4, 2, 1, 1>", "head_kernel<false>" --, or "" before the first one. */
+const char* mml_rows_last_kernel(void);
+/* Which of the fast gate kernels a group of this shape will get, before any buffer exists: n_gates gates, each over all
+ * n_experts experts in order, expert outputs of H columns (bf16 when e_bf16), gate inputs of gd_max columns -- assuming
+ * 16-byte aligned buffers and row pitches that are multiples of 8 elements.  A bit set under the process's switches
+ * (MMLREC_GATE_*): what mml_gate_mix_fwd / _bwd decide is built on the same rule (csrc/rows_route.hpp), so a caller that
+ * chooses storage formats by it (model/mmoe.py, engine.GateGroupOp) cannot drift from the library.  The fast kernels alone
+ * honour mml_gate_group.out_bf16.  No GPU work, no error text. */
+#define MML_GATE_SHAPE_FAST_FWD 1 /* the forward runs a fast row kernel                                  */
+#define MML_GATE_SHAPE_FAST_BWD 2 /* the backward does                                                   */
+#define MML_GATE_SHAPE_HV_FWD 4   /* ... the forward's form with eight row columns per lane (bf16 experts) */
+#define MML_GATE_SHAPE_HV_BWD 8   /* ... the backward's                                                  */
+int32_t mml_gate_rows_shape(int32_t H, int32_t gd_max, int32_t n_experts, int32_t n_gates, int32_t e_bf16);
 
 /* ------------------------------------------------------------------------------------------------
  * K5' (round 6)  the top of the network in ONE launch: last tower layer (Linear(K -> N) + ReLU) -> head (Linear(N -> 1,

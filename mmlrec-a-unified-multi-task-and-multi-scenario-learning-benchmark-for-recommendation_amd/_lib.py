@@ -107,6 +107,7 @@ ROWS_REDUCE_HEAD, ROWS_REDUCE_GATE, ROWS_REDUCE_TOWER_HEAD = 0, 1, 2
 MAX_REDUCE_SEGS = 40  # csrc/reduce.hpp: segments of one reduction launch
 NT_MAX_GROUP = 48     # csrc/gemm_nt.hip: weight-gradient problems one gemm_nt_kernel launch takes
 GATE_MIX_BF16, GATE_DE_BF16, GATE_DG_BF16, GATE_E_BF16 = 1, 2, 4, 8
+GATE_SHAPE_FAST_FWD, GATE_SHAPE_FAST_BWD, GATE_SHAPE_HV_FWD, GATE_SHAPE_HV_BWD = 1, 2, 4, 8  # mml_gate_rows_shape
 
 
 class GateDesc(C.Structure):
@@ -270,6 +271,8 @@ _SIGS = {
     "mml_head_bce_fwd_bwd": (C.c_int, [_PP(HeadGroup), fp, i64, fp]),
     "mml_head_bce_fwd_bwd_phase": (C.c_int, [_PP(HeadGroup), fp, i64, i32, fp]),
     "mml_rows_reduce_batch": (C.c_int, [_PP(RowsReduceItem), i32, fp]),
+    "mml_rows_last_kernel": (C.c_char_p, []),
+    "mml_gate_rows_shape": (i32, [i32, i32, i32, i32, i32]),
     "mml_ew_mul": (C.c_int, [fp, fp, fp, i64, fp]),
     "mml_ew_mul_bwd": (C.c_int, [fp, fp, fp, fp, fp, i32, i32, i64, fp]),
     "mml_ew_mul_bwd_act": (C.c_int, [fp, fp, fp, fp, fp, i32, i32, i64, i32, i32, fp]),

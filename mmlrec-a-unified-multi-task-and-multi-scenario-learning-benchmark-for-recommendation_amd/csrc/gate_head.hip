@@ -13,6 +13,8 @@
 #include "reduce.hpp"
 #include "rows_fast.hpp"
 
+#include <stdlib.h>
+
 namespace mml {
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -20,9 +22,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
-
-constexpr int ROW_BLOCK = 256;               // 4 waves = 4 samples in flight per workgroup
-constexpr int ROW_WAVES = ROW_BLOCK / kWave;
 
 // ------------------------------------------------------------------------------------------------
 // gate forward
@@ -295,11 +294,41 @@ __global__ __launch_bounds__(ROW_BLOCK) void head_kernel(const mml_head_group g,
   }
 }
 
-static int row_grid(int64_t B) {
-  int64_t blocks = cdiv(B, ROW_WAVES);
-  if (blocks > 256 * 8) blocks = 256 * 8;  // persistent rows beyond 8 workgroups per CU
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
+// ------------------------------------------------------------------------------------------------
+// host side: the dispatch rule is rows_route.hpp; what follows validates the arguments, reads the switches, launches
+// what the rule planned and reduces the per-workgroup partial sums
+// ------------------------------------------------------------------------------------------------
+// The process-wide switches, read once.
+static const RowsEnv& rows_env() {
+  static const RowsEnv env = [] {
+    auto num = [](const char* name, int dflt) {
+      const char* e = getenv(name);
+      return e ? atoi(e) : dflt;
+    };
+    RowsEnv v = ROWS_ENV_DEFAULT;
+    v.gate_pack = num("MMLREC_GATE_PACK", 1) == 0 ? 0 : 1;
+    v.gate_fwd_mode = num("MMLREC_GATE_FWD_MODE", -1);
+    v.gate_bwd_mode = num("MMLREC_GATE_BWD_MODE", -1);
+    v.gate_hv = num("MMLREC_GATE_HV", 1);
+    v.gate_fwd_wgs = num("MMLREC_GATE_FWD_WGS", ROWS_UNSET);
+    v.gate_bwd_wgs = num("MMLREC_GATE_BWD_WGS", 4);
+    v.head_wgs = num("MMLREC_HEAD_WGS", 2);
+    return v;
+  }();
+  return env;
+}
+
+static thread_local const char* g_rows_last = "";
+// a launch that went out becomes the thread's reported symbol (mml_rows_last_kernel)
+int rows_launched(const char* symbol, const char* what) {
+  const int rc = check_launch(what);
+  if (rc == MML_OK) g_rows_last = symbol;
+  return rc;
+}
+
+static int refused(const RowsRefusal& why) {
+  set_error("%s", why.msg);
+  return why.code;
 }
 
 static int check_gate_group(const mml_gate_group* g, bool bwd, const char* who) {
@@ -324,39 +353,56 @@ static int check_gate_group(const mml_gate_group* g, bool bwd, const char* who) 
   return MML_OK;
 }
 
+static int gate_bwd_generic(const mml_gate_group& g, const GatePlan& p, float* slab, hipStream_t st) {
+  GateBwdAux aux{};
+  for (int i = 0; i < g.n_gates; ++i) aux.wg_off[i] = p.wg_off[i];
+  aux.wg_total = p.wg_total;
+  aux.slab = slab;
+  MML_ROWS_LAUNCH("mml_gate_mix_bwd", p.lds, (g, aux), gate_mix_bwd_kernel);
+}
+
+// the reduction of the slab rows a backward plan's kernel (either family) left: dWg of every active gate
+static ReduceLaunch gate_reduce(const mml_gate_group& g, const GatePlan& p, float* slab) {
+  ReduceLaunch R{};
+  int64_t start = 0;
+  for (int i = 0; i < g.n_gates; ++i) {
+    const mml_gate_desc& d = g.gate[i];
+    if (!d.active) continue;
+    ReduceSeg& s = R.seg[R.n++];
+    s.slab = slab + p.wg_off[i]; s.out = d.dWg; s.n = (int64_t)d.ne * d.Gd; s.sstride = p.stride;
+    s.cols = d.Gd; s.ldo = d.Gd; s.accumulate = 0; s.start = start; s.S = p.grid;
+    start += s.n;
+  }
+  R.total = start;
+  return R;
+}
+
 }  // namespace mml
 
 using namespace mml;
+
+extern "C" const char* mml_rows_last_kernel(void) { return g_rows_last; }
+
+extern "C" int32_t mml_gate_rows_shape(int32_t H, int32_t gd_max, int32_t n_experts, int32_t n_gates, int32_t e_bf16) {
+  return gate_rows_shape(H, gd_max, n_experts, n_gates, e_bf16 != 0, rows_env());
+}
 
 extern "C" int mml_gate_mix_fwd(const mml_gate_group* grp, mml_stream_t stream) {
   int rc = check_gate_group(grp, false, "mml_gate_mix_fwd");
   if (rc) return rc;
   if (grp->B == 0) return MML_OK;
-  rc = gate_fwd_fast(grp, to_stream(stream));
-  if (rc <= 0) return rc;  // handled by the aligned fast path (or failed there)
-  if (grp->out_bf16) {     // (bf16 outputs exist in the fast row kernels only: include/mmlrec.h)
-    set_error("mml_gate_mix_fwd: out_bf16 on a shape the fast row kernel does not serve");
-    return MML_ERR_UNSUPPORTED;
-  }
-  MML_LAUNCH(gate_mix_fwd_kernel, dim3(row_grid(grp->B)), dim3(ROW_BLOCK), 0, to_stream(stream), *grp);
-  return check_launch("mml_gate_mix_fwd");
-}
-
-static int gate_bwd_layout(const mml_gate_group* g, GateBwdAux& aux) {
-  int off = 0;
-  for (int i = 0; i < g->n_gates; ++i) {
-    aux.wg_off[i] = off;
-    if (g->gate[i].active) off += g->gate[i].ne * g->gate[i].Gd;
-  }
-  aux.wg_total = off;
-  return off;
+  GatePlan p;
+  if (gate_route(grp, false, rows_env(), p)) return refused(p.why);
+  hipStream_t st = to_stream(stream);
+  if (p.family != GATE_FWD_GENERIC) return gate_launch_fast(*grp, p, nullptr, st);
+  MML_ROWS_LAUNCH("mml_gate_mix_fwd", p.lds, (*grp), gate_mix_fwd_kernel);
 }
 
 extern "C" int64_t mml_gate_mix_bwd_workspace_bytes(const mml_gate_group* grp) {
   if (!grp) return 0;
   int64_t tot = 0;
   for (int i = 0; i < grp->n_gates && i < MML_MAX_GATES; ++i) tot += (int64_t)grp->gate[i].ne * grp->gate[i].Gd;
-  return (int64_t)256 * 8 * tot * 4 + 256;  // either path uses at most 2048 workgroups
+  return (int64_t)256 * 8 * tot * 4 + 256;  // either family uses at most 2048 workgroups (tests/test_rows_route_cpu.py)
 }
 
 extern "C" int mml_gate_mix_bwd(const mml_gate_group* grp, void* workspace, int64_t workspace_bytes,
@@ -365,91 +411,38 @@ extern "C" int mml_gate_mix_bwd(const mml_gate_group* grp, void* workspace, int6
 }
 
 // phase 1: the row kernel (input gradients stored, per-workgroup partial sums of dWg left in the workspace); phase 2: the
-// reduction of those partial sums into dWg; 0: both.  (Which kernel phase 1 ran is a function of the group alone, so
-// phase 2 finds the same layout.)
+// reduction of those partial sums into dWg; 0: both.  (The plan is a function of the group and the switches alone, so
+// phase 2 finds the layout phase 1 used.)
 extern "C" int mml_gate_mix_bwd_phase(const mml_gate_group* grp, void* workspace, int64_t workspace_bytes, int32_t phase,
                                       mml_stream_t stream) {
   int rc = check_gate_group(grp, true, "mml_gate_mix_bwd");
   if (rc) return rc;
   MML_REQUIRE(phase >= 0 && phase <= 2, "mml_gate_mix_bwd_phase: bad phase");
   if (grp->B == 0) return MML_OK;
-  {
-    GateFastAux fa{};
-    if (gate_fast_config(grp, true, fa)) {
-      MML_REQUIRE(workspace && (int64_t)fa.grid * fa.wg_total * 4 <= workspace_bytes,
-                  "mml_gate_mix_bwd: workspace too small");
-      fa.slab = static_cast<float*>(workspace);
-      rc = 0;
-      if (phase != 2) rc = gate_bwd_fast(grp, fa, to_stream(stream));
-      else if (!gate_bwd_fast_serves(grp, fa)) rc = 1;
-      if (rc < 0) return rc;
-      if (rc == 0) {
-        if (phase == 1) return MML_OK;
-        ReduceLaunch R{};
-        int64_t start = 0;
-        for (int i = 0; i < grp->n_gates; ++i) {
-          const mml_gate_desc& d = grp->gate[i];
-          if (!d.active) continue;
-          ReduceSeg& s = R.seg[R.n++];
-          s.slab = fa.slab + fa.wg_off[i]; s.out = d.dWg; s.n = (int64_t)d.ne * d.Gd; s.sstride = fa.wg_total;
-          s.cols = d.Gd; s.ldo = d.Gd; s.accumulate = 0; s.start = start; s.S = fa.grid;
-          start += s.n;
-        }
-        R.total = start;
-        return launch_slab_reduce(R, to_stream(stream), "mml_gate_mix_bwd(reduce)");
-      }
-    }
-  }
-  if (grp->out_bf16) {  // (bf16 outputs exist in the fast row kernels only: include/mmlrec.h)
-    set_error("mml_gate_mix_bwd: out_bf16 on a shape the fast row kernel does not serve");
-    return MML_ERR_UNSUPPORTED;
-  }
-  GateBwdAux aux{};
-  const int tot = gate_bwd_layout(grp, aux);
-  const int grid = row_grid(grp->B);
-  MML_REQUIRE(workspace && (int64_t)grid * tot * 4 <= workspace_bytes, "mml_gate_mix_bwd: workspace too small");
-  const size_t lds = (size_t)(tot + ROW_WAVES * MML_MAX_GATES * MML_MAX_EXPERTS) * 4;
-  MML_REQUIRE(lds <= 64 * 1024, "mml_gate_mix_bwd: gate weights too large for the LDS accumulators (%zu B)", lds);
-  aux.slab = static_cast<float*>(workspace);
+  GatePlan p;
+  const char* why = gate_route(grp, true, rows_env(), p);
+  // (the order these checks always had: the fast kernel's workspace, bf16 outputs without it, the generic kernel's
+  // workspace, its LDS)
+  MML_REQUIRE(!p.ws_first || (workspace && p.ws_first <= workspace_bytes), "mml_gate_mix_bwd: workspace too small");
+  if (why && p.why.code == MML_ERR_UNSUPPORTED) return refused(p.why);
+  MML_REQUIRE(workspace && p.ws_bytes <= workspace_bytes, "mml_gate_mix_bwd: workspace too small");
+  if (why) return refused(p.why);
+  float* slab = static_cast<float*>(workspace);
+  hipStream_t st = to_stream(stream);
   if (phase != 2) {
-    MML_LAUNCH(gate_mix_bwd_kernel, dim3(grid), dim3(ROW_BLOCK), lds, to_stream(stream), *grp, aux);
-    rc = check_launch("mml_gate_mix_bwd");
+    rc = p.family == GATE_BWD_FAST ? gate_launch_fast(*grp, p, slab, st) : gate_bwd_generic(*grp, p, slab, st);
     if (rc) return rc;
   }
   if (phase == 1) return MML_OK;
-  ReduceLaunch R{};
-  int64_t start = 0;
-  for (int i = 0; i < grp->n_gates; ++i) {
-    const mml_gate_desc& d = grp->gate[i];
-    if (!d.active) continue;
-    ReduceSeg& s = R.seg[R.n++];
-    s.slab = aux.slab + aux.wg_off[i]; s.out = d.dWg; s.n = (int64_t)d.ne * d.Gd; s.sstride = tot;
-    s.cols = d.Gd; s.ldo = d.Gd; s.accumulate = 0; s.start = start; s.S = grid;
-    start += s.n;
-  }
-  R.total = start;
-  return launch_slab_reduce(R, to_stream(stream), "mml_gate_mix_bwd(reduce)");
+  return launch_slab_reduce(gate_reduce(*grp, p, slab), st, "mml_gate_mix_bwd(reduce)");
 }
 
-static bool head_group_gated(const mml_head_group* g) {
-  for (int t = 0; t < g->n_heads; ++t)
-    if (g->head[t].gate) return true;
-  return false;
-}
-
-static bool head_group_kinds(const mml_head_group* g) {
-  for (int t = 0; t < g->n_heads; ++t)
-    if (g->head[t].kind) return true;
-  return false;
-}
-
-static int check_head_group(const mml_head_group* g, bool train, const char* who, int& hmax) {
+static int check_head_group(const mml_head_group* g, bool train, const char* who) {
   MML_REQUIRE(g, "%s: null group", who);
   MML_REQUIRE(g->n_heads >= 1 && g->n_heads <= MML_MAX_HEADS && g->B >= 0, "%s: n_heads=%d", who, g->n_heads);
   MML_REQUIRE(g->prob && g->ldprob >= g->n_heads, "%s: prob null / ldprob", who);
   MML_REQUIRE(!train || (g->y && g->ldy >= g->n_heads) || (g->dprob && g->lddprob >= g->n_heads),
               "%s: training needs y or dprob", who);
-  hmax = 0;
   for (int t = 0; t < g->n_heads; ++t) {
     const mml_head_desc& d = g->head[t];
     MML_REQUIRE(d.Hin && d.w && d.bias && d.H >= 1 && d.H <= HEAD_SLOTS * 64 && d.ldh >= d.H,
@@ -461,7 +454,6 @@ static int check_head_group(const mml_head_group* g, bool train, const char* who
                 "%s: gated head %d: gate pitch / dgate", who, t);
     MML_REQUIRE(!d.gate || d.gate_act == MML_ACT_NONE || d.gate_act == MML_ACT_SIGMOID || d.gate_act == MML_ACT_SIGMOID2,
                 "%s: gated head %d: gate_act must be none, sigmoid or 2 sigmoid", who, t);
-    if (d.H > hmax) hmax = d.H;
     const int kc = head_kind_check(d.kind, train && g->y);
     MML_REQUIRE(kc != 1, "%s: head %d: kind 0x%x is not MML_HEAD_KIND(output form, loss)", who, t, d.kind);
     if (kc == 2) {
@@ -473,32 +465,33 @@ static int check_head_group(const mml_head_group* g, bool train, const char* who
   return MML_OK;
 }
 
+static int head_launch(const mml_head_group& g, const HeadPlan& p, float* slab, bool train, const char* what, hipStream_t st) {
+  if (p.family == HEAD_FAST) return head_launch_fast(g, p, slab, train, st);
+  HeadAux aux{};
+  aux.slab = slab;
+  aux.stride = p.stride;
+  aux.hmax = p.hmax;
+  aux.train = train ? 1 : 0;
+  if (p.kinds) MML_ROWS_LAUNCH(what, 0, (g, aux), head_kernel<true>);
+  MML_ROWS_LAUNCH(what, 0, (g, aux), head_kernel<false>);
+}
+
 extern "C" int64_t mml_head_workspace_bytes(const mml_head_group* grp) {
   if (!grp) return 0;
   int hmax = 0;
   for (int t = 0; t < grp->n_heads && t < MML_MAX_HEADS; ++t)
     if (grp->head[t].H > hmax) hmax = grp->head[t].H;
-  return (int64_t)256 * 8 * (grp->n_heads * (hmax + 1) + 1) * 4 + 256;  // either path uses at most 2048 workgroups
+  // either family uses at most 2048 workgroups (tests/test_rows_route_cpu.py)
+  return (int64_t)256 * 8 * (grp->n_heads * (hmax + 1) + 1) * 4 + 256;
 }
 
 extern "C" int mml_head_fwd(const mml_head_group* grp, mml_stream_t stream) {
-  int hmax;
-  int rc = check_head_group(grp, false, "mml_head_fwd", hmax);
+  int rc = check_head_group(grp, false, "mml_head_fwd");
   if (rc) return rc;
   if (grp->B == 0) return MML_OK;
-  {
-    HeadFastAux fa{};
-    if (head_fast_config(grp, false, hmax, fa)) return head_fast(grp, fa, to_stream(stream));
-  }
-  if (head_group_gated(grp)) {
-    set_error("mml_head_fwd: gated heads on a shape the fast row kernel does not serve");
-    return MML_ERR_UNSUPPORTED;
-  }
-  HeadAux aux{};
-  aux.hmax = hmax;
-  if (head_group_kinds(grp)) MML_LAUNCH(head_kernel<true>, dim3(row_grid(grp->B)), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
-  else MML_LAUNCH(head_kernel<false>, dim3(row_grid(grp->B)), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
-  return check_launch("mml_head_fwd");
+  HeadPlan p;
+  if (head_route(grp, false, rows_env(), p)) return refused(p.why);
+  return head_launch(*grp, p, nullptr, false, "mml_head_fwd", to_stream(stream));
 }
 
 extern "C" int mml_head_bce_fwd_bwd(const mml_head_group* grp, void* workspace, int64_t workspace_bytes,
@@ -511,33 +504,16 @@ extern "C" int mml_head_bce_fwd_bwd(const mml_head_group* grp, void* workspace, 
 extern "C" int mml_head_bce_fwd_bwd_phase(const mml_head_group* grp, void* workspace, int64_t workspace_bytes, int32_t phase,
                                           mml_stream_t stream) {
   MML_REQUIRE(phase >= 0 && phase <= 2, "mml_head_bce_fwd_bwd_phase: bad phase");
-  int hmax;
-  int rc = check_head_group(grp, true, "mml_head_bce_fwd_bwd", hmax);
+  int rc = check_head_group(grp, true, "mml_head_bce_fwd_bwd");
   if (rc) return rc;
   if (grp->B == 0) return MML_OK;
-  int grid = row_grid(grp->B);
-  HeadAux aux{};
-  aux.hmax = hmax;
-  aux.stride = grp->n_heads * (hmax + 1) + 1;
-  aux.train = 1;
-  HeadFastAux fa{};
-  const bool fast = head_fast_config(grp, true, hmax, fa) != 0;
-  if (fast) grid = fa.grid;
-  MML_REQUIRE(workspace && (int64_t)grid * aux.stride * 4 <= workspace_bytes, "mml_head_bce_fwd_bwd: workspace too small");
-  aux.slab = static_cast<float*>(workspace);
+  HeadPlan p;
+  const char* why = head_route(grp, true, rows_env(), p);
+  MML_REQUIRE(workspace && p.ws_bytes <= workspace_bytes, "mml_head_bce_fwd_bwd: workspace too small");
+  float* slab = static_cast<float*>(workspace);
   if (phase != 2) {
-    if (fast) {
-      fa.slab = aux.slab; fa.stride = aux.stride; fa.train = 1;
-      rc = head_fast(grp, fa, to_stream(stream));
-    } else {
-      if (grp->dh_bf16 || head_group_gated(grp)) {
-        set_error("mml_head_bce_fwd_bwd: dh_bf16 / gated heads on a shape the fast row kernel does not serve");
-        return MML_ERR_UNSUPPORTED;
-      }
-      if (head_group_kinds(grp)) MML_LAUNCH(head_kernel<true>, dim3(grid), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
-      else MML_LAUNCH(head_kernel<false>, dim3(grid), dim3(ROW_BLOCK), 0, to_stream(stream), *grp, aux);
-      rc = check_launch("mml_head_bce_fwd_bwd");
-    }
+    if (why) return refused(p.why);
+    rc = head_launch(*grp, p, slab, true, "mml_head_bce_fwd_bwd", to_stream(stream));
     if (rc) return rc;
   }
   if (phase == 1) return MML_OK;
@@ -546,18 +522,18 @@ extern "C" int mml_head_bce_fwd_bwd_phase(const mml_head_group* grp, void* works
   for (int t = 0; t < grp->n_heads; ++t) {
     const mml_head_desc& d = grp->head[t];
     ReduceSeg& w = R.seg[R.n++];
-    w.slab = aux.slab + t * (hmax + 1); w.out = d.dw; w.n = d.H; w.sstride = aux.stride; w.cols = d.H; w.ldo = d.H;
-    w.start = start; w.S = grid;
+    w.slab = slab + t * (p.hmax + 1); w.out = d.dw; w.n = d.H; w.sstride = p.stride; w.cols = d.H; w.ldo = d.H;
+    w.start = start; w.S = p.grid;
     start += d.H;
     ReduceSeg& bb = R.seg[R.n++];
-    bb.slab = aux.slab + t * (hmax + 1) + hmax; bb.out = d.dbias; bb.n = 1; bb.sstride = aux.stride; bb.cols = 1;
-    bb.ldo = 1; bb.start = start; bb.S = grid;
+    bb.slab = slab + t * (p.hmax + 1) + p.hmax; bb.out = d.dbias; bb.n = 1; bb.sstride = p.stride; bb.cols = 1;
+    bb.ldo = 1; bb.start = start; bb.S = p.grid;
     start += 1;
   }
   if (grp->loss) {
     ReduceSeg& l = R.seg[R.n++];
-    l.slab = aux.slab + grp->n_heads * (hmax + 1); l.out = grp->loss; l.n = 1; l.sstride = aux.stride; l.cols = 1;
-    l.ldo = 1; l.start = start; l.S = grid;
+    l.slab = slab + grp->n_heads * (p.hmax + 1); l.out = grp->loss; l.n = 1; l.sstride = p.stride; l.cols = 1;
+    l.ldo = 1; l.start = start; l.S = p.grid;
     start += 1;
   }
   R.total = start;

@@ -11,9 +11,27 @@
 #include "reduce.hpp"
 #include "rows_fast.hpp"
 
-#include <stdlib.h>
-
 namespace mml {
+
+// The kernels' argument blocks, filled from a plan (rows_route.hpp) by the launchers at the end of this file.
+struct GateFastAux {
+  int32_t wg_off[MML_MAX_GATES];  // float offset of gate i's weight block (all gates, active or not)
+  int32_t wg_total;
+  int32_t lps, ne, ng, grid;
+  int32_t ident;                  // every gate mixes experts 0..ne-1 in order (MMoE): backward reuses its expert-row loads
+  int32_t hv;                     // 16-byte pieces of an expert / mixture row per lane: 1, or 2 (bf16 rows of 129..256 columns
+                                  // on 32-lane groups -- two samples per wave and trip, 16-byte accesses)
+  float* slab;                    // backward: [grid][wg_total] per-workgroup dWg partials
+};
+
+struct HeadFastAux {
+  float* slab;                    // [grid][stride]
+  int32_t stride, hmax, train;
+  int32_t lps, nt, grid;
+  int32_t gated;                  // some head reads Hin (.) gate (mml_head_desc.gate)
+  int32_t kinds;                  // some head has a non-zero kind: the KINDS instantiation (out_bits / loss_bits below)
+  uint32_t out_bits, loss_bits;   // head t: output form in bit t, loss in bits 2t, 2t + 1 (a lane picks its head's by shifts)
+};
 
 // Sum over the LPS lanes of a lane group, result in every lane.  Inside a row of 16 lanes the exchange is a DPP modifier
 // (quad permutes, then the two mirrors: VALU only); only the steps across rows go through the LDS crossbar
@@ -82,15 +100,6 @@ __device__ __forceinline__ float quad_sum(float v) {
   v += dpp_get<0xB1>(v);
   return v + dpp_get<0x4E>(v);
 }
-// (lab knob MMLREC_GATE_PACK=0: the eight separate butterflies of round 5)
-static int gate_pack_on() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("MMLREC_GATE_PACK");
-    on = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return on;
-}
 
 __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
   return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w;
@@ -137,9 +146,7 @@ __device__ __forceinline__ void st4o(float* base, int64_t off, const float4& v, 
   }
 }
 
-constexpr int FB = 256;          // threads per workgroup
-constexpr int FW = FB / 64;      // waves per workgroup
-
+// (FB threads = FW waves per workgroup: rows_route.hpp)
 // ------------------------------------------------------------------------------------------------ gate forward
 template <int LPS, int NE>
 __global__ __launch_bounds__(FB) void gate_fwd_fast_kernel(const mml_gate_group g, const GateFastAux aux) {
@@ -798,7 +805,7 @@ __global__ __launch_bounds__(FB) void gate_bwd_fast_kernel(const mml_gate_group 
 #define MML_HEAD_U (NT <= 2 ? 4 : ((NT <= 4 && !GATED) ? 4 : 2))
 #endif
 // KINDS: some head of the group has a non-zero kind (identity output, squared / absolute error: include/mmlrec.h K5).  The
-// host picks the instantiation (head_fast_config), so the all-binary one carries no branch on it.
+// host picks the instantiation (rows_route.hpp: head_route), so the all-binary one carries no branch on it.
 template <int LPS, int NT, bool GATED, bool KINDS>
 __global__ __launch_bounds__(FB) void head_fast_kernel(const mml_head_group g, const HeadFastAux aux) {
   __shared__ float red[FW][NT * (4 * LPS + 1) + 1];
@@ -1005,260 +1012,79 @@ __global__ __launch_bounds__(FB) void head_fast_kernel(const mml_head_group g, c
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int pick_lps(int width) { return width <= 64 ? 16 : (width <= 128 ? 32 : (width <= 256 ? 64 : 0)); }
-
-int fast_row_grid(int64_t B, int lps, int per_cu = 4) {
-  const int spb = FW * (64 / lps);
-  int64_t blocks = cdiv(B, spb);
-  if (blocks > 256 * per_cu) blocks = 256 * per_cu;  // persistent: one partial slab row per workgroup goes to the reducer
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
-static bool ok4(const void* p, int64_t ld) { return aligned16(p) && (ld % 4 == 0); }
-
-// does the load-once forward take this group on lane groups of `lps` lanes?  (MMLREC_GATE_FWD_MODE=0: per-gate kernel
-// everywhere, a measurement knob)
-static size_t gate_fwd_once_lds(const GateFastAux& aux, int lps) {
-  return ((size_t)aux.wg_total + (size_t)FW * (64 / lps) * aux.ng * MML_MAX_EXPERTS + (size_t)aux.ng * aux.ne) * 4;
-}
-static bool gate_fwd_once_ok(const mml_gate_group& g, const GateFastAux& aux, int lps) {
-  static int forced = -2;
-  if (forced == -2) {
-    const char* e = getenv("MMLREC_GATE_FWD_MODE");
-    forced = e ? atoi(e) : -1;
-  }
-  return forced != 0 && g.n_experts <= aux.ne && aux.ne * aux.ng <= 32 && gate_fwd_once_lds(aux, lps) <= 60 * 1024;
-}
-
-int gate_fast_config(const mml_gate_group* g, bool bwd, GateFastAux& aux) {
-  if (g->H % 4 || g->H > 256) return 0;
-  int width = g->H, nemax = 0, off = 0;
-  for (int x = 0; x < g->n_experts; ++x) {
-    if (!ok4(g->E[x], g->lde[x])) return 0;
-    if (bwd && !ok4(g->dE[x], g->ldde[x])) return 0;
-  }
-  for (int i = 0; i < g->n_gates; ++i) {
-    const mml_gate_desc& d = g->gate[i];
-    if (d.Gd % 4 || d.Gd > 256 || !ok4(d.G, d.ldg) || !aligned16(d.Wg)) return 0;
-    if (!bwd && !ok4(d.mix, d.ldmix)) return 0;
-    if (bwd && d.active && (!ok4(d.dmix, d.lddmix) || !ok4(d.dG, d.lddg))) return 0;
-    if (d.Gd > width) width = d.Gd;
-    if (d.ne > nemax) nemax = d.ne;
-    aux.wg_off[i] = off;
-    off += d.ne * d.Gd;
-  }
-  aux.wg_total = off;
-  aux.ident = 1;
-  for (int i = 0; i < g->n_gates; ++i) {
-    const mml_gate_desc& d = g->gate[i];
-    if (d.ne != g->n_experts) aux.ident = 0;
-    for (int e = 0; e < d.ne; ++e)
-      if (d.expert[e] != e) aux.ident = 0;
-  }
-  aux.lps = pick_lps(width);
-  aux.ne = nemax <= 4 ? 4 : (nemax <= 8 ? 8 : 16);
-  aux.ng = g->n_gates <= 2 ? 2 : (g->n_gates == 3 ? 3 : (g->n_gates <= 4 ? 4 : 8));  // 3: a PLE level at T = 2
-  aux.hv = 1;
-  // forward, bf16 expert rows wider than 128 columns under gate inputs of at most 128 (KuaiRec-32 in the bf16-storage mode):
-  // 32-lane groups with eight row columns per lane (gate_fwd_once_kernel<.., HV = 2>; MMLREC_GATE_HV=0: one sample per wave)
-  static int bwd_forced = -2;
-  if (bwd_forced == -2) {
-    const char* e = getenv("MMLREC_GATE_BWD_MODE");
-    bwd_forced = e ? atoi(e) : -1;
-  }
-  // (lab, MMLREC_GATE_HV=2: the same form on 16-lane groups for fp32 rows of 65..128 columns under gate inputs of at most 64 --
-  //  AE-30's MMoE: four samples per wave and trip)
-  static int hv16 = -1;
-  if (hv16 < 0) {
-    const char* e = getenv("MMLREC_GATE_HV");
-    hv16 = (e && atoi(e) == 2) ? 1 : 0;
-  }
-  const bool wide16 = (g->out_bf16 & MML_GATE_E_BF16) && g->H > 128;
-  const bool narrow32 = hv16 && !(g->out_bf16 & MML_GATE_E_BF16) && g->H > 64 && g->H <= 128;
-  if ((wide16 || narrow32) && g->H % 8 == 0 && aux.ne == 4 && aux.ng == 2 && gate_pack_on() &&
-      (!bwd || (aux.ident && bwd_forced == -1))) {
-    const int lps_hv = wide16 ? 32 : 16, gd_max = wide16 ? 128 : 64;
-    static int hv_on = -1;
-    if (hv_on < 0) {
-      const char* e = getenv("MMLREC_GATE_HV");
-      hv_on = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    bool ok = hv_on != 0 && g->n_experts <= 4 && (bwd || gate_fwd_once_ok(*g, aux, lps_hv));  // (only these kernels have the form)
-    for (int x = 0; x < g->n_experts && ok; ++x)
-      ok = g->lde[x] % 8 == 0 && (!bwd || g->ldde[x] % ((g->out_bf16 & MML_GATE_DE_BF16) ? 8 : 4) == 0);
-    for (int i = 0; i < g->n_gates && ok; ++i)
-      ok = g->gate[i].Gd <= gd_max && (bwd || g->gate[i].ldmix % ((g->out_bf16 & MML_GATE_MIX_BF16) ? 8 : 4) == 0);
-    if (ok) {
-      aux.lps = lps_hv;
-      aux.hv = 2;
-    }
-  }
-  if (bwd && aux.ne * aux.ng > 32) return 0;  // register budget (upstream gradients, coefficients)
-  static int fwd_per_cu = -1;
-  if (fwd_per_cu < 0) {
-    const char* e = getenv("MMLREC_GATE_FWD_WGS");
-    fwd_per_cu = e ? atoi(e) : 4;
-  }
-  // the forward kernel writes no per-workgroup partials.  Round 5: with the next trip's rows requested ahead (91 VGPRs for
-  // MMoE's 4 experts x 2 gates) FOUR workgroups per CU are the best grid -- AE-30 at B = 65 536, device time of the call:
-  // 45.7 us (5.2 TB/s of its own bytes) against 48.4 with five, 54.5 with six, 52.8 with eight; before the prefetch six
-  // were one round of resident workgroups (64 us; eight 67-68, twelve 72).
-  static int bwd_per_cu = -1;
-  if (bwd_per_cu < 0) {
-    const char* e = getenv("MMLREC_GATE_BWD_WGS");
-    bwd_per_cu = e ? atoi(e) : 4;
-  }
-  // (the forward of a PLE level -- 8 experts x 3 gates, 148 VGPRs: three waves per SIMD -- is one round of resident
-  // workgroups at three per CU: 119.9 us against 126.6 with four, 132.0 with two, B = 65 536)
-  const int fwd_here = (!getenv("MMLREC_GATE_FWD_WGS") && aux.ne * aux.ng > 16) ? 3 : fwd_per_cu;
-  aux.grid = fast_row_grid(g->B, aux.lps, bwd ? bwd_per_cu : fwd_here);
-  return aux.lps;
-}
-
-template <int LPS>
-static void launch_gate_fwd(const mml_gate_group& g, const GateFastAux& aux, hipStream_t st) {
-  dim3 gr(aux.grid), bl(FB);
-  const size_t lds1 = gate_fwd_once_lds(aux, LPS);
-  if (gate_fwd_once_ok(g, aux, LPS)) {
-#define MML_GF(NE_, NG_) MML_LAUNCH((gate_fwd_once_kernel<LPS, NE_, NG_>), gr, bl, lds1, st, g, aux)
-    if (aux.ne == 4 && aux.ng == 2) {
-      if constexpr (LPS == 32 || LPS == 16) {
-        if (aux.hv == 2) {
-          MML_LAUNCH((gate_fwd_once_kernel<LPS, 4, 2, true, 2>), gr, bl, lds1, st, g, aux);
-          return;
-        }
-      }
-      if (gate_pack_on()) MML_LAUNCH((gate_fwd_once_kernel<LPS, 4, 2, true>), gr, bl, lds1, st, g, aux);
-      else MML_GF(4, 2);
-      return;
-    }
-    if (aux.ne == 4 && aux.ng == 3) { MML_GF(4, 3); return; }
-    if (aux.ne == 4 && aux.ng == 4) { MML_GF(4, 4); return; }
-    if (aux.ne == 4 && aux.ng == 8) { MML_GF(4, 8); return; }
-    if (aux.ne == 8 && aux.ng == 2) { MML_GF(8, 2); return; }
-    if (aux.ne == 8 && aux.ng == 3) { MML_GF(8, 3); return; }
-    if (aux.ne == 8 && aux.ng == 4) { MML_GF(8, 4); return; }
-    if (aux.ne == 16 && aux.ng == 2) { MML_GF(16, 2); return; }
-#undef MML_GF
-  }
-  const size_t lds = (size_t)aux.wg_total * 4;
-  if (aux.ne == 4) MML_LAUNCH((gate_fwd_fast_kernel<LPS, 4>), gr, bl, lds, st, g, aux);
-  else if (aux.ne == 8) MML_LAUNCH((gate_fwd_fast_kernel<LPS, 8>), gr, bl, lds, st, g, aux);
-  else MML_LAUNCH((gate_fwd_fast_kernel<LPS, 16>), gr, bl, lds, st, g, aux);
-}
-
-int gate_fwd_fast(const mml_gate_group* g, hipStream_t st) {
+// csrc/rows_route.hpp decides.  What follows fills a kernel's argument block from the plan and launches the instantiation
+// the plan names: one line per instantiation, the plan's numbers against the literal template arguments (the text
+// mml_rows_last_kernel() reports).  A plan that names none is a defect of the rule, reported as an error.
+int gate_launch_fast(const mml_gate_group& g, const GatePlan& p, float* slab, hipStream_t st) {
   GateFastAux aux{};
-  if (!gate_fast_config(g, false, aux)) return 1;  // not handled
-  if ((size_t)aux.wg_total * 4 > 48 * 1024) return 1;
-  if (aux.lps == 16) launch_gate_fwd<16>(*g, aux, st);
-  else if (aux.lps == 32) launch_gate_fwd<32>(*g, aux, st);
-  else launch_gate_fwd<64>(*g, aux, st);
-  return check_launch("mml_gate_mix_fwd(fast)");
-}
-
-size_t gate_bwd_fast_lds(const GateFastAux& aux) {
-  const int spw = 64 / aux.lps;
-  return ((size_t)aux.wg_total + (size_t)FW * spw * aux.ng * MML_MAX_EXPERTS + (size_t)FW * spw * aux.wg_total +
-          (size_t)aux.ng * aux.ne) * 4;
-}
-
-template <int LPS>
-static int launch_gate_bwd(const mml_gate_group& g, const GateFastAux& aux, hipStream_t st) {
-  const size_t lds = gate_bwd_fast_lds(aux);
-  dim3 gr(aux.grid), bl(FB);
-  static int forced = -2;  // MMLREC_GATE_BWD_MODE=0|1|2: measurement knob (default: best applicable mode)
-  if (forced == -2) {
-    const char* e = getenv("MMLREC_GATE_BWD_MODE");
-    forced = e ? atoi(e) : -1;
+  for (int i = 0; i < MML_MAX_GATES; ++i) aux.wg_off[i] = p.wg_off[i];
+  aux.wg_total = p.wg_total;
+  aux.lps = p.lps;
+  aux.ne = p.ne;
+  aux.ng = p.ng;
+  aux.grid = p.grid;
+  aux.ident = p.ident;
+  aux.hv = p.hv;
+  aux.slab = slab;
+  // the eight combinations with NE * NG <= 32 (3 gates: a PLE level at T = 2)
+#define GATE_ARMS(ARM, L) ARM(L, 4, 2) ARM(L, 4, 3) ARM(L, 4, 4) ARM(L, 4, 8) ARM(L, 8, 2) ARM(L, 8, 3) ARM(L, 8, 4) ARM(L, 16, 2)
+  if (p.family == GATE_FWD_ONCE) {
+#define ONCE(L, NE, NG, PACK, HV)                                                      \
+  if (p.lps == L && p.ne == NE && p.ng == NG && (p.pack != 0) == PACK && p.hv == HV)   \
+    MML_ROWS_LAUNCH("mml_gate_mix_fwd(fast)", p.lds, (g, aux), gate_fwd_once_kernel<L, NE, NG, PACK, HV>);
+#define ONCE_PLAIN(L, NE, NG) ONCE(L, NE, NG, false, 1)
+    GATE_ARMS(ONCE_PLAIN, 16) GATE_ARMS(ONCE_PLAIN, 32) GATE_ARMS(ONCE_PLAIN, 64)
+    // 4 experts x 2 gates: the packed sums, and on them eight row columns per lane (32-lane groups; 16: the lab form)
+    ONCE(16, 4, 2, true, 1) ONCE(32, 4, 2, true, 1) ONCE(64, 4, 2, true, 1)
+    ONCE(16, 4, 2, true, 2) ONCE(32, 4, 2, true, 2)
+#undef ONCE_PLAIN
+#undef ONCE
+  } else if (p.family == GATE_FWD_FAST) {
+#define PER_GATE(L, NE) \
+  if (p.lps == L && p.ne == NE) MML_ROWS_LAUNCH("mml_gate_mix_fwd(fast)", p.lds, (g, aux), gate_fwd_fast_kernel<L, NE>);
+    PER_GATE(16, 4) PER_GATE(16, 8) PER_GATE(16, 16) PER_GATE(32, 4) PER_GATE(32, 8) PER_GATE(32, 16)
+    PER_GATE(64, 4) PER_GATE(64, 8) PER_GATE(64, 16)
+#undef PER_GATE
+  } else if (p.family == GATE_BWD_FAST) {
+#define BWD(L, NE, NG, MODE, HV)                                                  \
+  if (p.lps == L && p.ne == NE && p.ng == NG && p.mode == MODE && p.hv == HV)     \
+    MML_ROWS_LAUNCH("mml_gate_mix_bwd(fast)", p.lds, (g, aux), gate_bwd_fast_kernel<L, NE, NG, MODE, HV>);
+    // (every MODE of every combination, as they were always built; the rule asks for MODE 1 where NE * NG <= 8)
+#define BWD_MODES(L, NE, NG) BWD(L, NE, NG, 0, 1) BWD(L, NE, NG, 1, 1) BWD(L, NE, NG, 2, 1)
+    GATE_ARMS(BWD_MODES, 16) GATE_ARMS(BWD_MODES, 32) GATE_ARMS(BWD_MODES, 64)
+    BWD(16, 4, 2, 1, 2) BWD(32, 4, 2, 1, 2)
+#undef BWD_MODES
+#undef BWD
   }
-#define MML_GB(NE_, NG_)                                                                       \
-  do {                                                                                         \
-    if (aux.ident && NE_ * NG_ <= 8 && forced != 2 && forced != 0) MML_LAUNCH((gate_bwd_fast_kernel<LPS, NE_, NG_, 1>), gr, bl, lds, st, g, aux); \
-    else if (g.n_experts <= NE_ && NE_ * NG_ <= 32 && forced != 0) MML_LAUNCH((gate_bwd_fast_kernel<LPS, NE_, NG_, 2>), gr, bl, lds, st, g, aux); \
-    else MML_LAUNCH((gate_bwd_fast_kernel<LPS, NE_, NG_, 0>), gr, bl, lds, st, g, aux);   \
-  } while (0)
-  if (aux.hv == 2) {  // (gate_fast_config: the MMoE form on 32-lane groups)
-    if constexpr (LPS == 32 || LPS == 16) MML_LAUNCH((gate_bwd_fast_kernel<LPS, 4, 2, 1, 2>), gr, bl, lds, st, g, aux);
-    else return 1;
-  } else if (aux.ne == 4 && aux.ng == 2) MML_GB(4, 2);
-  else if (aux.ne == 4 && aux.ng == 4) MML_GB(4, 4);
-  else if (aux.ne == 4 && aux.ng == 8) MML_GB(4, 8);
-  else if (aux.ne == 8 && aux.ng == 2) MML_GB(8, 2);
-  else if (aux.ne == 8 && aux.ng == 3) MML_GB(8, 3);
-  else if (aux.ne == 4 && aux.ng == 3) MML_GB(4, 3);
-  else if (aux.ne == 8 && aux.ng == 4) MML_GB(8, 4);
-  else if (aux.ne == 16 && aux.ng == 2) MML_GB(16, 2);
-  else return 1;
-#undef MML_GB
-  return check_launch("mml_gate_mix_bwd(fast)");
+#undef GATE_ARMS
+  set_error("gate row kernels: no instantiation for family %d <%d, %d, %d> pack %d hv %d mode %d", p.family, p.lps, p.ne, p.ng,
+            p.pack, p.hv, p.mode);
+  return MML_ERR_UNSUPPORTED;
 }
 
-bool gate_bwd_fast_serves(const mml_gate_group* g, const GateFastAux& aux) {
-  (void)g;
-  return gate_bwd_fast_lds(aux) <= 60 * 1024;
-}
-
-int gate_bwd_fast(const mml_gate_group* g, GateFastAux& aux, hipStream_t st) {
-  if (!gate_bwd_fast_serves(g, aux)) return 1;
-  if (aux.lps == 16) return launch_gate_bwd<16>(*g, aux, st);
-  if (aux.lps == 32) return launch_gate_bwd<32>(*g, aux, st);
-  return launch_gate_bwd<64>(*g, aux, st);
-}
-
-int head_fast_config(const mml_head_group* g, bool train, int hmax, HeadFastAux& aux) {
-  if (hmax % 4 || hmax > 256) return 0;
-  for (int t = 0; t < g->n_heads; ++t) {
-    const mml_head_desc& d = g->head[t];
-    if (d.H % 4 || !ok4(d.Hin, d.ldh) || !aligned16(d.w) || (d.w2 && !aligned16(d.w2))) return 0;
-    if (train && !ok4(d.dH, d.lddh)) return 0;
-    if (d.gate && (!ok4(d.gate, d.ldgate) || (train && !ok4(d.dgate, d.lddgate)) || g->dh_bf16)) return 0;
-    if (d.gate) aux.gated = 1;
-    if (d.kind) aux.kinds = 1;
-    aux.out_bits |= (uint32_t)(MML_HEAD_KIND_OUT(d.kind) & 1) << t;
-    aux.loss_bits |= (uint32_t)(MML_HEAD_KIND_LOSS(d.kind) & 3) << (2 * t);
-  }
-  aux.lps = pick_lps(hmax);
-  aux.nt = g->n_heads <= 2 ? 2 : (g->n_heads <= 4 ? 4 : 8);
-  aux.hmax = hmax;
-  static int head_per_cu = -1;
-  if (head_per_cu < 0) {
-    const char* e = getenv("MMLREC_HEAD_WGS");
-    head_per_cu = e ? atoi(e) : 2;
-  }
-  // (two workgroups per CU since the trips hold U samples per lane group: the call -- kernel + the reduction of one
-  // partial row per workgroup -- takes 29.4 us on AE-30 / 77.9 on PepNet at B = 65 536 against 34.3 / 83.0 with four,
-  // 47.8 / 84.0 with eight, 31.5 / 104.8 with one)
-  aux.grid = fast_row_grid(g->B, aux.lps, head_per_cu);
-  return aux.lps;
-}
-
-template <int LPS, bool KINDS>
-static void launch_head_k(const mml_head_group& g, const HeadFastAux& aux, hipStream_t st) {
-  dim3 gr(aux.grid), bl(FB);
-  if (aux.gated) {
-    if (aux.nt == 2) MML_LAUNCH((head_fast_kernel<LPS, 2, true, KINDS>), gr, bl, 0, st, g, aux);
-    else if (aux.nt == 4) MML_LAUNCH((head_fast_kernel<LPS, 4, true, KINDS>), gr, bl, 0, st, g, aux);
-    else MML_LAUNCH((head_fast_kernel<LPS, 8, true, KINDS>), gr, bl, 0, st, g, aux);
-    return;
-  }
-  if (aux.nt == 2) MML_LAUNCH((head_fast_kernel<LPS, 2, false, KINDS>), gr, bl, 0, st, g, aux);
-  else if (aux.nt == 4) MML_LAUNCH((head_fast_kernel<LPS, 4, false, KINDS>), gr, bl, 0, st, g, aux);
-  else MML_LAUNCH((head_fast_kernel<LPS, 8, false, KINDS>), gr, bl, 0, st, g, aux);
-}
-
-template <int LPS>
-static void launch_head(const mml_head_group& g, const HeadFastAux& aux, hipStream_t st) {
-  if (aux.kinds) launch_head_k<LPS, true>(g, aux, st);
-  else launch_head_k<LPS, false>(g, aux, st);
-}
-
-int head_fast(const mml_head_group* g, const HeadFastAux& aux, hipStream_t st) {
-  if (aux.lps == 16) launch_head<16>(*g, aux, st);
-  else if (aux.lps == 32) launch_head<32>(*g, aux, st);
-  else launch_head<64>(*g, aux, st);
-  return check_launch("mml_head(fast)");
+int head_launch_fast(const mml_head_group& g, const HeadPlan& p, float* slab, bool train, hipStream_t st) {
+  HeadFastAux aux{};
+  aux.slab = slab;
+  aux.stride = p.stride;
+  aux.hmax = p.hmax;
+  aux.train = train ? 1 : 0;
+  aux.lps = p.lps;
+  aux.nt = p.nt;
+  aux.grid = p.grid;
+  aux.gated = p.gated;
+  aux.kinds = p.kinds;
+  aux.out_bits = p.out_bits;
+  aux.loss_bits = p.loss_bits;
+#define HEAD(L, NT, GATED, KINDS)                                                            \
+  if (p.lps == L && p.nt == NT && (p.gated != 0) == GATED && (p.kinds != 0) == KINDS)        \
+    MML_ROWS_LAUNCH("mml_head(fast)", 0, (g, aux), head_fast_kernel<L, NT, GATED, KINDS>);
+#define HEAD_FORMS(L, NT) HEAD(L, NT, false, false) HEAD(L, NT, false, true) HEAD(L, NT, true, false) HEAD(L, NT, true, true)
+  HEAD_FORMS(16, 2) HEAD_FORMS(16, 4) HEAD_FORMS(16, 8) HEAD_FORMS(32, 2) HEAD_FORMS(32, 4) HEAD_FORMS(32, 8)
+  HEAD_FORMS(64, 2) HEAD_FORMS(64, 4) HEAD_FORMS(64, 8)
+#undef HEAD_FORMS
+#undef HEAD
+  set_error("head row kernel: no instantiation for <%d, %d> gated %d kinds %d", p.lps, p.nt, p.gated, p.kinds);
+  return MML_ERR_UNSUPPORTED;
 }
 
 }  // namespace mml

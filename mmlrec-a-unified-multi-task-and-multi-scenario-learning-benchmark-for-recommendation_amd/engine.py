@@ -841,7 +841,14 @@ def g16_layer_ok(B, K, N, training):
 
 
 def _fast_row_width_ok(n):
-    return n % 4 == 0 and 0 < n <= 256  # (csrc/rows_fast.hip: gate_fast_config / head_fast_config)
+    return n % 4 == 0 and 0 < n <= 256  # (csrc/rows_route.hpp: head_route; the gate side asks gate_rows_shape)
+
+
+def gate_rows_shape(H, gd_max, n_experts, n_gates, e_bf16):
+    """Which fast gate kernels a group of this shape gets (L.GATE_SHAPE_* bits): the library's own rule under the process's
+    switches (mml_gate_rows_shape, csrc/rows_route.hpp), asked before any buffer exists.  Only the fast kernels write or
+    read bf16 tensors, so whoever chooses a storage format for a gate group's operands asks here."""
+    return int(L.load().mml_gate_rows_shape(H, gd_max, n_experts, n_gates, int(bool(e_bf16))))
 
 
 def _padded_view(buf, kp):
@@ -1325,9 +1332,10 @@ class GateGroupOp(Op):
         self.experts, self.gates, self.H = experts, gates, H
 
     def writes_grad16(self, plan, v):
-        # (the fast row kernels write dE / dG as bf16: mml_gate_group.out_bf16; their shape conditions)
-        return (_fast_row_width_ok(self.H) and all(_fast_row_width_ok(g["G"].n) for g in self.gates) and
-                len(self.experts) * max(len(self.gates), 2) <= 32)
+        # (the fast backward writes dE / dG as bf16: mml_gate_group.out_bf16; whether it serves the group is the library's rule)
+        shape = gate_rows_shape(self.H, max(g["G"].n for g in self.gates), len(self.experts), len(self.gates),
+                                any(e.is16 for e in self.experts))
+        return bool(shape & L.GATE_SHAPE_FAST_BWD)
 
     def inputs(self):
         return list(self.experts) + [g["G"] for g in self.gates]

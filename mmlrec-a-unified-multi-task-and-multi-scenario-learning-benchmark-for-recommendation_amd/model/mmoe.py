@@ -1,11 +1,26 @@
 """MMoE (reference model/mmoe.py:8-119): Ne expert DNNs and T gate DNNs on the shared input, softmax-gated
 expert mix per task, T towers + heads.  Layer l of every expert AND gate DNN is one grouped MFMA launch."""
+import os
+
 import torch.nn as nn
 
 from .. import engine as E
 from .basemodel import BaseModel
 from .towers import build_tower_modules, emit_towers
 from .utils import DNN, emit_dnn_stacks
+
+
+def experts_bf16_by_default(H, G, Ne, T, training):
+    """Whether Ne expert outputs of H columns under T gates with inputs of G columns are stored as bf16 when nobody says
+    otherwise: where the library runs the gate kernels' form with EIGHT row columns per lane (csrc/rows_fast.hip, HV = 2:
+    16-byte loads of bf16 rows, two samples per wave and trip; round 6) -- forward, and backward when the plan trains.
+    Under the default switches: 129..256-wide experts, H % 8 == 0, gate inputs of at most 128 columns, 4 experts x 2 tasks.
+    On the kernels' other form bf16 rows are a net loss (round 5, KuaiRec-32, B = 65 536: the second layers' forward
+    136 -> 121 us, but the gate kernels -- one 16-byte load per lane and expert -- fell to 8-byte loads: backward
+    161 -> 191, forward 90 -> 98), so a library that declines the form (MMLREC_GATE_PACK=0, MMLREC_GATE_HV=0, ...) gets
+    fp32 experts."""
+    want = E.L.GATE_SHAPE_HV_FWD | (E.L.GATE_SHAPE_HV_BWD if training else 0)
+    return E.gate_rows_shape(H, G, Ne, T, True) & want == want
 
 
 class MMOE(BaseModel):
@@ -52,17 +67,13 @@ class MMOE(BaseModel):
         # bf16-storage path: the expert outputs are read by the gate kernels only, which widen bf16 exactly
         # (mml_gate_group.out_bf16 bit 3) -- half the bytes of the largest tensor three kernels move
         H_, G_ = self.expert_dnn_hidden_units[-1], (self.gate_dnn_hidden_units[-1] if hasattr(self, "gate_dnn") else 0)
-        # Round 5 (KuaiRec-32, B = 65 536, same box): the second layers' forward 136 -> 121 us, but the gate kernels -- one
-        # 16-byte load per lane and expert -- fell to 8-byte loads: backward 161 -> 191, forward 90 -> 98; a net loss.
-        # Round 6: the MMoE gate kernels have a form with EIGHT row columns per lane on 32-lane groups (csrc/rows_fast.hip,
-        # HV = 2: 16-byte loads of bf16 rows, two samples per wave and trip) for 129..256-wide experts under gate inputs
-        # of at most 128 columns, 4 experts x 2 tasks: there the experts are bf16 by default (MMLREC_BF16_EXPERTS=0 / 1
-        # forces either way).
-        import os
-        hv_form = 128 < H_ <= 256 and H_ % 8 == 0 and 0 < G_ <= 128 and Ne <= 4 and T <= 2
+        # MMLREC_BF16_EXPERTS=0 / 1 forces either way -- where the fast gate kernels serve the group at all: only they
+        # read bf16 rows.
         env16 = os.environ.get("MMLREC_BF16_EXPERTS")
-        e16 = (plan.bf16 and (env16 == "1" or (env16 is None and hv_form)) and hasattr(self, "gate_dnn") and
-               E._fast_row_width_ok(H_) and E._fast_row_width_ok(G_) and H_ % 8 == 0 and Ne * max(T, 2) <= 32)
+        fast = E.L.GATE_SHAPE_FAST_FWD | (E.L.GATE_SHAPE_FAST_BWD if plan.training else 0)
+        e16 = (plan.bf16 and hasattr(self, "gate_dnn") and H_ % 8 == 0 and
+               (experts_bf16_by_default(H_, G_, Ne, T, plan.training) if env16 is None else
+                env16 == "1" and E.gate_rows_shape(H_, G_, Ne, T, True) & fast == fast))
         stacks = [self.expert_dnn[e].layer_problems(plan, store, f"expert_dnn.{e}", x0, last16=e16) for e in range(Ne)]
         if hasattr(self, "gate_dnn"):
             stacks += [self.gate_dnn[t].layer_problems(plan, store, f"gate_dnn.{t}", x0) for t in range(T)]
@@ -71,10 +82,10 @@ class MMOE(BaseModel):
         gate_in = tops[Ne:] if hasattr(self, "gate_dnn") else [x0] * T
         H = self.expert_dnn_hidden_units[-1]
         # bf16-storage path: a task's mixture is read by its tower's first layer only -- the gate kernel writes it as bf16
-        # when that layer runs on the bf16-storage kernels (mml_gate_group.out_bf16)
+        # when that layer runs on the bf16-storage kernels (mml_gate_group.out_bf16) and the forward is a fast row kernel
         mc = self.model_config
         mix16 = (plan.bf16 and hasattr(self, "tower_dnn") and not mc.get("dnn_use_bn", False) and
-                 E._fast_row_width_ok(H) and all(E._fast_row_width_ok(g.n) for g in gate_in) and
+                 bool(E.gate_rows_shape(H, max(g.n for g in gate_in), Ne, T, e16) & E.L.GATE_SHAPE_FAST_FWD) and
                  E.g16_layer_ok(plan.B, H, self.tower_dnn_hidden_units[0], plan.training))
         gates = [dict(G=gate_in[t], Wg=store.pvals[f"gate_dnn_final_layer.{t}.weight"],
                       mix=plan.val(H, name=f"mmoe_out.{t}", store16=mix16), expert=list(range(Ne))) for t in range(T)]

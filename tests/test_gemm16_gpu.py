@@ -281,6 +281,8 @@ def test_gate_kernels_with_eight_columns_per_lane_against_float64(ops, B, H, Gd)
     in the bf16-storage mode) run on 32-lane groups with EIGHT row columns per lane (csrc/rows_fast.hip, HV = 2: 16-byte
     loads of bf16 rows, two samples per wave and trip), forward and backward -- against float64 on the same (bf16-exact)
     expert values, ragged batches and row widths that end inside a lane's eight columns."""
+    from mmlrec_amd import _lib as L
+    from test_rows_route_cpu import HV_SYMBOLS  # (what the dispatch rule plans for these shapes: held there against the rule)
     g = torch.Generator().manual_seed(8)
     Ne, T = 4, 2
     E16 = [torch.randn(B, H, generator=g).relu().to(torch.bfloat16).to(dev()) for _ in range(Ne)]
@@ -291,11 +293,13 @@ def test_gate_kernels_with_eight_columns_per_lane_against_float64(ops, B, H, Gd)
         gates = [dict(G=Gs[t], Wg=Wg[t], P=torch.empty(B, Ne, device=dev()),
                       mix=torch.empty(B, H, dtype=out_dtype, device=dev()), expert=list(range(Ne))) for t in range(T)]
         ops.gate_mix_fwd(ops.make_gate_group(E16, gates, B, H))
+        assert L.load().mml_rows_last_kernel().decode() == HV_SYMBOLS[0]
         dE = [torch.empty(B, H, dtype=out_dtype, device=dev()) for _ in range(Ne)]
         for t in range(T):
             gates[t].update(dmix=dmix[t], dG=torch.empty(B, Gd, device=dev()), dWg=torch.empty(Ne, Gd, device=dev()),
                             g_relu=1, active=1)
         ops.gate_mix_bwd(ops.make_gate_group(E16, gates, B, H, d_experts=dE, e_relu=True), dev())
+        assert L.load().mml_rows_last_kernel().decode() == HV_SYMBOLS[1]
         torch.cuda.synchronize()
         Ed = torch.stack([e.double() for e in E16], 1)                         # [B, Ne, H]
         dE_ref = torch.zeros_like(Ed)

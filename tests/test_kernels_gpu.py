@@ -323,8 +323,23 @@ def _gate_setup(rng, B, H, nexp, gate_sets, Gd):
     (257, 64, 3, [[2, 0, 1]], 32),
     (129, 128, 4, [[0, 1, 2, 3], [3, 1]], 64),
     (1000, 64, 4, [[0, 1, 2, 3], [0, 1, 2, 3]], 16),
+    # the other (NE, NG) instantiations, every gate over all experts (16-lane groups, B no multiple of their 16 samples
+    # per workgroup); more than 32 coefficients (per-gate forward, generic backward); gates over disjoint halves
+    (70, 32, 4, [list(range(4))] * 3, 16),
+    (70, 32, 4, [list(range(4))] * 4, 16),
+    (70, 32, 4, [list(range(4))] * 8, 16),
+    (70, 32, 8, [list(range(8))] * 2, 16),
+    (70, 32, 8, [list(range(8))] * 4, 16),
+    (70, 32, 16, [list(range(16))] * 2, 16),
+    (70, 32, 16, [list(range(16))] * 3, 16),
+    (70, 32, 8, [list(range(8))] * 8, 16),
+    (70, 32, 8, [[0, 1, 2, 3], [4, 5, 6, 7]], 16),
 ])
 def test_gate_mix_fwd_bwd(ops, B, H, nexp, gate_sets, Gd):
+    # what the dispatch rule plans for this shape (tests/test_rows_route_cpu.py holds the table against the rule itself)
+    from mmlrec_amd import _lib as L
+    from test_rows_route_cpu import GATE_SYMBOLS, gate_symbols_key
+    fwd_symbol, bwd_symbol = GATE_SYMBOLS[gate_symbols_key(B, H, nexp, gate_sets, Gd)]
     rng = np.random.default_rng(7)
     E, gates = _gate_setup(rng, B, H, nexp, gate_sets, Gd)
     Et = [T(e) for e in E]
@@ -333,6 +348,7 @@ def test_gate_mix_fwd_bwd(ops, B, H, nexp, gate_sets, Gd):
         gd.append(dict(G=T(G), Wg=T(Wg), P=torch.empty(B, len(members), device=dev()),
                        mix=torch.empty(B, H, device=dev()), expert=members))
     ops.gate_mix_fwd(ops.make_gate_group(Et, gd, B, H))
+    assert L.load().mml_rows_last_kernel().decode() == fwd_symbol
     refs = []
     for (G, Wg, members), q in zip(gates, gd):
         p, mix = orc.gate_mix_fwd(orc.linear_fwd(G, Wg), np.stack([E[x] for x in members], 1))
@@ -356,6 +372,7 @@ def test_gate_mix_fwd_bwd(ops, B, H, nexp, gate_sets, Gd):
         q["ref_dG"] = (dlog @ Wg) * (G > 0)
         q["ref_dWg"] = dlog.T.astype(np.float64) @ G.astype(np.float64)
     ops.gate_mix_bwd(ops.make_gate_group(Et, gd, B, H, d_experts=dEt), dev())
+    assert L.load().mml_rows_last_kernel().decode() == bwd_symbol
     for x in range(nexp):
         assert rel(dEt[x].cpu().numpy(), dE_ref[x] * (E[x] > 0)) < 2e-5
     for q in gd:
@@ -369,6 +386,7 @@ def test_gate_mix_fwd_bwd(ops, B, H, nexp, gate_sets, Gd):
         q["dWg"].fill_(float("nan"))
     dE2 = [torch.full((B, H), 7.0, device=dev()) for _ in range(nexp)]
     ops.gate_mix_bwd(ops.make_gate_group(Et, gd, B, H, d_experts=dE2), dev(), phases=True)
+    assert L.load().mml_rows_last_kernel().decode() == bwd_symbol
     for q, w_, g_ in zip(act, one_w, one_g):
         # (the generic kernel -- H = 300 here -- sums dWg with LDS float atomics: its order, hence the last bit, varies run to run)
         assert rel(q["dWg"].cpu().numpy(), w_.cpu().numpy()) < 1e-6 and torch.equal(q["dG"], g_)
@@ -401,6 +419,10 @@ def test_head_bce(ops, B, H, T_, masked):
                           ref=(pm, dlogit[:, None] * w[None, :] * (Hin > 0), dlogit @ Hin.astype(np.float64),
                                dlogit.sum())))
     ops.head_bce_fwd_bwd(ops.make_head_group(heads, prob, y=T(y), mask=T(mask) if masked else None, loss=loss), dev())
+    # (the instantiation the dispatch rule plans for this shape: tests/test_rows_route_cpu.py)
+    from mmlrec_amd import _lib as L
+    from test_rows_route_cpu import HEAD_SYMBOLS
+    assert L.load().mml_rows_last_kernel().decode() == HEAD_SYMBOLS[(H, T_, False)]
     assert abs(float(loss.item()) - ref_loss) / ref_loss < 1e-4
     for t, h in enumerate(heads):
         pm, dH, dw, db = h["ref"]
@@ -410,6 +432,7 @@ def test_head_bce(ops, B, H, T_, masked):
         assert abs(float(h["dbias"].item()) - db) < 2e-5 * max(abs(db), 1.0)
     prob2 = torch.empty(B, T_, device=dev())
     ops.head_fwd(ops.make_head_group(heads, prob2, mask=T(mask) if masked else None))
+    assert L.load().mml_rows_last_kernel().decode() == HEAD_SYMBOLS[(H, T_, False)]
     assert torch.equal(prob, prob2)
     # the two-launch form (mml_head_bce_fwd_bwd_phase): the same bits
     keep = [(h["dw"].clone(), h["dbias"].clone(), h["dH"].clone()) for h in heads]
@@ -475,6 +498,8 @@ def test_gated_head_bce(ops, B, H, T_, gate_act):
     slots = ops.amax_slots(2, dev())
     grp.amax_dH, grp.amax_dG = slots[0].data_ptr(), slots[1].data_ptr()
     ops.head_bce_fwd_bwd(grp, dev())
+    from test_rows_route_cpu import HEAD_SYMBOLS  # (the instantiation the dispatch rule plans for this shape)
+    assert L.load().mml_rows_last_kernel().decode() == HEAD_SYMBOLS[(H, T_, True)]
     assert abs(float(loss.item()) - ref_loss) / ref_loss < 1e-4
     for t, h in enumerate(heads):
         p, dH, dG, dw, db = h["ref"]
@@ -491,6 +516,7 @@ def test_gated_head_bce(ops, B, H, T_, gate_act):
         assert v >= am and v <= am * (1 + 1e-6)
     prob2 = torch.empty(B, T_, device=dev())
     ops.head_fwd(ops.make_head_group(heads, prob2))
+    assert L.load().mml_rows_last_kernel().decode() == HEAD_SYMBOLS[(H, T_, True)]
     assert torch.equal(prob, prob2)
     keep = [(h["dw"].clone(), h["dbias"].clone(), h["dH"].clone(), h["dgate"].clone() if "gate" in h else None) for h in heads]
     for h in heads:
