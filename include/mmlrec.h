@@ -868,7 +868,9 @@ int mml_ew_add_n(const float* const* in, int32_t n_in, float* out, int64_t n, mm
 /* n independent items in one launch (16 per kernel-argument block): out[i] (+)= sum_k x_k[i] * (y_k ? y_k[i] : 1).
  * STAR's derived parameters -- W_spec[d] * W_shared and b_spec[d] + b_shared of every head and layer
  * (SharedSpecificLinear, model/utils.py:214-216) -- and their gradients (d W_shared = sum_d dW_eff[d] * W_spec[d], ...)
- * as one call each way instead of one launch per tensor.  `d` is a HOST array. */
+ * as one call each way instead of one launch per tensor.  `d` is a HOST array.  The whole array is validated before the
+ * first launch: a malformed item (its index is in mml_last_error()) returns MML_ERR_ARG and no output of the call is
+ * written. */
 #define MML_SUMPROD_TERMS 8
 #define MML_SUMPROD_BATCH 16
 typedef struct mml_sumprod_desc {

@@ -404,16 +404,21 @@ extern "C" int mml_act_bwd(const float* y, const float* dy, float* dst, int64_t 
 
 extern "C" int mml_sumprod_batch(const mml_sumprod_desc* d, int32_t n, mml_stream_t stream) {
   MML_REQUIRE(n >= 0 && (n == 0 || d), "mml_sumprod_batch: bad descriptor array");
+  // the whole array before the first launch: a malformed item behind the first block of 16 must not be reported after
+  // the blocks in front of it have overwritten their outputs
+  for (int i = 0; i < n; ++i) {
+    const mml_sumprod_desc& D = d[i];
+    MML_REQUIRE(D.out && D.n >= 0 && D.n_terms >= 0 && D.n_terms <= MML_SUMPROD_TERMS, "mml_sumprod_batch: item %d malformed", i);
+    for (int k = 0; k < D.n_terms; ++k) MML_REQUIRE(D.x[k], "mml_sumprod_batch: item %d term %d is null", i, k);
+    MML_REQUIRE(D.act >= MML_ACT_NONE && D.act <= MML_ACT_SIGMOID2 && (D.act == MML_ACT_NONE || (D.deriv_of && !D.accumulate)),
+                "mml_sumprod_batch: item %d: a folded activation derivative needs deriv_of and no accumulation", i);
+  }
   for (int i0 = 0; i0 < n; i0 += MML_SUMPROD_BATCH) {
     SumProdBatch Bt{};
     const int m = (n - i0 < MML_SUMPROD_BATCH) ? n - i0 : MML_SUMPROD_BATCH;
     int64_t nmax = 0;
     for (int i = 0; i < m; ++i) {
       const mml_sumprod_desc& D = d[i0 + i];
-      MML_REQUIRE(D.out && D.n >= 0 && D.n_terms >= 0 && D.n_terms <= MML_SUMPROD_TERMS, "mml_sumprod_batch: item %d malformed", i0 + i);
-      for (int k = 0; k < D.n_terms; ++k) MML_REQUIRE(D.x[k], "mml_sumprod_batch: item %d term %d is null", i0 + i, k);
-      MML_REQUIRE(D.act >= MML_ACT_NONE && D.act <= MML_ACT_SIGMOID2 && (D.act == MML_ACT_NONE || (D.deriv_of && !D.accumulate)),
-                  "mml_sumprod_batch: item %d: a folded activation derivative needs deriv_of and no accumulation", i0 + i);
       Bt.d[i] = D;
       nmax = D.n > nmax ? D.n : nmax;
     }
