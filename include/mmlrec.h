@@ -256,6 +256,33 @@ int mml_scatter_pool_bwd(const mml_pool_desc* d, const float* X, int64_t ldX, in
                          int64_t ldo, const uint8_t* argmax, int64_t ldarg, uint32_t* const* seen,
                          const int64_t* rowbase, int32_t* touched, int32_t* touched_count, int32_t touched_cap,
                          uint8_t* row_marks, int32_t* status, mml_stream_t stream);
+/* Deterministic form of K2p (what mml_scatter_bwd_det is to mml_scatter_bwd): the same launch, the same validity rules,
+ * mean count, argmax routing and status reporting, but bitwise repeatable and independent of the order of the samples.
+ *   addends   what K2p adds: dOut[b, block] (single-valued, sum), dOut / ((float)n_valid + 1e-8f) (mean: ONE fp32
+ *             division, then the conversion) or dOut[e] where argmax[e] == t (max).  |addend| <= max |dOut|: the divisor
+ *             of a valid position is >= 1.
+ *   unit      2^(emax - 150 - shift), emax = the exponent field of the largest word of amax_slot (the magnitude of
+ *             dOut[0:B, 0:(n_single + n_pooled) * E], measured by the call unless supplied) clamped to [1, 254], shift =
+ *             mml_scatter_pool_det_shift(d, B).  Every addend is rounded to the unit ONCE (to nearest); the chunk sums
+ *             in LDS and the row totals use the same unit, so every total is an exact integer sum of the rounded addends.
+ *   headroom  row r of table tb can receive B * L_tb addends, L_tb = the single-valued fields on tb + the sum of maxlen
+ *             over the pooled fields on tb: 24 significand bits + shift + ceil(log2(B * max_tb L_tb)) < 63 with
+ *             shift = min(28, 62 - 24 - ceil(log2(B * max_tb L_tb))).  Where that leaves shift < 4 the rule returns a
+ *             negative value and the entry point MML_ERR_ARG (B * max_tb L_tb > 2^34).  For a schema without pooled
+ *             fields and one field per table the rule is mml_scatter_det_shift(B).
+ *   totals    acc64[t]: int64 [V_t, E] per TABLE (n_tables pointers, all zero between calls); fields that share a table
+ *             add to the same totals, so shared tables are allowed.  row_marks (required): the per-table byte map of
+ *             mml_scatter_pool_bwd.  The second launch turns the totals of the marked rows into fp32, adds them to
+ *             d->table[t] and zeroes them.  Inf / NaN addends are not folded: they reach d->table[t] as float atomics.
+ *   flags     MML_SCATTER_DET_CLEAR_MARKS / _AMAX_SUPPLIED / _DEFER_TOTALS with the meaning and the exclusions of
+ *             mml_scatter_bwd_det (deferred totals: acc_shift = mml_scatter_pool_det_shift(d, B)); any other bit is
+ *             MML_ERR_ARG.
+ * The descriptor checks are those of mml_scatter_pool_bwd; acc64, every acc64[t], amax_slot and row_marks are required. */
+int32_t mml_scatter_pool_det_shift(const mml_pool_desc* d, int64_t B);
+int mml_scatter_pool_bwd_det(const mml_pool_desc* d, const float* X, int64_t ldX, int64_t B, const float* dOut,
+                             int64_t ldo, const uint8_t* argmax, int64_t ldarg, int64_t* const* acc64,
+                             uint32_t* amax_slot, uint8_t* row_marks, int32_t flags, int32_t* status,
+                             mml_stream_t stream);
 /* The distinct VALID rows of a batch without gradients (the counterpart of mml_index_unique, same outputs, per
  * table): what the lazy-exact table optimizer brings up to date before the gather reads it. */
 int mml_index_unique_pool(const mml_pool_desc* d, const float* X, int64_t ldX, int64_t B, uint32_t* const* seen,

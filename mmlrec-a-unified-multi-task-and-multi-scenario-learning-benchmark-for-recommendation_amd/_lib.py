@@ -29,7 +29,7 @@ def head_kind(out=HEAD_OUT_SIGMOID, loss=HEAD_LOSS_BCE):
 
 
 ERR_ARG = -1
-# mml_scatter_bwd_det flags (include/mmlrec.h)
+# mml_scatter_bwd_det / mml_scatter_pool_bwd_det flags (include/mmlrec.h)
 SCATTER_DET_CLEAR_MARKS, SCATTER_DET_AMAX_SUPPLIED, SCATTER_DET_DEFER_TOTALS = 1, 2, 4
 OPT_SGD, OPT_ADAM, OPT_ADAGRAD, OPT_RMSPROP = 0, 1, 2, 3
 OPT_KINDS = {"sgd": OPT_SGD, "adam": OPT_ADAM, "adagrad": OPT_ADAGRAD, "rmsprop": OPT_RMSPROP}
@@ -327,6 +327,8 @@ _SIGS = {
     "mml_gather_pool_fwd": (C.c_int, [_PP(PoolDesc), fp, i64, i32, i32, i64, fp, i64, fp, i64, fp, i64, fp, fp]),
     "mml_scatter_pool_bwd": (C.c_int, [_PP(PoolDesc), fp, i64, i64, fp, i64, fp, i64, _PP(fp), _PP(i64), fp, fp, i32,
                                        fp, fp, fp]),
+    "mml_scatter_pool_det_shift": (i32, [_PP(PoolDesc), i64]),
+    "mml_scatter_pool_bwd_det": (C.c_int, [_PP(PoolDesc), fp, i64, i64, fp, i64, fp, i64, _PP(fp), fp, fp, i32, fp, fp]),
     "mml_index_unique_pool": (C.c_int, [_PP(PoolDesc), fp, i64, i64, _PP(fp), _PP(i64), fp, fp, i32, fp, fp, fp]),
 }
 EXPORTS = tuple(_SIGS)

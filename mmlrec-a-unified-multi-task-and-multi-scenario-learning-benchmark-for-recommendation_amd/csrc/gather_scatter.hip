@@ -9,6 +9,7 @@
 // atomics into dense [V,E] accumulators, shaped as E contiguous floats per row per wave-instruction.
 #include "common.hpp"
 #include "fold_fixed.hpp"
+#include "scatter_det.hpp"
 
 #include <stdlib.h>
 
@@ -797,17 +798,8 @@ static int try_fold(const FieldTable& ft, const ScatterArgs& a, hipStream_t stre
 }
 
 // Deterministic mode, second launch: every marked row's 64-bit totals -> fp32, added to the gradient accumulator (one
-// thread owns a row: no atomics), the totals zeroed again.  One field per workgroup range like rows_compact_kernel.
-struct DetFinalArgs {
-  float* gtab[MML_MAX_FIELDS];
-  long long* acc64[MML_MAX_FIELDS];
-  int64_t vocab[MML_MAX_FIELDS];
-  int64_t markbase[MML_MAX_FIELDS];
-  int32_t blk0[MML_MAX_FIELDS + 1];
-  uint8_t* marks;
-  const uint32_t* amax_dout;
-  int32_t F, E, fix_shift, clear_marks;
-};
+// thread owns a row: no atomics), the totals zeroed again.  One field per workgroup range like rows_compact_kernel
+// (DetFinalArgs: scatter_det.hpp; the pooled scatter passes one entry per TABLE).
 __global__ __launch_bounds__(256) void scatter_det_finalize_kernel(const DetFinalArgs a) {
   int f = 0;
   while (f + 1 < a.F && (int)blockIdx.x >= a.blk0[f + 1]) ++f;
@@ -830,6 +822,20 @@ __global__ __launch_bounds__(256) void scatter_det_finalize_kernel(const DetFina
     }
     if (a.clear_marks) marks[row] = 0;
   }
+}
+
+int launch_det_finalize(DetFinalArgs& fa, hipStream_t stream, const char* who) {
+  int total = 0;
+  for (int f = 0; f < fa.F; ++f) {
+    int64_t nb = cdiv(fa.vocab[f], 256 * 8);
+    if (nb > 1024) nb = 1024;
+    if (nb < 1) nb = 1;
+    fa.blk0[f] = total;
+    total += (int)nb;
+  }
+  fa.blk0[fa.F] = total;
+  MML_LAUNCH(scatter_det_finalize_kernel, dim3((unsigned)total), dim3(256), 0, stream, fa);
+  return check_launch(who);
 }
 
 }  // namespace mml
@@ -1162,17 +1168,7 @@ extern "C" int mml_scatter_bwd_det(float* const* grad_tables, const int64_t* voc
   else rc = launch_fold<512, 16, 1024, true>(ft, a, st, "mml_scatter_bwd_det");
   if (rc) return rc < 0 ? rc : MML_ERR_UNSUPPORTED;
   if (defer) return MML_OK;  // (mml_opt_step_dense converts the marked rows' totals: mml_opt_tensor.acc64)
-  int total = 0;
-  for (int f = 0; f < F; ++f) {
-    fa.markbase[f] = a.markbase[f];
-    int64_t nb = cdiv(vocab[f], 256 * 8);
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    fa.blk0[f] = total;
-    total += (int)nb;
-  }
-  fa.blk0[F] = total;
+  for (int f = 0; f < F; ++f) fa.markbase[f] = a.markbase[f];
   fa.marks = row_marks; fa.amax_dout = amax_slot; fa.F = F; fa.E = E; fa.fix_shift = shift; fa.clear_marks = clear_marks;
-  MML_LAUNCH(scatter_det_finalize_kernel, dim3((unsigned)total), dim3(256), 0, st, fa);
-  return check_launch("mml_scatter_bwd_det");
+  return launch_det_finalize(fa, st, "mml_scatter_bwd_det");
 }

@@ -10,8 +10,14 @@
 // fixed point (fold_fixed.hpp) and flushes E contiguous float atomics per distinct row -- scatter_fold_kernel's
 // scheme with one lookup per lane group.  The bookkeeping is per TABLE, so fields that share a table share its
 // bitmap and its mark range.
+//
+// K2p deterministic (mml_scatter_pool_bwd_det): the same kernel with DET set -- the fixed-point unit comes from the
+// launch-wide magnitude of dOut and the shift of mml_scatter_pool_det_shift, and the flush adds the chunk sums to
+// per-TABLE 64-bit row totals with integer atomics; scatter_det_finalize_kernel (gather_scatter.hip) turns them into
+// the fp32 gradient, one workgroup range per table.
 #include "common.hpp"
 #include "fold_fixed.hpp"
+#include "scatter_det.hpp"
 
 #include <atomic>
 
@@ -293,9 +299,16 @@ struct PoolScatterArgs {
   uint8_t* marks;
   int32_t want_seen;
   int32_t* status;
+  // deterministic mode (mml_scatter_pool_bwd_det): ONE fixed-point unit for the whole launch, from the magnitude slot of
+  // dOut, and 64-bit integer totals per TABLE row (the fields of a shared table add to the same totals)
+  long long* acc64[MML_MAX_FIELDS];
+  const uint32_t* amax_dout;
+  int32_t fix_shift;
 };
 
-template <int SLOTS, int E>
+// DET: see scatter_fold_kernel<..., DET> (gather_scatter.hip).  The magnitude of dOut bounds every addend: a mean
+// field divides by n + 1e-8 >= 1 wherever a position is valid, a max field passes or zeroes the value, a sum field passes it.
+template <int SLOTS, int E, bool DET = false>
 __global__ __launch_bounds__((SLOTS / 2) * (E / 4)) void scatter_pool_fold_kernel(const PoolFields fd,
                                                                                    const PoolScatterArgs a) {
   constexpr int LPS = E / 4;        // lanes per lookup
@@ -370,6 +383,12 @@ __global__ __launch_bounds__((SLOTS / 2) * (E / 4)) void scatter_pool_fold_kerne
       if ((int)(am4 >> 24) != t) g.w = 0.f;
     }
     if (!valid) g = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  if (DET) {  // the launch-wide magnitude of dOut (uniform loads: no LDS round trip)
+    unsigned m = 0;
+    for (int i = 0; i < MML_AMAX_WORDS; ++i) m = a.amax_dout[i] > m ? a.amax_dout[i] : m;
+    mx = m;
+  } else if (a.dOut) {
     // largest magnitude (as bit pattern) of the workgroup's gradient values -> the fixed-point scale
     const unsigned m0 = __float_as_uint(g.x) & 0x7fffffffu, m1 = __float_as_uint(g.y) & 0x7fffffffu;
     const unsigned m2 = __float_as_uint(g.z) & 0x7fffffffu, m3 = __float_as_uint(g.w) & 0x7fffffffu;
@@ -378,10 +397,14 @@ __global__ __launch_bounds__((SLOTS / 2) * (E / 4)) void scatter_pool_fold_kerne
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o));
     if (lane == 0 && mx) atomicMax(&mx_bits, mx);
     __syncthreads();
+    mx = mx_bits;
   }
-  int emax = (int)(mx_bits >> 23);
-  const bool nonfinite = emax >= 255;  // Inf / NaN reach the table as float atomics, not through the fold
+  int emax = (int)(mx >> 23);
+  // Inf / NaN reach the table as float atomics, not through the fold (DET: a NaN does not register in the magnitude
+  // slot, so every addend is looked at)
+  const bool nonfinite = DET || emax >= 255;
   emax = emax < 1 ? 1 : (emax > 254 ? 254 : emax);
+  const int shift = DET ? a.fix_shift : 28;
   // ---- insert
   {
     unsigned slot = 0;
@@ -413,10 +436,10 @@ __global__ __launch_bounds__((SLOTS / 2) * (E / 4)) void scatter_pool_fold_kerne
     }
     if (a.dOut && key >= 0) {
       unsigned long long* ptr = reinterpret_cast<unsigned long long*>(acc) + (part * 4) * PITCH + slot;
-      atomicAdd(ptr, (unsigned long long)to_fixed(g.x, emax));
-      atomicAdd(ptr + PITCH, (unsigned long long)to_fixed(g.y, emax));
-      atomicAdd(ptr + 2 * PITCH, (unsigned long long)to_fixed(g.z, emax));
-      atomicAdd(ptr + 3 * PITCH, (unsigned long long)to_fixed(g.w, emax));
+      atomicAdd(ptr, (unsigned long long)to_fixed(g.x, emax, shift));
+      atomicAdd(ptr + PITCH, (unsigned long long)to_fixed(g.y, emax, shift));
+      atomicAdd(ptr + 2 * PITCH, (unsigned long long)to_fixed(g.z, emax, shift));
+      atomicAdd(ptr + 3 * PITCH, (unsigned long long)to_fixed(g.w, emax, shift));
       if (nonfinite) {
         float* dst = a.gtab[tb] + (int64_t)key * E + part * 4;
         const float gv[4] = {g.x, g.y, g.z, g.w};
@@ -427,7 +450,8 @@ __global__ __launch_bounds__((SLOTS / 2) * (E / 4)) void scatter_pool_fold_kerne
     }
   }
   __syncthreads();
-  // ---- flush: E contiguous float atomics per distinct row; the row is marked for its TABLE
+  // ---- flush: E contiguous float atomics (DET: 64-bit integer atomics on the table's totals) per distinct row; the
+  // row is marked for its TABLE
   float* gt = a.gtab[tb];
   const int n_items = (direct ? (int)V : n_occ) * E;
   for (int item = threadIdx.x; item < n_items; item += blockDim.x) {
@@ -435,7 +459,12 @@ __global__ __launch_bounds__((SLOTS / 2) * (E / 4)) void scatter_pool_fold_kerne
     const int slot = direct ? i : (int)occ[i];
     const int k2 = keys[slot];
     if (k2 < 0) continue;
-    if (a.dOut) atomicAdd(gt + (int64_t)k2 * E + e, from_fixed(acc[e * PITCH + slot], emax));
+    if (DET) {
+      const long long v = acc[e * PITCH + slot];
+      if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.acc64[tb]) + (int64_t)k2 * E + e, (unsigned long long)v);
+    } else if (a.dOut) {
+      atomicAdd(gt + (int64_t)k2 * E + e, from_fixed(acc[e * PITCH + slot], emax));
+    }
     if (e == 0) {
       if (a.marks) a.marks[a.markbase[tb] + k2] = 1;  // plain store: hot rows cost nothing (see mark_rows_kernel)
       else if (a.want_seen) atomicOr(a.seen[tb] + (k2 >> 5), 1u << (k2 & 31));
@@ -475,7 +504,7 @@ __global__ __launch_bounds__(256) void mark_pool_rows_kernel(const PoolFields fd
   if (bad && a.status) atomicOr(a.status, bad);
 }
 
-template <int SLOTS, int E>
+template <int SLOTS, int E, bool DET = false>
 static int launch_pool_fold(const PoolFields& fd, const PoolScatterArgs& a, int nblocks, hipStream_t stream,
                             const char* who) {
   constexpr int NT = (SLOTS / 2) * (E / 4);
@@ -485,7 +514,7 @@ static int launch_pool_fold(const PoolFields& fd, const PoolScatterArgs& a, int 
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_pool_fold_kernel<SLOTS, E>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_pool_fold_kernel<SLOTS, E, DET>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
     if (e != hipSuccess) {
       set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
@@ -493,7 +522,7 @@ static int launch_pool_fold(const PoolFields& fd, const PoolScatterArgs& a, int 
     }
     if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_relaxed);
   }
-  MML_LAUNCH((scatter_pool_fold_kernel<SLOTS, E>), dim3((unsigned)nblocks), dim3(NT), lds, stream, fd, a);
+  MML_LAUNCH((scatter_pool_fold_kernel<SLOTS, E, DET>), dim3((unsigned)nblocks), dim3(NT), lds, stream, fd, a);
   return check_launch(who);
 }
 
@@ -639,6 +668,17 @@ static int fill_pool_fields(const mml_pool_desc* d, int64_t B, int chunk, PoolFi
   return MML_OK;
 }
 
+// per TABLE: gradient rows, size and the first byte of its range in the mark map (row_marks of mml_scatter_pool_bwd)
+static void fill_pool_tables(const mml_pool_desc* d, PoolScatterArgs& a) {
+  int64_t words = 0;
+  for (int t = 0; t < d->n_tables; ++t) {
+    a.gtab[t] = d->table[t];
+    a.vocab[t] = (int32_t)d->vocab[t];
+    a.markbase[t] = words * 32;
+    words += (d->vocab[t] + 31) / 32;
+  }
+}
+
 static int pool_rows_impl(const mml_pool_desc* d, const float* X, int64_t ldX, int64_t B, const float* dOut,
                           int64_t ldo, const uint8_t* argmax, int64_t ldarg, uint32_t* const* seen,
                           const int64_t* rowbase, int32_t* touched, int32_t* touched_count, int32_t touched_cap,
@@ -663,14 +703,8 @@ static int pool_rows_impl(const mml_pool_desc* d, const float* X, int64_t ldX, i
   MML_REQUIRE(ldX >= max_col(d) + 1 || B == 1, "%s: ldX=%lld < %lld columns the fields read", who, (long long)ldX,
               (long long)(max_col(d) + 1));
   PoolScatterArgs a{};
-  int64_t words = 0;
-  for (int t = 0; t < d->n_tables; ++t) {
-    a.gtab[t] = d->table[t];
-    a.seen[t] = touched ? seen[t] : nullptr;
-    a.vocab[t] = (int32_t)d->vocab[t];
-    a.markbase[t] = words * 32;
-    words += (d->vocab[t] + 31) / 32;
-  }
+  fill_pool_tables(d, a);
+  for (int t = 0; t < d->n_tables; ++t) a.seen[t] = touched ? seen[t] : nullptr;
   a.X = X; a.dOut = dOut; a.argmax = argmax; a.ldX = ldX; a.B = B; a.ldo = ldo; a.ldarg = ldarg;
   a.marks = row_marks; a.want_seen = touched ? 1 : 0; a.status = status;
   PoolFields fd{};
@@ -710,6 +744,89 @@ extern "C" int mml_scatter_pool_bwd(const mml_pool_desc* d, const float* X, int6
   }
   return pool_rows_impl(d, X, ldX, B, dOut, ldo, argmax, ldarg, seen, rowbase, touched, touched_count, touched_cap,
                         row_marks, status, stream, who);
+}
+
+// headroom of the deterministic totals: a row of table tb may receive B * L_tb addends at the launch-wide maximum,
+// L_tb = its single-valued fields + the maxlen of its pooled fields: 24 significand bits + shift + ceil(log2(B * Lmax)) < 63
+extern "C" int32_t mml_scatter_pool_det_shift(const mml_pool_desc* d, int64_t B) {
+  if (check_desc(d, false, "mml_scatter_pool_det_shift") || B < 0) return -1;
+  int64_t per_table[MML_MAX_FIELDS] = {0};
+  for (int f = 0; f < d->n_single; ++f) per_table[d->s_table[f]] += 1;
+  for (int p = 0; p < d->n_pooled; ++p) per_table[d->p_table[p]] += d->p_maxlen[p];
+  int64_t lmax = 1;
+  for (int t = 0; t < d->n_tables; ++t) lmax = per_table[t] > lmax ? per_table[t] : lmax;
+  if (B > ((int64_t)1 << 40)) return -1;  // (lmax < 2^13: the product below stays far inside 64 bits)
+  const int64_t n = (B < 1 ? 1 : B) * lmax;
+  int lg = 0;
+  while (((int64_t)1 << lg) < n) ++lg;
+  const int shift = 62 - 24 - lg;
+  if (shift < 4) return -1;
+  return shift > 28 ? 28 : shift;
+}
+
+extern "C" int mml_scatter_pool_bwd_det(const mml_pool_desc* d, const float* X, int64_t ldX, int64_t B,
+                                        const float* dOut, int64_t ldo, const uint8_t* argmax, int64_t ldarg,
+                                        int64_t* const* acc64, uint32_t* amax_slot, uint8_t* row_marks, int32_t flags,
+                                        int32_t* status, mml_stream_t stream) {
+  const char* who = "mml_scatter_pool_bwd_det";
+  int rc = check_desc(d, true, who);
+  if (rc) return rc;
+  MML_REQUIRE(B >= 0, "%s: B=%lld", who, (long long)B);
+  MML_REQUIRE(acc64 && amax_slot && row_marks, "%s: acc64, amax_slot and row_marks are required", who);
+  for (int t = 0; t < d->n_tables; ++t) MML_REQUIRE(acc64[t], "%s: acc64[%d] is null", who, t);
+  const int all_flags = MML_SCATTER_DET_CLEAR_MARKS | MML_SCATTER_DET_AMAX_SUPPLIED | MML_SCATTER_DET_DEFER_TOTALS;
+  MML_REQUIRE((flags & ~all_flags) == 0, "%s: unknown flag bits 0x%x", who, flags & ~all_flags);
+  const bool defer = (flags & MML_SCATTER_DET_DEFER_TOTALS) != 0;
+  const int clear_marks = flags & MML_SCATTER_DET_CLEAR_MARKS;
+  MML_REQUIRE(!(defer && clear_marks), "%s: deferred totals are found through the marks: "
+              "MML_SCATTER_DET_DEFER_TOTALS excludes MML_SCATTER_DET_CLEAR_MARKS", who);
+  const int shift = mml_scatter_pool_det_shift(d, B);
+  MML_REQUIRE(shift >= 0, "%s: B=%lld samples times the lookups of one table leave no headroom in the 64-bit totals", who,
+              (long long)B);
+  if (B == 0) return MML_OK;
+  const int64_t ncols = (int64_t)(d->n_single + d->n_pooled) * d->E;
+  MML_REQUIRE(X != nullptr, "%s: null X", who);
+  MML_REQUIRE(ldX >= max_col(d) + 1 || B == 1, "%s: ldX=%lld < %lld columns the fields read", who, (long long)ldX,
+              (long long)(max_col(d) + 1));
+  MML_REQUIRE(dOut && aligned16(dOut) && ldo % 4 == 0 && ldo >= ncols,
+              "%s: dOut must be 16-byte aligned with ldo %% 4 == 0 and ldo >= (n_single + n_pooled) * E", who);
+  if (has_max(d))
+    MML_REQUIRE(argmax && ldarg >= (int64_t)d->n_pooled * d->E && ldarg % 4 == 0 &&
+                    (reinterpret_cast<uintptr_t>(argmax) & 3u) == 0,
+                "%s: a max field needs the argmax bytes of mml_gather_pool_fwd", who);
+  hipStream_t st = to_stream(stream);
+  if (!(flags & MML_SCATTER_DET_AMAX_SUPPLIED)) {
+    // the launch-wide magnitude of dOut (a maximum does not depend on the order either)
+    rc = mml_amax_reset(amax_slot, 1, stream);
+    if (rc) return rc;
+    mml_amax_desc ad{};
+    ad.x = dOut; ad.rows = B; ad.ld = ldo; ad.cols = (int32_t)ncols; ad.slot = amax_slot;
+    rc = mml_amax_batch(&ad, 1, stream);
+    if (rc) return rc;
+  }
+  PoolScatterArgs a{};
+  DetFinalArgs fa{};
+  fill_pool_tables(d, a);
+  for (int t = 0; t < d->n_tables; ++t) {
+    a.acc64[t] = reinterpret_cast<long long*>(acc64[t]);
+    fa.gtab[t] = a.gtab[t];
+    fa.acc64[t] = a.acc64[t];
+    fa.vocab[t] = d->vocab[t];
+    fa.markbase[t] = a.markbase[t];
+  }
+  a.X = X; a.dOut = dOut; a.argmax = argmax; a.ldX = ldX; a.B = B; a.ldo = ldo; a.ldarg = ldarg;
+  a.marks = row_marks; a.status = status; a.amax_dout = amax_slot; a.fix_shift = shift;
+  PoolFields fd{};
+  const int slots = d->E == 16 ? 512 : 1024;
+  rc = fill_pool_fields(d, B, slots / 2, fd, who);
+  if (rc) return rc;
+  if (d->E == 8) rc = launch_pool_fold<1024, 8, true>(fd, a, fd.blk0[fd.nf], st, who);
+  else if (d->E == 4) rc = launch_pool_fold<1024, 4, true>(fd, a, fd.blk0[fd.nf], st, who);
+  else rc = launch_pool_fold<512, 16, true>(fd, a, fd.blk0[fd.nf], st, who);
+  if (rc || defer) return rc;  // (deferred: mml_opt_step_dense converts the marked rows' totals, mml_opt_tensor.acc64)
+  fa.marks = row_marks; fa.amax_dout = amax_slot; fa.F = d->n_tables; fa.E = d->E; fa.fix_shift = shift;
+  fa.clear_marks = clear_marks;
+  return launch_det_finalize(fa, st, who);
 }
 
 extern "C" int mml_index_unique_pool(const mml_pool_desc* d, const float* X, int64_t ldX, int64_t B,

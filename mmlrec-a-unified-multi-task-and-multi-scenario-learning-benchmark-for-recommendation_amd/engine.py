@@ -685,6 +685,34 @@ class GatherOp(Op):
         return [(lib.mml_gather_fwd, (tabs, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), self.dense_col0,
                                       self.nd, plan.B, out.data_ptr(), ops._ld(out), plan.status.data_ptr()), meta)]
 
+    def _det_setup(self, plan, emb_cols, shift):
+        """The buffers and flags of the deterministic scatter call (mml_scatter_bwd_det / mml_scatter_pool_bwd_det):
+        (acc64 pointer array, mark map, magnitude slot, flags); sets self.det_deferred.  emb_cols: the columns of
+        d(dnn_input) the scatter reads, shift: the totals' shift for this batch."""
+        det, sr = self.deterministic, self.sparse_rows
+        acc = ops._ptr_array(det["acc64"])
+        marks = self.grad_marks if self.grad_marks is not None else (sr.marks if sr is not None else det["marks"])
+        keep_marks = self.grad_marks is not None or sr is not None
+        slot = det["slot"]
+        plan.keep += [acc]
+        flags = 0 if keep_marks else L.SCATTER_DET_CLEAR_MARKS
+        fused = plan.knobs.det_fused  # (MMLREC_DET_FUSED=0: the call measures and finalizes for itself)
+        g = self.out
+        # the magnitude of d(dnn_input) from the launch that wrote it: the one writer raised g.gamax (a slot of the
+        # pool the step's opening mml_amax_reset zeroes) with the exact maximum over the [B, emb_cols] region read here
+        if (fused and self.nd == 0 and getattr(g, "gamax_exact", False) and g.written == 1 and
+                plan.raised_grad_slot(g) is not None and g.n == emb_cols):
+            slot = g.gamax
+            flags |= L.SCATTER_DET_AMAX_SUPPLIED
+        # the totals stay in acc64 for the ONE marked streaming launch of the dense table optimizer
+        self.det_deferred = None
+        # (never in a PCGrad per-task plan: its banks take the fp32 rows of every pass; never in the multi-GPU subclasses)
+        if (fused and type(self) in (GatherOp, PooledGatherOp) and sr is None and not getattr(plan, "pcgrad_T", 0) and
+                L.opt_takes_det_totals([t.data.numel() for t in self.tables], self.grad_marks is not None)):
+            flags |= L.SCATTER_DET_DEFER_TOTALS
+            self.det_deferred = dict(slot=slot, shift=shift)
+        return acc, marks, slot, flags
+
     def bwd_calls(self, plan):
         if self.out.grad is None or not any(t.needs_grad for t in self.tables):
             return []
@@ -712,27 +740,7 @@ class GatherOp(Op):
             # deterministic scatter: 64-bit integer row totals, then fp32 (two launches + the magnitude of d(dnn_input),
             # or the fold alone: MML_SCATTER_DET_AMAX_SUPPLIED / _DEFER_TOTALS below);
             # the marks feed the marked dense update (left set) or the touched-row list (compaction, which clears them)
-            acc = ops._ptr_array(det["acc64"])
-            marks = self.grad_marks if self.grad_marks is not None else (sr.marks if sr is not None else det["marks"])
-            keep_marks = self.grad_marks is not None or sr is not None
-            slot = det["slot"]
-            plan.keep += [acc]
-            flags = 0 if keep_marks else L.SCATTER_DET_CLEAR_MARKS
-            fused = plan.knobs.det_fused  # (MMLREC_DET_FUSED=0: the call measures and finalizes for itself)
-            g = self.out
-            # the magnitude of d(dnn_input) from the launch that wrote it: the one writer raised g.gamax (a slot of the
-            # pool the step's opening mml_amax_reset zeroes) with the exact maximum over the [B, F * E] region read here
-            if (fused and self.nd == 0 and getattr(g, "gamax_exact", False) and g.written == 1 and
-                    plan.raised_grad_slot(g) is not None and g.n == F * E):
-                slot = g.gamax
-                flags |= L.SCATTER_DET_AMAX_SUPPLIED
-            # the totals stay in acc64 for the ONE marked streaming launch of the dense table optimizer
-            self.det_deferred = None
-            # (never in a PCGrad per-task plan: its banks take the fp32 rows of every pass)
-            if (fused and type(self) is GatherOp and sr is None and not getattr(plan, "pcgrad_T", 0) and
-                    L.opt_takes_det_totals([t.data.numel() for t in self.tables], self.grad_marks is not None)):
-                flags |= L.SCATTER_DET_DEFER_TOTALS
-                self.det_deferred = dict(slot=slot, shift=int(lib.mml_scatter_det_shift(plan.B)))
+            acc, marks, slot, flags = self._det_setup(plan, F * E, int(lib.mml_scatter_det_shift(plan.B)))
             calls = [(lib.mml_scatter_bwd_det, (gt, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), plan.B,
                                                 self.out.grad.data_ptr(), ops._ld(self.out.grad), acc, slot.data_ptr(),
                                                 marks.data_ptr(), flags, plan.status.data_ptr()),
@@ -811,6 +819,28 @@ class PooledGatherOp(GatherOp):
         meta = dict(kernel="scatter_pool_fold_kernel", tail=True,  # ids + dOut block read + row read-modify-write
                     bytes=float(plan.B) * (len(self.singles) * (4 + 12 * E) +
                                            sum(4 * pf[1] + 4 * E + 8 * E * pf[1] for pf in self.pooled)))
+        det = self.deterministic
+        if det is not None:
+            # deterministic scatter (GatherOp.bwd_calls): totals, marks and the finalize launch are per TABLE
+            shift = int(lib.mml_scatter_pool_det_shift(C.byref(d), plan.B))
+            if shift < 0:
+                raise L.MMLError(f"deterministic pooled scatter: a batch of {plan.B} samples times the lookups of one "
+                                 "table leaves no headroom in the 64-bit totals")
+            acc, marks, slot, flags = self._det_setup(plan, (len(self.singles) + len(self.pooled)) * E, shift)
+            calls = [(lib.mml_scatter_pool_bwd_det, (C.byref(d), self.X.data_ptr(), ops._ld(self.X), plan.B,
+                                                     self.out.grad.data_ptr(), ops._ld(self.out.grad),
+                                                     L.ptr(self.argmax), 0 if self.argmax is None else ops._ld(self.argmax),
+                                                     acc, slot.data_ptr(), marks.data_ptr(), flags,
+                                                     plan.status.data_ptr()),
+                      dict(meta, kernel="scatter_pool_fold_kernel<det>", det_flags=flags,
+                           ptrs=[a.data_ptr() for a in det["acc64"]]))]
+            if sr is not None:
+                vocab = (L.i64 * T)(*[t.data.shape[0] for t in self.tables])
+                plan.keep.append(vocab)
+                calls.append((lib.mml_rows_compact, (seen, vocab, rb, T, sr.touched.data_ptr(), sr.count.data_ptr(),
+                                                     sr.touched.numel(), sr.marks.data_ptr()),
+                              dict(kernel="rows_compact_kernel", bytes=float(sr.marks.numel()), tail=True)))
+            return calls
         return [(lib.mml_scatter_pool_bwd, (C.byref(d), self.X.data_ptr(), ops._ld(self.X), plan.B,
                                             self.out.grad.data_ptr(), ops._ld(self.out.grad), L.ptr(self.argmax),
                                             0 if self.argmax is None else ops._ld(self.argmax)) + extra +

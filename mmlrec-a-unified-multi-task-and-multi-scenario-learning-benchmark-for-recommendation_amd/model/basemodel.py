@@ -326,8 +326,12 @@ class BaseModel(nn.Module):
         if vl:
             if par_ is not None:
                 raise NotImplementedError("multi-valued (pooled) features on sharded / replicated tables")
-            if self._scatter_mode() == "deterministic" and training:
-                raise NotImplementedError("scatter_mode='deterministic' with multi-valued (pooled) features")
+            # The deterministic pooled scatter (mml_scatter_pool_bwd_det) is asked for by name: scatter_mode alone keeps
+            # the refusal it has had since pooled features came, which callers and the suite rely on.
+            if self._scatter_mode() == "deterministic" and training and not self._pooled_deterministic():
+                raise NotImplementedError("scatter_mode='deterministic' with multi-valued (pooled) features: set "
+                                          "model.pooled_deterministic = True (or model_config['pooled_deterministic']) "
+                                          "to sum their table gradients with the deterministic pooled scatter")
             if mark_rows is not None:
                 raise NotImplementedError("the row-marking gather of the split dense update has no pooled form")
         # (pooled fields: dnn_input stays fp32 -- the pooled gather has no bf16-storage form)
@@ -346,6 +350,8 @@ class BaseModel(nn.Module):
                                    sparse_rows=sparse_rows)
             if grad_marks and training and sparse_rows is None:
                 gop.grad_marks = store.ensure_grad_marks(ptabs)[0]
+            # (the op names every table once: fields may share a table, their totals are per table)
+            self._maybe_deterministic(gop, store, ptabs, training, E_dim)
             plan.add(gop)
             plan.layer_outputs["dnn_input"] = x0
             return self._finish_record(plan, store, x0)
@@ -416,8 +422,9 @@ class BaseModel(nn.Module):
 
     def _maybe_deterministic(self, gop, store, tables, training, E_dim):
         """model.scatter_mode = "deterministic" (or model_config["scatter_mode"]): the table gradients of the step are
-        summed in order-independent integer fixed point (mml_scatter_bwd_det) -- bitwise repeatable runs, and replicated
-        tables that stay bitwise equal on every rank without re-broadcasts.  Default "atomic" (float atomics: faster)."""
+        summed in order-independent integer fixed point (mml_scatter_bwd_det; mml_scatter_pool_bwd_det with multi-valued
+        features) -- bitwise repeatable runs, and replicated tables that stay bitwise equal on every rank without
+        re-broadcasts.  Default "atomic" (float atomics: faster)."""
         mode = self._scatter_mode()
         if mode == "deterministic" and training:
             if E_dim not in (4, 8, 16) or len({id(t) for t in tables}) != len(tables):
@@ -429,6 +436,15 @@ class BaseModel(nn.Module):
         if mode not in ("atomic", "deterministic"):
             raise ValueError("scatter_mode must be 'atomic' or 'deterministic'")
         return mode
+
+    def _pooled_deterministic(self):
+        """model.pooled_deterministic (or model_config["pooled_deterministic"]): with scatter_mode = "deterministic", a
+        model with multi-valued (pooled) features sums their table gradients with mml_scatter_pool_bwd_det too.  Default
+        off: scatter_mode alone refuses such a model, as it always has."""
+        own = getattr(self, "pooled_deterministic", None)
+        if own is None:
+            own = (self.config or {}).get("model_config", {}).get("pooled_deterministic", False)
+        return bool(own)
 
     def _reject_deterministic(self, where):
         if self._scatter_mode() == "deterministic":

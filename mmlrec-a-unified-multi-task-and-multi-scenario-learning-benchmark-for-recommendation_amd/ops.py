@@ -280,6 +280,37 @@ def scatter_pool_bwd(grad_tables, X, singles, pooled, d_out, argmax=None, seen=N
     L.check(rc, "mml_scatter_pool_bwd")
 
 
+def scatter_pool_bwd_det(grad_tables, X, singles, pooled, d_out, acc64, marks, argmax=None, amax_slot=None,
+                         clear_marks=True, status=None, amax_supplied=False, defer_totals=False, flags=None):
+    """Deterministic form of scatter_pool_bwd (mml_scatter_pool_bwd_det): acc64 = one int64 [V, E] accumulator per TABLE
+    (all zero between calls), marks = the byte map of marks_bytes(table sizes).  Bitwise repeatable, independent of the
+    order of the samples; tables shared by several fields are allowed.  amax_supplied / defer_totals as in
+    scatter_bwd_det, with scatter_pool_det_shift(...) as the totals' shift.  `flags` (an int) replaces the three switches."""
+    lib = L.load()
+    _need_gpu(X, d_out)
+    d = make_pool_desc(grad_tables, singles, pooled)
+    if amax_slot is None:
+        amax_slot = amax_slots(1, X.device)[0]
+    if flags is None:
+        flags = ((L.SCATTER_DET_CLEAR_MARKS if clear_marks else 0) | (L.SCATTER_DET_AMAX_SUPPLIED if amax_supplied else 0) |
+                 (L.SCATTER_DET_DEFER_TOTALS if defer_totals else 0))
+    rc = lib.mml_scatter_pool_bwd_det(C.byref(d), X.data_ptr(), _ld(X), X.shape[0], d_out.data_ptr(), _ld(d_out),
+                                      L.ptr(argmax), 0 if argmax is None else _ld(argmax),
+                                      _ptr_array(acc64) if acc64 is not None else None, amax_slot.data_ptr(),
+                                      L.ptr(marks), int(flags), L.ptr(status), _stream())
+    L.check(rc, "mml_scatter_pool_bwd_det")
+
+
+def scatter_pool_det_shift(desc, B):
+    """log2 of the fixed-point scale the deterministic pooled scatter uses for B samples (mml_scatter_pool_det_shift):
+    `desc` = a PoolDesc (make_pool_desc) or (table sizes, E, singles, pooled).  Negative: B times the lookups of one
+    table leave no headroom in the 64-bit totals (the scatter refuses such a batch)."""
+    if not isinstance(desc, L.PoolDesc):
+        vocab, E, singles, pooled = desc
+        desc = make_pool_desc(None, singles, pooled, vocab=(list(vocab), E))
+    return int(L.load().mml_scatter_pool_det_shift(C.byref(desc), int(B)))
+
+
 def index_unique_pool(vocab, E, X, singles, pooled, seen, rowbase, touched, touched_count, status=None, marks=None):
     """The distinct VALID rows of a batch per table, without gradients (mml_index_unique_pool)."""
     _need_gpu(X, touched, touched_count)
