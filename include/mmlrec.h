@@ -1292,7 +1292,10 @@ int mml_opt_step_rows(float* const* tables, float* const* grad_tables, float* co
  *                         half an ulp of p (from then on only the moments decay, in closed form);
  *   mml_opt_catchup_dense does the same for EVERY row of one table (before evaluation / checkpointing).
  * Together with mml_opt_step_rows(..., last, ...) this reproduces the dense trajectory while touching only the rows
- * of the current batch. */
+ * of the current batch.
+ * Any E in [1, 64]: a row's elements are adjacent lanes of one wave (a group of the next power of two at or above E,
+ * the surplus lanes idle), all of which read last[row] before the row's first lane publishes the new step.  E > 64 is
+ * refused with MML_ERR_ARG by both entry points (a row would not fit one wave).  A row listed twice is undefined. */
 int mml_opt_catchup_rows(float* const* tables, float* const* state1, float* const* state2, int32_t* const* last,
                          const int64_t* rowbase, int32_t F, int32_t E, const int32_t* touched,
                          const int32_t* touched_count, int32_t touched_cap, const mml_opt_hyper* hyper,

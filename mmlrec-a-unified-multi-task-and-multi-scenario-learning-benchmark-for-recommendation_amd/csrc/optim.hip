@@ -937,6 +937,13 @@ struct CatchupLaunch {
   mml_opt_hyper h;
 };
 
+// log2 of the lanes a row of E elements gets in opt_catchup_kernel: the next power of two at or above E (1 <= E <= 64)
+__host__ __device__ __forceinline__ int catchup_group_shift(int E) {
+  int s = 0;
+  while ((1 << s) < E) ++s;
+  return s;
+}
+
 __global__ __launch_bounds__(256) void opt_catchup_kernel(const CatchupLaunch L) {
   __shared__ int64_t rb_lds[MML_MAX_FIELDS + 1];
   if (!L.dense) {
@@ -952,11 +959,16 @@ __global__ __launch_bounds__(256) void opt_catchup_kernel(const CatchupLaunch L)
     int32_t cnt = *L.touched_count;
     nrows = cnt > L.cap ? L.cap : cnt;
   }
-  const int64_t total = nrows * L.E;
+  // A row is a group of 2^gsh adjacent lanes, the next power of two at or above E (E <= 64: launch_catchup), lanes
+  // e >= E idle: the group lies inside ONE wave and ONE trip of the loop (2^gsh divides the wave, the workgroup and the
+  // grid's stride).  For E a power of two the items are row * E + e as they always were.
+  const int gsh = catchup_group_shift(L.E);
+  const int64_t total = nrows << gsh;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; item < total; item += stride) {
-    const int64_t li = item / L.E;
-    const int e = (int)(item - li * L.E);
+    const int64_t li = item >> gsh;
+    const int e = (int)(item & ((1 << gsh) - 1));
+    if (e >= L.E) continue;
     int f = 0;
     int64_t row = li;
     if (!L.dense) {
@@ -973,7 +985,11 @@ __global__ __launch_bounds__(256) void opt_catchup_kernel(const CatchupLaunch L)
     L.tab[f][o] = p;
     if (L.s1[f]) L.s1[f][o] = m;
     if (L.s2[f]) L.s2[f][o] = v;
-    // every lane of the row has read `from` above (same wave, in order), so lane 0 may now publish the new step
+    // The row's lanes are one lane group of this wave in this trip (above), so all of them have read `from` in the one
+    // wave-instruction above, which the wave issues before this store: lane 0 may now publish the new step.  No lane of
+    // another wave, workgroup or trip reads this row's word.  (Items dealt as row * E + e put the elements of a row
+    // into two waves or two trips whenever E does not divide 64: the late ones found from == target and skipped
+    // their replay.)
     __builtin_amdgcn_wave_barrier();
     if (e == 0) L.last[f][row] = target;
   }
@@ -1172,8 +1188,11 @@ extern "C" int mml_opt_step_dense(const mml_opt_tensor* tensors, int32_t n, cons
   return MML_OK;
 }
 
-static int launch_catchup(CatchupLaunch& L, int64_t max_items, hipStream_t st, const char* who) {
-  int64_t blocks = cdiv(max_items, 256);
+// max_rows rows at most, each a lane group of the next power of two at or above E (opt_catchup_kernel); E a power of
+// two: the grid of max_rows * E items.  E > 64 is refused: a row has to fit one wave.
+static int launch_catchup(CatchupLaunch& L, int64_t max_rows, hipStream_t st, const char* who) {
+  MML_REQUIRE(L.E <= 64, "%s: E = %d: a row's elements are the lanes of one wave, E <= 64", who, L.E);
+  int64_t blocks = cdiv(max_rows << catchup_group_shift(L.E), 256);
   if (blocks > 256 * 8) blocks = 256 * 8;
   if (blocks < 1) blocks = 1;
   MML_LAUNCH(opt_catchup_kernel, dim3((unsigned)blocks), dim3(256), 0, st, L);
@@ -1198,7 +1217,7 @@ extern "C" int mml_opt_catchup_rows(float* const* tables, float* const* state1, 
   }
   L.rowbase[F] = rowbase[F];
   L.F = F; L.E = E; L.touched = touched; L.touched_count = touched_count; L.cap = touched_cap; L.h = *hyper;
-  return launch_catchup(L, (int64_t)touched_cap * E, to_stream(stream), "mml_opt_catchup_rows");
+  return launch_catchup(L, (int64_t)touched_cap, to_stream(stream), "mml_opt_catchup_rows");
 }
 
 extern "C" int mml_opt_catchup_dense(float* table, float* state1, float* state2, int32_t* last, int64_t V, int32_t E,
@@ -1211,7 +1230,7 @@ extern "C" int mml_opt_catchup_dense(float* table, float* state1, float* state2,
   CatchupLaunch L{};
   L.tab[0] = table; L.s1[0] = state1; L.s2[0] = state2; L.last[0] = last;
   L.F = 1; L.E = E; L.dense = 1; L.V = V; L.h = *hyper;
-  return launch_catchup(L, V * E, to_stream(stream), "mml_opt_catchup_dense");
+  return launch_catchup(L, V, to_stream(stream), "mml_opt_catchup_dense");
 }
 
 extern "C" int mml_opt_step_rows(float* const* tables, float* const* grad_tables, float* const* state1,
