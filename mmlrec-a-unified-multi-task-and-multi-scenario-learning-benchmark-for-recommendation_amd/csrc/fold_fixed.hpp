@@ -1,6 +1,7 @@
-// 64-bit fixed point of the LDS row fold (scatter_fold_kernel, scatter_pool_fold_kernel): every gradient value of a
-// workgroup is scaled by 2^(150 + shift - emax), emax = the largest exponent the workgroup holds, and summed with
-// integer LDS atomics -- the chunk sum does not depend on the order of the addends (see gather_scatter.hip, K2).
+// 64-bit fixed point of the LDS row fold (scatter_fold.hpp: the insert and the flush that scatter_fold_kernel and
+// scatter_pool_fold_kernel share): every gradient value of a workgroup is scaled by 2^(150 + shift - emax), emax = the
+// largest exponent the workgroup holds, and summed with integer LDS atomics -- the chunk sum does not depend on the
+// order of the addends.
 #pragma once
 #include "common.hpp"
 

@@ -8,12 +8,10 @@
 // K2 restates aten::embedding_dense_backward (sparse=False, model/basemodel.py:122): row-granular float
 // atomics into dense [V,E] accumulators, shaped as E contiguous floats per row per wave-instruction.
 #include "common.hpp"
-#include "fold_fixed.hpp"
 #include "scatter_det.hpp"
+#include "scatter_fold.hpp"
 
 #include <stdlib.h>
-
-#include <atomic>
 
 namespace mml {
 
@@ -421,10 +419,8 @@ __global__ __launch_bounds__(256) void scatter_hash_kernel(const FieldTable ft, 
 // ------------------------------------------------------------------------------------------------
 // K2, restructured (round 2).  Same idea as scatter_hash_kernel -- fold the duplicate rows of a sample chunk in LDS,
 // then E contiguous float atomics per distinct row -- rebuilt around what the MI355X measurements said
-// (tools/lab/micro/lds_atomic.hip, per wave-instruction and CU):  ds_add_f32 = 195 cycles whatever the address
-// pattern, ds_add_u64 = 15, ds_add_u32 = 9, ds_cmpst_rtn_b32 = 15; a same-address integer atomic costs ~4 cycles per
-// lane.  The fp32 LDS atomics were 94 us of the old kernel's 168 us, the single-address "occupied slots" counter
-// most of another 54 us.  So:
+// (the LDS atomic rates: scatter_fold.hpp).  The fp32 LDS atomics were 94 us of the old kernel's 168 us, the
+// single-address "occupied slots" counter most of another 54 us.  So:
 //   * the duplicates of a chunk are summed in 64-bit FIXED POINT with integer LDS atomics: every gradient value is
 //     scaled by 2^(178 - emax), emax = the largest exponent the workgroup holds for this field, so the largest values
 //     keep their 24 mantissa bits 28 bits above the unit and 11 bits of headroom are left for 2048 addends.  Values
@@ -436,8 +432,7 @@ __global__ __launch_bounds__(256) void scatter_hash_kernel(const FieldTable ft, 
 //     of all SLOTS x E cells;
 //   * tables with V <= SLOTS rows are direct-mapped (slot = row: no compare-and-swap, no probing) and one workgroup
 //     folds kDirectReps chunks before it flushes.
-// LDS accumulators are plane-major, acc[e][slot] with a (SLOTS + 1) pitch: the lanes of an insert differ in slot
-// (random banks) and the lanes of a flush in e (consecutive banks).
+// The LDS layout, the insert and the flush are scatter_fold.hpp's, shared with scatter_pool_fold_kernel.
 // ------------------------------------------------------------------------------------------------
 struct ScatterPlan {
   int32_t reps[MML_MAX_FIELDS];          // chunks folded per workgroup (direct-mapped fields: kDirectReps, others 1)
@@ -533,84 +528,23 @@ __global__ __launch_bounds__(NT) void scatter_fold_kernel(const FieldTable ft, c
     __syncthreads();
   }
   int emax = (int)(mx_bits >> 23);
-  // A diverged backward (Inf / NaN in dOut) must reach the table like it does in the reference (index_add of a NaN is
-  // NaN), not be turned into a finite fixed-point value: such elements skip the fold and go to HBM as float atomics.
+  // Inf / NaN reach the table as float atomics, not through the fold (fold_insert).
+  // NOT scatter_pool_fold_kernel's `DET || emax >= 255`: under DET a NaN never raises the magnitude slot and is dropped here.
   const bool nonfinite = emax >= 255;  // workgroup-uniform
   emax = emax < 1 ? 1 : (emax > 254 ? 254 : emax);
   const int shift = DET ? a.fix_shift : 28;
-  // ---- insert
+  float* gt = a.gtab[f];
 #pragma unroll
   for (int r = 0; r < kDirectReps; ++r) {
     if (r >= reps) break;
 #pragma unroll
-    for (int k = 0; k < PASSES; ++k) {
-      const int key = rows[r][k];
-      unsigned slot = 0;
-      bool is_new = false;
-      if (direct) {
-        if (key >= 0) {
-          slot = (unsigned)key;
-          if (part == 0 && keys[slot] != key) keys[slot] = key;  // racing writers store the same value
-        }
-      } else {
-        if (key >= 0 && part == 0) {  // one lane per sample claims the slot ...
-          slot = (((unsigned)key * 2654435761u) >> 16) & (SLOTS - 1);
-          while (true) {
-            const int old = atomicCAS(&keys[slot], -1, key);
-            if (old == -1) { is_new = true; break; }
-            if (old == key) break;
-            slot = (slot + 1) & (SLOTS - 1);
-          }
-        }
-        // new slots of this wave join the occupied list with ONE counter atomic
-        const unsigned long long nm = __ballot(is_new);
-        if (nm) {
-          const int leader = __ffsll((long long)nm) - 1;
-          int base = 0;
-          if (lane == leader) base = atomicAdd(&n_occ, __popcll(nm));
-          base = __shfl(base, leader);
-          if (is_new) occ[base + __popcll(nm & ((1ull << lane) - 1ull))] = (unsigned short)slot;
-        }
-        if (LPS > 1) slot = (unsigned)__shfl((int)slot, lane & ~(LPS - 1));  // ... its lanes follow
-      }
-      if (a.dOut && key >= 0) {
-        unsigned long long* p = reinterpret_cast<unsigned long long*>(acc) + (part * 4) * PITCH + slot;
-        atomicAdd(p, (unsigned long long)to_fixed(g[r][k].x, emax, shift));
-        atomicAdd(p + PITCH, (unsigned long long)to_fixed(g[r][k].y, emax, shift));
-        atomicAdd(p + 2 * PITCH, (unsigned long long)to_fixed(g[r][k].z, emax, shift));
-        atomicAdd(p + 3 * PITCH, (unsigned long long)to_fixed(g[r][k].w, emax, shift));
-        if (nonfinite) {
-          float* dst = a.gtab[f] + (int64_t)key * E + part * 4;
-          const float gv[4] = {g[r][k].x, g[r][k].y, g[r][k].z, g[r][k].w};
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            if ((__float_as_uint(gv[i]) & 0x7f800000u) == 0x7f800000u) atomicAdd(dst + i, gv[i]);
-        }
-      }
-    }
+    for (int k = 0; k < PASSES; ++k)
+      fold_insert<SLOTS, E>(acc, keys, occ, &n_occ, direct, rows[r][k], part, lane, a.dOut != nullptr, g[r][k], emax,
+                            shift, nonfinite, gt);
   }
   __syncthreads();
-  float* gt = a.gtab[f];
-  const int n_items = (direct ? (int)V : n_occ) * E;
-  for (int item = threadIdx.x; item < n_items; item += NT) {
-    const int i = item / E, e = item - i * E;
-    const int slot = direct ? i : (int)occ[i];
-    const int key = keys[slot];
-    if (key < 0) continue;  // (direct-mapped: a row no sample of these chunks touched)
-    if (DET) {
-      const long long v = acc[e * PITCH + slot];
-      if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.acc64[f]) + (int64_t)key * E + e, (unsigned long long)v);
-    } else if (a.dOut) {
-      atomicAdd(gt + (int64_t)key * E + e, from_fixed(acc[e * PITCH + slot], emax));
-    }
-    // touched-row bookkeeping: only MARK the row here (a non-returning atomic: they run at the float-atomic request
-    // rate, while the returning form that told "first time seen" cost the index-only pass 0.5 ms); the list is built
-    // from the bitmaps by rows_compact_kernel
-    if (e == 0) {
-      if (a.marks) a.marks[a.markbase[f] + key] = 1;  // plain store: hot rows cost nothing (see mark_rows_kernel)
-      else if (a.touched) atomicOr(a.seen[f] + (key >> 5), 1u << (key & 31));
-    }
-  }
+  fold_flush<SLOTS, E, DET>(acc, keys, occ, n_occ, direct, (int)V, NT, a.dOut != nullptr, gt, DET ? a.acc64[f] : nullptr,
+                            emax, a.marks ? a.marks + a.markbase[f] : nullptr, a.touched ? a.seen[f] : nullptr);
   if (bad && a.status) atomicOr(a.status, bad);
 }
 
@@ -722,22 +656,17 @@ __global__ __launch_bounds__(1024) void rows_compact_kernel(const CompactArgs a)
 static int launch_compact(const FieldTable& ft, const ScatterArgs& a, hipStream_t stream, const char* who,
                           bool count_zeroed = false) {
   CompactArgs c{};
-  int64_t words = 0;
+  c.wordbase[a.F] = mark_bases(ft.vocab, a.F, c.wordbase);
   for (int f = 0; f < a.F; ++f) {
     c.seen[f] = a.seen[f];
-    c.wordbase[f] = words;  // (= a.markbase[f] / 32)
+    c.wordbase[f] /= 32;  // a bitmap word per 32 mark bytes
     c.rowbase[f] = a.rowbase[f];
-    words += (ft.vocab[f] + 31) / 32;
   }
-  c.wordbase[a.F] = words;
   c.marks = a.marks;
   c.F = a.F; c.touched = a.touched; c.count = a.touched_count; c.cap = a.touched_cap;
   if (!count_zeroed) {
-    hipError_t e = hipMemsetAsync(a.touched_count, 0, sizeof(int32_t), stream);
-    if (e != hipSuccess) {
-      set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
-      return MML_ERR_HIP;
-    }
+    const int rc = clear_touched(a.touched_count, stream, who);
+    if (rc) return rc;
   }
   int total = 0;
   for (int f = 0; f < a.F; ++f) {
@@ -767,21 +696,10 @@ static int launch_fold(const FieldTable& ft, const ScatterArgs& a, hipStream_t s
   sp.grp_base[a.F] = (int32_t)total;
   if (total * 8 > 0x7fffffff) return 1;  // caller falls back
   const size_t lds = (size_t)E * (SLOTS + 1) * 8 + (size_t)SLOTS * 4 + (size_t)SLOTS * 2;
-  // more than the 64 KiB a kernel may use by default; the attribute is per DEVICE (a process may drive several)
-  static std::atomic<uint64_t> attr_set{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_fold_kernel<SLOTS, E, NT, DET>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    if (e != hipSuccess) {
-      set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-      return MML_ERR_HIP;
-    }
-    if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_relaxed);
-  }
+  int rc = allow_big_lds<&scatter_fold_kernel<SLOTS, E, NT, DET>>(who);
+  if (rc) return rc;
   MML_LAUNCH((scatter_fold_kernel<SLOTS, E, NT, DET>), dim3((unsigned)(total * 8)), dim3(NT), lds, stream, ft, a, sp);
-  int rc = check_launch(who);
+  rc = check_launch(who);
   if (rc || !a.touched) return rc;
   return launch_compact(ft, a, stream, who, true);
 }
@@ -909,11 +827,7 @@ extern "C" int mml_gather_fwd_mark(const float* const* tables, const int64_t* vo
   GatherArgs a{};
   a.X = X; a.ldX = ldX; a.F = F; a.E = E; a.dense_col0 = dense_col0; a.Nd = Nd; a.B = B;
   a.out = out; a.ldo = ldo; a.status = status; a.marks = row_marks;
-  int64_t words = 0;
-  for (int f = 0; f < F; ++f) {
-    a.markbase[f] = words * 32;
-    words += (vocab[f] + 31) / 32;
-  }
+  mark_bases(vocab, F, a.markbase);
   return launch_gather(ft, a, to_stream(stream));
 }
 
@@ -933,14 +847,9 @@ extern "C" int mml_gather_fwd_idx32(const float* const* tables, const int64_t* v
   return launch_gather(ft, a, to_stream(stream));
 }
 
-// mark map layout: field f owns bytes [32 * wordbase_f, 32 * wordbase_f + V_f), wordbase = prefix sum of ceil(V_f / 32)
 static void set_marks(ScatterArgs& a, const FieldTable& ft, uint8_t* row_marks) {
   a.marks = row_marks;
-  int64_t words = 0;
-  for (int f = 0; f < a.F; ++f) {
-    a.markbase[f] = words * 32;
-    words += (ft.vocab[f] + 31) / 32;
-  }
+  mark_bases(ft.vocab, a.F, a.markbase);
 }
 
 static int scatter_impl(float* const* grad_tables, const int64_t* vocab, const int32_t* col, int32_t F,
@@ -955,16 +864,8 @@ static int scatter_impl(float* const* grad_tables, const int64_t* vocab, const i
   MML_REQUIRE(B == 0 || ((X || idx) && dOut), "mml_scatter_bwd: null X/dOut");
   MML_REQUIRE(!touched || (seen && rowbase && touched_count && touched_cap > 0),
               "mml_scatter_bwd: touched list needs seen/rowbase/touched_count/cap");
-  if (B == 0 || F == 0) {  // an empty batch touches no row: the list of the previous call must not survive
-    if (touched) {
-      hipError_t e = hipMemsetAsync(touched_count, 0, sizeof(int32_t), to_stream(stream));
-      if (e != hipSuccess) {
-        set_error("mml_scatter_bwd: hipMemsetAsync: %s", hipGetErrorString(e));
-        return MML_ERR_HIP;
-      }
-    }
-    return MML_OK;
-  }
+  if (B == 0 || F == 0)  // an empty batch touches no row: the list of the previous call must not survive
+    return touched ? clear_touched(touched_count, to_stream(stream), "mml_scatter_bwd") : MML_OK;
   ScatterArgs a{};
   for (int f = 0; f < F; ++f) {
     a.gtab[f] = grad_tables[f];
@@ -986,11 +887,8 @@ static int scatter_impl(float* const* grad_tables, const int64_t* vocab, const i
               "16-byte aligned dOut with ldo %% 4 == 0 (the LDS-fold kernel)");
   if (!touched) set_marks(a, ft, nullptr);
   if (touched) {  // the fold path resets the list itself; these kernels only append
-    hipError_t e = hipMemsetAsync(touched_count, 0, sizeof(int32_t), to_stream(stream));
-    if (e != hipSuccess) {
-      set_error("mml_scatter_bwd: hipMemsetAsync: %s", hipGetErrorString(e));
-      return MML_ERR_HIP;
-    }
+    rc = clear_touched(touched_count, to_stream(stream), "mml_scatter_bwd");
+    if (rc) return rc;
   }
   if (E <= 16) {
     // dynamic LDS stays under the 64 KiB default limit: SLOTS * (1 + E) * 4 bytes = 36 KiB (4 workgroups per CU)
@@ -1130,21 +1028,14 @@ extern "C" int mml_scatter_bwd_det(float* const* grad_tables, const int64_t* voc
   MML_REQUIRE(B == 0 || (X && dOut), "mml_scatter_bwd_det: null X/dOut");
   MML_REQUIRE(acc64 && amax_slot && row_marks, "mml_scatter_bwd_det: acc64, amax_slot and row_marks are required");
   MML_REQUIRE(ldo % 4 == 0 && aligned16(dOut), "mml_scatter_bwd_det: dOut must be 16-byte aligned with ldo %% 4 == 0");
-  const int all_flags = MML_SCATTER_DET_CLEAR_MARKS | MML_SCATTER_DET_AMAX_SUPPLIED | MML_SCATTER_DET_DEFER_TOTALS;
-  MML_REQUIRE((flags & ~all_flags) == 0, "mml_scatter_bwd_det: unknown flag bits 0x%x", flags & ~all_flags);
-  const bool defer = (flags & MML_SCATTER_DET_DEFER_TOTALS) != 0;
-  const int clear_marks = flags & MML_SCATTER_DET_CLEAR_MARKS;
-  MML_REQUIRE(!(defer && clear_marks), "mml_scatter_bwd_det: deferred totals are found through the marks: "
-              "MML_SCATTER_DET_DEFER_TOTALS excludes MML_SCATTER_DET_CLEAR_MARKS");
+  bool defer;
+  int clear_marks;
+  rc = det_flags(flags, "mml_scatter_bwd_det", &defer, &clear_marks);
+  if (rc) return rc;
   if (B == 0 || F == 0) return MML_OK;
   hipStream_t st = to_stream(stream);
   if (!(flags & MML_SCATTER_DET_AMAX_SUPPLIED)) {
-    // the launch-wide magnitude of dOut (a maximum does not depend on the order either)
-    rc = mml_amax_reset(amax_slot, 1, stream);
-    if (rc) return rc;
-    mml_amax_desc ad{};
-    ad.x = dOut; ad.rows = B; ad.ld = ldo; ad.cols = F * E; ad.slot = amax_slot;
-    rc = mml_amax_batch(&ad, 1, stream);
+    rc = measure_dout(dOut, B, ldo, (int64_t)F * E, amax_slot, stream);
     if (rc) return rc;
   }
   ScatterArgs a{};

@@ -7,19 +7,17 @@
 //
 // K2p is their backward: one workgroup takes ONE field and a chunk of at most CHUNK lookups (a single-valued field:
 // CHUNK samples; a pooled field: CHUNK / maxlen samples x maxlen positions), folds duplicate rows in LDS in 64-bit
-// fixed point (fold_fixed.hpp) and flushes E contiguous float atomics per distinct row -- scatter_fold_kernel's
-// scheme with one lookup per lane group.  The bookkeeping is per TABLE, so fields that share a table share its
-// bitmap and its mark range.
+// fixed point and flushes E contiguous float atomics per distinct row -- the fold of scatter_fold.hpp, shared with
+// scatter_fold_kernel, with one lookup per lane group.  The bookkeeping is per TABLE, so fields that share a table
+// share its bitmap and its mark range.
 //
 // K2p deterministic (mml_scatter_pool_bwd_det): the same kernel with DET set -- the fixed-point unit comes from the
 // launch-wide magnitude of dOut and the shift of mml_scatter_pool_det_shift, and the flush adds the chunk sums to
 // per-TABLE 64-bit row totals with integer atomics; scatter_det_finalize_kernel (gather_scatter.hip) turns them into
 // the fp32 gradient, one workgroup range per table.
 #include "common.hpp"
-#include "fold_fixed.hpp"
 #include "scatter_det.hpp"
-
-#include <atomic>
+#include "scatter_fold.hpp"
 
 namespace mml {
 
@@ -400,76 +398,18 @@ __global__ __launch_bounds__((SLOTS / 2) * (E / 4)) void scatter_pool_fold_kerne
     mx = mx_bits;
   }
   int emax = (int)(mx >> 23);
-  // Inf / NaN reach the table as float atomics, not through the fold (DET: a NaN does not register in the magnitude
-  // slot, so every addend is looked at)
+  // Inf / NaN reach the table as float atomics, not through the fold (fold_insert).
+  // NOT scatter_fold_kernel's `emax >= 255`: under DET a NaN never raises the magnitude slot, so every addend is looked at.
   const bool nonfinite = DET || emax >= 255;
   emax = emax < 1 ? 1 : (emax > 254 ? 254 : emax);
   const int shift = DET ? a.fix_shift : 28;
-  // ---- insert
-  {
-    unsigned slot = 0;
-    bool is_new = false;
-    if (direct) {
-      if (key >= 0) {
-        slot = (unsigned)key;
-        if (part == 0 && keys[slot] != key) keys[slot] = key;  // racing writers store the same value
-      }
-    } else {
-      if (key >= 0 && part == 0) {  // one lane per lookup claims the slot ...
-        slot = (((unsigned)key * 2654435761u) >> 16) & (SLOTS - 1);
-        while (true) {
-          const int old = atomicCAS(&keys[slot], -1, key);
-          if (old == -1) { is_new = true; break; }
-          if (old == key) break;
-          slot = (slot + 1) & (SLOTS - 1);
-        }
-      }
-      const unsigned long long nm = __ballot(is_new);
-      if (nm) {  // new slots of this wave join the occupied list with ONE counter atomic
-        const int leader = __ffsll((long long)nm) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(&n_occ, __popcll(nm));
-        base = __shfl(base, leader);
-        if (is_new) occ[base + __popcll(nm & ((1ull << lane) - 1ull))] = (unsigned short)slot;
-      }
-      if (LPS > 1) slot = (unsigned)__shfl((int)slot, lane & ~(LPS - 1));  // ... its lanes follow
-    }
-    if (a.dOut && key >= 0) {
-      unsigned long long* ptr = reinterpret_cast<unsigned long long*>(acc) + (part * 4) * PITCH + slot;
-      atomicAdd(ptr, (unsigned long long)to_fixed(g.x, emax, shift));
-      atomicAdd(ptr + PITCH, (unsigned long long)to_fixed(g.y, emax, shift));
-      atomicAdd(ptr + 2 * PITCH, (unsigned long long)to_fixed(g.z, emax, shift));
-      atomicAdd(ptr + 3 * PITCH, (unsigned long long)to_fixed(g.w, emax, shift));
-      if (nonfinite) {
-        float* dst = a.gtab[tb] + (int64_t)key * E + part * 4;
-        const float gv[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if ((__float_as_uint(gv[i]) & 0x7f800000u) == 0x7f800000u) atomicAdd(dst + i, gv[i]);
-      }
-    }
-  }
-  __syncthreads();
-  // ---- flush: E contiguous float atomics (DET: 64-bit integer atomics on the table's totals) per distinct row; the
-  // row is marked for its TABLE
   float* gt = a.gtab[tb];
-  const int n_items = (direct ? (int)V : n_occ) * E;
-  for (int item = threadIdx.x; item < n_items; item += blockDim.x) {
-    const int i = item / E, e = item - i * E;
-    const int slot = direct ? i : (int)occ[i];
-    const int k2 = keys[slot];
-    if (k2 < 0) continue;
-    if (DET) {
-      const long long v = acc[e * PITCH + slot];
-      if (v) atomicAdd(reinterpret_cast<unsigned long long*>(a.acc64[tb]) + (int64_t)k2 * E + e, (unsigned long long)v);
-    } else if (a.dOut) {
-      atomicAdd(gt + (int64_t)k2 * E + e, from_fixed(acc[e * PITCH + slot], emax));
-    }
-    if (e == 0) {
-      if (a.marks) a.marks[a.markbase[tb] + k2] = 1;  // plain store: hot rows cost nothing (see mark_rows_kernel)
-      else if (a.want_seen) atomicOr(a.seen[tb] + (k2 >> 5), 1u << (k2 & 31));
-    }
-  }
+  fold_insert<SLOTS, E>(acc, keys, occ, &n_occ, direct, key, part, lane, a.dOut != nullptr, g, emax, shift, nonfinite, gt);
+  __syncthreads();
+  // the row is marked for its TABLE
+  fold_flush<SLOTS, E, DET>(acc, keys, occ, n_occ, direct, (int)V, (int)blockDim.x, a.dOut != nullptr, gt,
+                            DET ? a.acc64[tb] : nullptr, emax, a.marks ? a.marks + a.markbase[tb] : nullptr,
+                            a.want_seen ? a.seen[tb] : nullptr);
   if (bad && a.status) atomicOr(a.status, bad);
 }
 
@@ -509,19 +449,8 @@ static int launch_pool_fold(const PoolFields& fd, const PoolScatterArgs& a, int 
                             const char* who) {
   constexpr int NT = (SLOTS / 2) * (E / 4);
   const size_t lds = (size_t)E * (SLOTS + 1) * 8 + (size_t)SLOTS * 4 + (size_t)(SLOTS / 2) * 4 + (size_t)SLOTS * 2;
-  // more than the 64 KiB a kernel may use by default; the attribute is per DEVICE (a process may drive several)
-  static std::atomic<uint64_t> attr_set{0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !((attr_set.load(std::memory_order_relaxed) >> dev) & 1ull)) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&scatter_pool_fold_kernel<SLOTS, E, DET>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-    if (e != hipSuccess) {
-      set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
-      return MML_ERR_HIP;
-    }
-    if (dev >= 0 && dev < 64) attr_set.fetch_or(1ull << dev, std::memory_order_relaxed);
-  }
+  const int rc = allow_big_lds<&scatter_pool_fold_kernel<SLOTS, E, DET>>(who);
+  if (rc) return rc;
   MML_LAUNCH((scatter_pool_fold_kernel<SLOTS, E, DET>), dim3((unsigned)nblocks), dim3(NT), lds, stream, fd, a);
   return check_launch(who);
 }
@@ -670,12 +599,10 @@ static int fill_pool_fields(const mml_pool_desc* d, int64_t B, int chunk, PoolFi
 
 // per TABLE: gradient rows, size and the first byte of its range in the mark map (row_marks of mml_scatter_pool_bwd)
 static void fill_pool_tables(const mml_pool_desc* d, PoolScatterArgs& a) {
-  int64_t words = 0;
+  mark_bases(d->vocab, d->n_tables, a.markbase);
   for (int t = 0; t < d->n_tables; ++t) {
     a.gtab[t] = d->table[t];
     a.vocab[t] = (int32_t)d->vocab[t];
-    a.markbase[t] = words * 32;
-    words += (d->vocab[t] + 31) / 32;
   }
 }
 
@@ -689,16 +616,8 @@ static int pool_rows_impl(const mml_pool_desc* d, const float* X, int64_t ldX, i
   if (touched)
     for (int t = 0; t < d->n_tables; ++t) MML_REQUIRE(seen[t] != nullptr, "%s: seen[%d] is null", who, t);
   hipStream_t st = to_stream(stream);
-  if (B == 0) {  // an empty batch touches no row: the list of the previous call must not survive
-    if (touched) {
-      hipError_t e = hipMemsetAsync(touched_count, 0, sizeof(int32_t), st);
-      if (e != hipSuccess) {
-        set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
-        return MML_ERR_HIP;
-      }
-    }
-    return MML_OK;
-  }
+  if (B == 0)  // an empty batch touches no row: the list of the previous call must not survive
+    return touched ? clear_touched(touched_count, st, who) : MML_OK;
   MML_REQUIRE(X != nullptr, "%s: null X", who);
   MML_REQUIRE(ldX >= max_col(d) + 1 || B == 1, "%s: ldX=%lld < %lld columns the fields read", who, (long long)ldX,
               (long long)(max_col(d) + 1));
@@ -774,12 +693,10 @@ extern "C" int mml_scatter_pool_bwd_det(const mml_pool_desc* d, const float* X, 
   MML_REQUIRE(B >= 0, "%s: B=%lld", who, (long long)B);
   MML_REQUIRE(acc64 && amax_slot && row_marks, "%s: acc64, amax_slot and row_marks are required", who);
   for (int t = 0; t < d->n_tables; ++t) MML_REQUIRE(acc64[t], "%s: acc64[%d] is null", who, t);
-  const int all_flags = MML_SCATTER_DET_CLEAR_MARKS | MML_SCATTER_DET_AMAX_SUPPLIED | MML_SCATTER_DET_DEFER_TOTALS;
-  MML_REQUIRE((flags & ~all_flags) == 0, "%s: unknown flag bits 0x%x", who, flags & ~all_flags);
-  const bool defer = (flags & MML_SCATTER_DET_DEFER_TOTALS) != 0;
-  const int clear_marks = flags & MML_SCATTER_DET_CLEAR_MARKS;
-  MML_REQUIRE(!(defer && clear_marks), "%s: deferred totals are found through the marks: "
-              "MML_SCATTER_DET_DEFER_TOTALS excludes MML_SCATTER_DET_CLEAR_MARKS", who);
+  bool defer;
+  int clear_marks;
+  rc = det_flags(flags, who, &defer, &clear_marks);
+  if (rc) return rc;
   const int shift = mml_scatter_pool_det_shift(d, B);
   MML_REQUIRE(shift >= 0, "%s: B=%lld samples times the lookups of one table leave no headroom in the 64-bit totals", who,
               (long long)B);
@@ -796,12 +713,7 @@ extern "C" int mml_scatter_pool_bwd_det(const mml_pool_desc* d, const float* X, 
                 "%s: a max field needs the argmax bytes of mml_gather_pool_fwd", who);
   hipStream_t st = to_stream(stream);
   if (!(flags & MML_SCATTER_DET_AMAX_SUPPLIED)) {
-    // the launch-wide magnitude of dOut (a maximum does not depend on the order either)
-    rc = mml_amax_reset(amax_slot, 1, stream);
-    if (rc) return rc;
-    mml_amax_desc ad{};
-    ad.x = dOut; ad.rows = B; ad.ld = ldo; ad.cols = (int32_t)ncols; ad.slot = amax_slot;
-    rc = mml_amax_batch(&ad, 1, stream);
+    rc = measure_dout(dOut, B, ldo, ncols, amax_slot, stream);
     if (rc) return rc;
   }
   PoolScatterArgs a{};

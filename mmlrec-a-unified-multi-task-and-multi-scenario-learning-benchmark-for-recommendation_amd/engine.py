@@ -713,6 +713,23 @@ class GatherOp(Op):
             self.det_deferred = dict(slot=slot, shift=shift)
         return acc, marks, slot, flags
 
+    def _rows_args(self, plan):
+        """The touched-row arguments of the scatter call (seen, rowbase, touched, count, cap, row_marks): the
+        bookkeeping of self.sparse_rows (one entry per table), or the marks alone."""
+        sr = self.sparse_rows
+        if sr is None:
+            return (None, None, None, None, 0, L.ptr(self.grad_marks))
+        seen = ops._ptr_array(sr.seen)
+        rb = (L.i64 * (len(self.tables) + 1))(*sr.rowbase)
+        plan.keep += [seen, rb]
+        return (seen, rb, sr.touched.data_ptr(), sr.count.data_ptr(), sr.touched.numel(), sr.marks.data_ptr())
+
+    def _compact_call(self, extra, vocab):
+        """The compaction behind a deterministic scatter: the marks it left -> the touched list of self.sparse_rows
+        (extra: _rows_args' tuple, vocab: rows per table)."""
+        return (L.load().mml_rows_compact, (extra[0], vocab, extra[1], len(self.tables)) + extra[2:],
+                dict(kernel="rows_compact_kernel", bytes=float(self.sparse_rows.marks.numel()), tail=True))
+
     def bwd_calls(self, plan):
         if self.out.grad is None or not any(t.needs_grad for t in self.tables):
             return []
@@ -725,14 +742,7 @@ class GatherOp(Op):
         plan.keep += [gt, vocab, col]
         for t in self.tables:
             _claim(t)
-        sr = self.sparse_rows
-        if sr is not None:
-            seen = ops._ptr_array(sr.seen)
-            rb = (L.i64 * (F + 1))(*sr.rowbase)
-            plan.keep += [seen, rb]
-            extra = (seen, rb, sr.touched.data_ptr(), sr.count.data_ptr(), sr.touched.numel(), sr.marks.data_ptr())
-        else:
-            extra = (None, None, None, None, 0, L.ptr(self.grad_marks))
+        extra = self._rows_args(plan)
         meta = dict(kernel=scatter_symbol(E),
                     bytes=float(plan.B) * F * (4 + 12 * E), tail=True)  # idx + grad read + row RMW
         det = self.deterministic
@@ -746,10 +756,8 @@ class GatherOp(Op):
                                                 marks.data_ptr(), flags, plan.status.data_ptr()),
                       dict(meta, kernel="scatter_fold_kernel<det>", det_flags=flags,
                            ptrs=[a.data_ptr() for a in det["acc64"]]))]
-            if sr is not None:
-                calls.append((lib.mml_rows_compact, (seen, vocab, rb, F, sr.touched.data_ptr(), sr.count.data_ptr(),
-                                                     sr.touched.numel(), sr.marks.data_ptr()),
-                              dict(kernel="rows_compact_kernel", bytes=float(sr.marks.numel()), tail=True)))
+            if self.sparse_rows is not None:
+                calls.append(self._compact_call(extra, vocab))
             return calls
         return [(lib.mml_scatter_bwd, (gt, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), plan.B,
                                        self.out.grad.data_ptr(), ops._ld(self.out.grad)) + extra +
@@ -808,14 +816,7 @@ class PooledGatherOp(GatherOp):
         d = self._desc(plan, "grad")
         for t in self.tables:
             _claim(t)
-        sr = self.sparse_rows
-        if sr is not None:
-            seen = ops._ptr_array(sr.seen)
-            rb = (L.i64 * (T + 1))(*sr.rowbase)
-            plan.keep += [seen, rb]
-            extra = (seen, rb, sr.touched.data_ptr(), sr.count.data_ptr(), sr.touched.numel(), sr.marks.data_ptr())
-        else:
-            extra = (None, None, None, None, 0, L.ptr(self.grad_marks))
+        extra = self._rows_args(plan)
         meta = dict(kernel="scatter_pool_fold_kernel", tail=True,  # ids + dOut block read + row read-modify-write
                     bytes=float(plan.B) * (len(self.singles) * (4 + 12 * E) +
                                            sum(4 * pf[1] + 4 * E + 8 * E * pf[1] for pf in self.pooled)))
@@ -834,12 +835,10 @@ class PooledGatherOp(GatherOp):
                                                      plan.status.data_ptr()),
                       dict(meta, kernel="scatter_pool_fold_kernel<det>", det_flags=flags,
                            ptrs=[a.data_ptr() for a in det["acc64"]]))]
-            if sr is not None:
+            if self.sparse_rows is not None:
                 vocab = (L.i64 * T)(*[t.data.shape[0] for t in self.tables])
                 plan.keep.append(vocab)
-                calls.append((lib.mml_rows_compact, (seen, vocab, rb, T, sr.touched.data_ptr(), sr.count.data_ptr(),
-                                                     sr.touched.numel(), sr.marks.data_ptr()),
-                              dict(kernel="rows_compact_kernel", bytes=float(sr.marks.numel()), tail=True)))
+                calls.append(self._compact_call(extra, vocab))
             return calls
         return [(lib.mml_scatter_pool_bwd, (C.byref(d), self.X.data_ptr(), ops._ld(self.X), plan.B,
                                             self.out.grad.data_ptr(), ops._ld(self.out.grad), L.ptr(self.argmax),

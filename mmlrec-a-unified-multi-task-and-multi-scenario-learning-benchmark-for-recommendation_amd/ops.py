@@ -323,7 +323,8 @@ def index_unique_pool(vocab, E, X, singles, pooled, seen, rowbase, touched, touc
 
 
 def marks_bytes(vocab):
-    """Size of the row-mark scratch map of mml_scatter_bwd / mml_index_unique (include/mmlrec.h: row_marks)."""
+    """Size of the row-mark scratch map of mml_scatter_bwd / mml_index_unique (include/mmlrec.h: row_marks); the layout
+    is defined once in C: mark_bases (csrc/scatter_fold.hpp)."""
     return 32 * sum((int(v) + 31) // 32 for v in vocab)
 
 

@@ -14,7 +14,8 @@ names are bitwise 0; (4) the totals are zero after a call that finalizes, the ma
 set exactly on the valid rows per table; (5) a magnitude slot filled beforehand gives the same bits; (6) deferred
 totals leave the fp32 gradient alone and from_fixed of them, on the host, is the gradient of (1) bit for bit.
 Then: a NaN addend reaches its fp32 row and disturbs nothing else, an out-of-range id at a valid position sets the
-status word and adds nothing, and the refusals launch nothing."""
+status word and adds nothing, and the refusals launch nothing.  And a schema of single-valued fields alone leaves the
+same totals and marks as mml_scatter_bwd_det, bit for bit: the two kernels share one fold (csrc/scatter_fold.hpp)."""
 import itertools
 
 import numpy as np
@@ -144,6 +145,57 @@ def test_deterministic_pooled_scatter(E, T, B):
     check_marks(case, m6, want_rows)
     host = [np.ldexp(a.astype(np.float64), emax - 150 - shift).astype(np.float32) for a in acc6]
     assert same_bits(g1, host)
+
+
+@pytest.mark.parametrize("E", ES)
+def test_single_valued_and_pooled_kernels_are_one_fold(E):
+    """scatter_fold_kernel and scatter_pool_fold_kernel share one insert and one flush (csrc/scatter_fold.hpp): a
+    schema of single-valued fields alone -- tables of 3 (hot, direct-mapped), 50 (direct-mapped) and 5 000 rows (hashed)
+    -- sent through both deterministic scatters with the same magnitude slot and deferred totals leaves the same
+    64-bit totals, bit for bit (exact integer sums of the same to_fixed values: no tolerance), and the same marks.
+    B = 1000: a ragged last chunk at both chunk sizes (512 lookups at E = 4 and 8, 256 at E = 16)."""
+    import mmlrec_amd  # noqa: F401
+    from mmlrec_amd import ops
+    from test_pooled_rows_gpu import draw_ids
+    dev = torch.device("cuda:0")
+    B, vocab = 1000, (3, 50, 5000)
+    rng = np.random.default_rng(4242 + E)
+    Xh = np.stack([draw_ids(rng, "zipf", v, B, 0) for v in vocab], axis=1).astype(np.float32)
+    g = torch.Generator().manual_seed(E)
+    d = torch.randn(B, 3 * E, generator=g) * torch.logspace(-6, 2, B).unsqueeze(1)[torch.randperm(B, generator=g)]
+    X, d_out = torch.from_numpy(Xh).to(dev), d.to(dev)
+    singles = [(f, f) for f in range(3)]
+    # the two shift rules agree at this B (mml_scatter_det_shift, mml_scatter_pool_det_shift)
+    assert ops.scatter_det_shift(B) == 28
+    assert ops.scatter_pool_det_shift((vocab, E, singles, []), B) == 28
+    slot = ops.amax_slots(1, dev)[0]
+    ops.amax_batch([(d_out, slot)])
+
+    def run(pooled_kernel):
+        grads = [torch.zeros(v, E, device=dev) for v in vocab]
+        acc = [torch.zeros(v, E, dtype=torch.int64, device=dev) for v in vocab]
+        marks = torch.zeros(ops.marks_bytes(vocab), dtype=torch.uint8, device=dev)
+        status = ops.new_status(dev)
+        kw = dict(amax_slot=slot, clear_marks=False, status=status, amax_supplied=True, defer_totals=True)
+        if pooled_kernel:
+            ops.scatter_pool_bwd_det(grads, X, singles, [], d_out, acc, marks, **kw)
+        else:
+            ops.scatter_bwd_det(grads, X, [0, 1, 2], d_out, acc, marks, **kw)
+        torch.cuda.synchronize()
+        assert int(status.item()) == 0
+        return [x.cpu().numpy() for x in grads], [a.cpu().numpy() for a in acc], marks.cpu().numpy()
+
+    g_s, acc_s, m_s = run(False)
+    g_p, acc_p, m_p = run(True)
+    assert any(a.any() for a in acc_s)
+    for t in range(3):
+        assert np.array_equal(acc_s[t], acc_p[t]), f"totals of table {t}"
+        assert not g_s[t].view(np.uint32).any() and not g_p[t].view(np.uint32).any()
+    assert np.array_equal(m_s, m_p)
+    base = 0
+    for t, v in enumerate(vocab):  # (and they are the rows of the batch)
+        assert np.array_equal(np.nonzero(m_s[base:base + v])[0], np.unique(Xh[:, t].astype(np.int64)))
+        base += 32 * ((v + 31) // 32)
 
 
 def test_nan_addend_reaches_its_row_and_nothing_else_moves():
