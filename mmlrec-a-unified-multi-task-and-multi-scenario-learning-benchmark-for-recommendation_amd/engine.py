@@ -19,6 +19,7 @@ import torch
 from . import _lib as L
 from . import profiling
 from . import ops
+from . import bind
 
 ACT = {"none": L.ACT_NONE, None: L.ACT_NONE, "linear": L.ACT_NONE, "relu": L.ACT_RELU, "sigmoid": L.ACT_SIGMOID,
        "sigmoid2": L.ACT_SIGMOID2}
@@ -211,6 +212,13 @@ class Plan:
         t = torch.zeros(*shape, dtype=dtype, device=self.device)
         self.keep.append(t)
         return t
+
+    def bound(self, b, **meta):
+        """The call-list entry (fn, args, meta) of a bind.Bound; the ctypes arrays and descriptors among its arguments
+        are kept alive with the plan."""
+        self.keep += [getattr(a, "_obj", a) for a in b.args
+                      if isinstance(getattr(a, "_obj", a), (C.Array, C.Structure))]
+        return (getattr(L.load(), b.name), b.args, meta)
 
     def _rows(self, n, pad_k=False):
         """[B, n] view of a fresh buffer with 16-byte aligned rows.  pad_k: when n is not a multiple of 16 the row is
@@ -644,57 +652,41 @@ class GatherOp(Op):
         return []
 
     def fwd_calls(self, plan):
-        lib = L.load()
         F = len(self.tables)
         E = self.tables[0].data.shape[1]
-        tabs = ops._ptr_array([t.data for t in self.tables])
-        vocab = (L.i64 * F)(*[t.data.shape[0] for t in self.tables])
-        col = (L.i32 * F)(*self.cols)
-        plan.keep += [tabs, vocab, col]
+        # (tables, X, cols, dense_col0, nd): how every bind.gather* builder opens
+        src = ([t.data for t in self.tables], self.X, self.cols, self.dense_col0, self.nd)
         meta = dict(kernel="gather_vec4_kernel" if E % 4 == 0 else "gather_scalar_kernel",
                     bytes=float(plan.B) * (F * (4 + 8 * E) + 8 * self.nd))  # index + row read + row write
         mr = self.mark_rows
+        out = self.out.buf
         if self.out.is16:  # bf16-storage path: dnn_input leaves the gather as the first layers' GEMM operand
             if mr is not None:
                 raise L.MMLError("the row-marking gather has no bf16 form (split dense update)")
-            meta16 = dict(kernel="gather16_kernel", bytes=float(plan.B) * (F * (4 + 6 * E) + 6 * self.nd))
-            return [(lib.mml_gather16_fwd, (tabs, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), self.dense_col0,
-                                            self.nd, plan.B, self.out.buf.data_ptr(), ops._ld(self.out.buf),
-                                            plan.status.data_ptr()), meta16)]
+            return [plan.bound(bind.gather16_fwd(*src, out, plan.status, B=plan.B), kernel="gather16_kernel",
+                               bytes=float(plan.B) * (F * (4 + 6 * E) + 6 * self.nd))]
         if mr is not None:
-            ps = ops._ptr_array(mr.seen)
-            rb = (L.i64 * (F + 1))(*mr.rowbase)
-            plan.keep += [ps, rb]
-            return [(lib.mml_gather_fwd_mark, (tabs, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X),
-                                               self.dense_col0, self.nd, plan.B, self.out.buf.data_ptr(),
-                                               ops._ld(self.out.buf), mr.marks.data_ptr(), plan.status.data_ptr()), meta),
-                    (lib.mml_rows_compact, (ps, vocab, rb, F, mr.touched.data_ptr(), mr.count.data_ptr(),
-                                            mr.touched.numel(), mr.marks.data_ptr()),
-                     dict(kernel="rows_compact_kernel", bytes=float(mr.marks.numel())))]
-        out = self.out.buf
-        nwg = int(lib.mml_gather_wgmax_len(F, E, self.nd, plan.B)) if plan.amax_pool is not None else 0
+            return [plan.bound(bind.gather_fwd_mark(*src, out, mr.marks, plan.status, B=plan.B), **meta),
+                    plan.bound(bind.rows_compact([t.data.shape[0] for t in self.tables], bind.rows_args(mr)),
+                               kernel="rows_compact_kernel", bytes=float(mr.marks.numel()))]
+        nwg = int(L.load().mml_gather_wgmax_len(F, E, self.nd, plan.B)) if plan.amax_pool is not None else 0
         if (nwg > 0 and plan.knobs.gather_wgmax and ops._ld(out) % 4 == 0 and
                 out.data_ptr() % 16 == 0 and all(t.data.data_ptr() % 16 == 0 for t in self.tables)):
             # the magnitude of the gathered input comes out of the gather itself: one value per workgroup, read by the
             # magnitude launch in front of the first GEMM instead of a pass over the whole output (25 -> 6 us at 65 536)
             wg = plan.zeros(1, nwg)
             self.out.amax_src = wg
-            return [(lib.mml_gather_fwd_wgmax, (tabs, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X),
-                                                self.dense_col0, self.nd, plan.B, out.data_ptr(), ops._ld(out),
-                                                wg.data_ptr(), nwg, plan.status.data_ptr()), meta)]
-        return [(lib.mml_gather_fwd, (tabs, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), self.dense_col0,
-                                      self.nd, plan.B, out.data_ptr(), ops._ld(out), plan.status.data_ptr()), meta)]
+            return [plan.bound(bind.gather_fwd_wgmax(*src, out, wg, nwg, plan.status, B=plan.B), **meta)]
+        return [plan.bound(bind.gather_fwd(*src, out, plan.status, B=plan.B), **meta)]
 
     def _det_setup(self, plan, emb_cols, shift):
         """The buffers and flags of the deterministic scatter call (mml_scatter_bwd_det / mml_scatter_pool_bwd_det):
-        (acc64 pointer array, mark map, magnitude slot, flags); sets self.det_deferred.  emb_cols: the columns of
+        (mark map, magnitude slot, flags); sets self.det_deferred.  emb_cols: the columns of
         d(dnn_input) the scatter reads, shift: the totals' shift for this batch."""
         det, sr = self.deterministic, self.sparse_rows
-        acc = ops._ptr_array(det["acc64"])
         marks = self.grad_marks if self.grad_marks is not None else (sr.marks if sr is not None else det["marks"])
         keep_marks = self.grad_marks is not None or sr is not None
         slot = det["slot"]
-        plan.keep += [acc]
         flags = 0 if keep_marks else L.SCATTER_DET_CLEAR_MARKS
         fused = plan.knobs.det_fused  # (MMLREC_DET_FUSED=0: the call measures and finalizes for itself)
         g = self.out
@@ -711,38 +703,26 @@ class GatherOp(Op):
                 L.opt_takes_det_totals([t.data.numel() for t in self.tables], self.grad_marks is not None)):
             flags |= L.SCATTER_DET_DEFER_TOTALS
             self.det_deferred = dict(slot=slot, shift=shift)
-        return acc, marks, slot, flags
+        return marks, slot, flags
 
-    def _rows_args(self, plan):
-        """The touched-row arguments of the scatter call (seen, rowbase, touched, count, cap, row_marks): the
-        bookkeeping of self.sparse_rows (one entry per table), or the marks alone."""
-        sr = self.sparse_rows
-        if sr is None:
-            return (None, None, None, None, 0, L.ptr(self.grad_marks))
-        seen = ops._ptr_array(sr.seen)
-        rb = (L.i64 * (len(self.tables) + 1))(*sr.rowbase)
-        plan.keep += [seen, rb]
-        return (seen, rb, sr.touched.data_ptr(), sr.count.data_ptr(), sr.touched.numel(), sr.marks.data_ptr())
+    def _rows_args(self):
+        """The touched-row arguments of the scatter call: the bookkeeping of self.sparse_rows (one entry per table), or
+        the marks alone."""
+        return bind.rows_args(self.sparse_rows, marks=self.grad_marks)
 
-    def _compact_call(self, extra, vocab):
-        """The compaction behind a deterministic scatter: the marks it left -> the touched list of self.sparse_rows
-        (extra: _rows_args' tuple, vocab: rows per table)."""
-        return (L.load().mml_rows_compact, (extra[0], vocab, extra[1], len(self.tables)) + extra[2:],
-                dict(kernel="rows_compact_kernel", bytes=float(self.sparse_rows.marks.numel()), tail=True))
+    def _compact_entry(self, plan):
+        """The compaction behind a deterministic scatter: the marks it left -> the touched list of self.sparse_rows."""
+        return plan.bound(bind.rows_compact([t.data.shape[0] for t in self.tables], self._rows_args()),
+                          kernel="rows_compact_kernel", bytes=float(self.sparse_rows.marks.numel()), tail=True)
 
     def bwd_calls(self, plan):
         if self.out.grad is None or not any(t.needs_grad for t in self.tables):
             return []
-        lib = L.load()
         F = len(self.tables)
         E = self.tables[0].data.shape[1]
-        gt = ops._ptr_array([t.grad for t in self.tables])
-        vocab = (L.i64 * F)(*[t.data.shape[0] for t in self.tables])
-        col = (L.i32 * F)(*self.cols)
-        plan.keep += [gt, vocab, col]
+        gt = [t.grad for t in self.tables]
         for t in self.tables:
             _claim(t)
-        extra = self._rows_args(plan)
         meta = dict(kernel=scatter_symbol(E),
                     bytes=float(plan.B) * F * (4 + 12 * E), tail=True)  # idx + grad read + row RMW
         det = self.deterministic
@@ -750,18 +730,16 @@ class GatherOp(Op):
             # deterministic scatter: 64-bit integer row totals, then fp32 (two launches + the magnitude of d(dnn_input),
             # or the fold alone: MML_SCATTER_DET_AMAX_SUPPLIED / _DEFER_TOTALS below);
             # the marks feed the marked dense update (left set) or the touched-row list (compaction, which clears them)
-            acc, marks, slot, flags = self._det_setup(plan, F * E, int(lib.mml_scatter_det_shift(plan.B)))
-            calls = [(lib.mml_scatter_bwd_det, (gt, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), plan.B,
-                                                self.out.grad.data_ptr(), ops._ld(self.out.grad), acc, slot.data_ptr(),
-                                                marks.data_ptr(), flags, plan.status.data_ptr()),
-                      dict(meta, kernel="scatter_fold_kernel<det>", det_flags=flags,
-                           ptrs=[a.data_ptr() for a in det["acc64"]]))]
+            marks, slot, flags = self._det_setup(plan, F * E, int(L.load().mml_scatter_det_shift(plan.B)))
+            calls = [plan.bound(bind.scatter_bwd_det(gt, self.X, self.cols, self.out.grad, det["acc64"], slot, marks, flags,
+                                                     plan.status, B=plan.B),
+                                **dict(meta, kernel="scatter_fold_kernel<det>", det_flags=flags,
+                                       ptrs=[a.data_ptr() for a in det["acc64"]]))]
             if self.sparse_rows is not None:
-                calls.append(self._compact_call(extra, vocab))
+                calls.append(self._compact_entry(plan))
             return calls
-        return [(lib.mml_scatter_bwd, (gt, vocab, col, F, E, self.X.data_ptr(), ops._ld(self.X), plan.B,
-                                       self.out.grad.data_ptr(), ops._ld(self.out.grad)) + extra +
-                 (plan.status.data_ptr(),), meta)]
+        return [plan.bound(bind.scatter_bwd(gt, self.X, self.cols, self.out.grad, self._rows_args(), plan.status, B=plan.B),
+                           **meta)]
 
 
 class PooledGatherOp(GatherOp):
@@ -775,89 +753,66 @@ class PooledGatherOp(GatherOp):
         self.singles, self.pooled = list(singles), list(pooled)
         self.argmax = None
 
-    def _desc(self, plan, which):
-        d = ops.make_pool_desc([getattr(t, which) for t in self.tables], self.singles,
-                               [ops.PooledField(*pf) for pf in self.pooled])
-        plan.keep.append(d)
-        return d
+    def _desc(self, which):
+        return ops.make_pool_desc([getattr(t, which) for t in self.tables], self.singles,
+                                  [ops.PooledField(*pf) for pf in self.pooled])
 
     def _lookups(self):
         return len(self.singles) + sum(pf[1] for pf in self.pooled)
 
     def fwd_calls(self, plan):
-        lib = L.load()
         if self.out.is16 or self.mark_rows is not None:
             raise L.MMLError("the pooled gather has no bf16-storage form and no row-marking form")
         E, P = self.tables[0].data.shape[1], len(self.pooled)
-        d = self._desc(plan, "data")
+        d = self._desc("data")
         if any(pf[2] == "max" for pf in self.pooled):
             self.argmax = plan.zeros(plan.B, P * E, dtype=torch.uint8)
-        out = self.out.buf
         # ids + rows read (every position: an upper bound of the valid ones) + blocks and dense columns written
         meta = dict(kernel="gather_pool_kernel",
                     bytes=float(plan.B) * (len(self.singles) * (4 + 8 * E) + 8 * self.nd +
                                            sum(4 * pf[1] + 4 * E * pf[1] + 4 * E for pf in self.pooled)))
         wg, nwg = None, 0
         if plan.amax_pool is not None and plan.knobs.gather_wgmax:
-            nwg = int(lib.mml_gather_pool_wgmax_len(C.byref(d), self.nd, plan.B))
+            nwg = int(L.load().mml_gather_pool_wgmax_len(C.byref(d), self.nd, plan.B))
             if nwg > 0:
                 wg = plan.zeros(1, nwg)
                 self.out.amax_src = wg
-        return [(lib.mml_gather_pool_fwd, (C.byref(d), self.X.data_ptr(), ops._ld(self.X), self.dense_col0, self.nd,
-                                           plan.B, out.data_ptr(), ops._ld(out), L.ptr(self.argmax),
-                                           0 if self.argmax is None else ops._ld(self.argmax), L.ptr(wg), nwg,
-                                           plan.status.data_ptr()), meta)]
+        return [plan.bound(bind.gather_pool_fwd(d, self.X, self.dense_col0, self.nd, self.out.buf, self.argmax, wg, nwg,
+                                                plan.status, B=plan.B), **meta)]
 
     def bwd_calls(self, plan):
         if self.out.grad is None or not any(t.needs_grad for t in self.tables):
             return []
-        lib = L.load()
-        E, T = self.tables[0].data.shape[1], len(self.tables)
-        d = self._desc(plan, "grad")
+        E = self.tables[0].data.shape[1]
+        d = self._desc("grad")
         for t in self.tables:
             _claim(t)
-        extra = self._rows_args(plan)
         meta = dict(kernel="scatter_pool_fold_kernel", tail=True,  # ids + dOut block read + row read-modify-write
                     bytes=float(plan.B) * (len(self.singles) * (4 + 12 * E) +
                                            sum(4 * pf[1] + 4 * E + 8 * E * pf[1] for pf in self.pooled)))
         det = self.deterministic
         if det is not None:
             # deterministic scatter (GatherOp.bwd_calls): totals, marks and the finalize launch are per TABLE
-            shift = int(lib.mml_scatter_pool_det_shift(C.byref(d), plan.B))
+            shift = int(L.load().mml_scatter_pool_det_shift(C.byref(d), plan.B))
             if shift < 0:
                 raise L.MMLError(f"deterministic pooled scatter: a batch of {plan.B} samples times the lookups of one "
                                  "table leaves no headroom in the 64-bit totals")
-            acc, marks, slot, flags = self._det_setup(plan, (len(self.singles) + len(self.pooled)) * E, shift)
-            calls = [(lib.mml_scatter_pool_bwd_det, (C.byref(d), self.X.data_ptr(), ops._ld(self.X), plan.B,
-                                                     self.out.grad.data_ptr(), ops._ld(self.out.grad),
-                                                     L.ptr(self.argmax), 0 if self.argmax is None else ops._ld(self.argmax),
-                                                     acc, slot.data_ptr(), marks.data_ptr(), flags,
-                                                     plan.status.data_ptr()),
-                      dict(meta, kernel="scatter_pool_fold_kernel<det>", det_flags=flags,
-                           ptrs=[a.data_ptr() for a in det["acc64"]]))]
+            marks, slot, flags = self._det_setup(plan, (len(self.singles) + len(self.pooled)) * E, shift)
+            calls = [plan.bound(bind.scatter_pool_bwd_det(d, self.X, self.out.grad, self.argmax, det["acc64"], slot, marks,
+                                                          flags, plan.status, B=plan.B),
+                                **dict(meta, kernel="scatter_pool_fold_kernel<det>", det_flags=flags,
+                                       ptrs=[a.data_ptr() for a in det["acc64"]]))]
             if self.sparse_rows is not None:
-                vocab = (L.i64 * T)(*[t.data.shape[0] for t in self.tables])
-                plan.keep.append(vocab)
-                calls.append(self._compact_call(extra, vocab))
+                calls.append(self._compact_entry(plan))
             return calls
-        return [(lib.mml_scatter_pool_bwd, (C.byref(d), self.X.data_ptr(), ops._ld(self.X), plan.B,
-                                            self.out.grad.data_ptr(), ops._ld(self.out.grad), L.ptr(self.argmax),
-                                            0 if self.argmax is None else ops._ld(self.argmax)) + extra +
-                 (plan.status.data_ptr(),), meta)]
+        return [plan.bound(bind.scatter_pool_bwd(d, self.X, self.out.grad, self.argmax, self._rows_args(), plan.status,
+                                                 B=plan.B), **meta)]
 
     def unique_calls(self, plan, rows):
         """The batch's distinct VALID rows per table -> `seen` bitmaps + touched list (the index pre-pass of lazy_exact)."""
-        lib = L.load()
-        T = len(self.tables)
-        d = self._desc(plan, "data")
-        ps = ops._ptr_array(rows.seen)
-        rb = (L.i64 * (T + 1))(*rows.rowbase)
-        plan.keep += [ps, rb]
         X, nrows = self.index_view(plan)
-        return [(lib.mml_index_unique_pool, (C.byref(d), X.data_ptr(), ops._ld(X), nrows, ps, rb,
-                                             rows.touched.data_ptr(), rows.count.data_ptr(), rows.touched.numel(),
-                                             rows.marks.data_ptr(), plan.status.data_ptr()),
-                 dict(kernel="mark_pool_rows_kernel+rows_compact_kernel", bytes=float(nrows) * self._lookups() * 5))]
+        return [plan.bound(bind.index_unique_pool(self._desc("data"), X, bind.rows_args(rows), plan.status, B=nrows),
+                           kernel="mark_pool_rows_kernel+rows_compact_kernel", bytes=float(nrows) * self._lookups() * 5)]
 
 
 def g16_layer_ok(B, K, N, training):

@@ -10,8 +10,10 @@ import os
 import torch
 
 from . import _lib as L
+from . import bind
 
 _workspaces = {}
+_ld, _ptr_array = bind.ld, bind.ptr_array
 
 
 def _stream():
@@ -48,8 +50,9 @@ def _f32_2d(t, name):
     return t
 
 
-def _ld(t):
-    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+def _issue(b):
+    """Launch a bind.Bound on the current stream."""
+    L.check(getattr(L.load(), b.name)(*b.args, _stream()), b.name)
 
 
 _SPIN_CAL = {}  # device index -> (spin ticks for ~0.2 ms, measured ms of one such spin)
@@ -124,13 +127,6 @@ def workspace(nbytes, device):
     return ws
 
 
-def _ptr_array(tensors):
-    arr = (L.fp * len(tensors))()
-    for i, t in enumerate(tensors):
-        arr[i] = t.data_ptr() if t is not None else None
-    return arr
-
-
 def new_status(device):
     return torch.zeros(1, dtype=torch.int32, device=device)
 
@@ -146,20 +142,11 @@ def check_status(status, what="embedding lookup"):
 # ---------------------------------------------------------------------------------------------- K1 / K2
 def gather_fwd(tables, X, cols, dense_col0=0, nd=0, out=None, status=None):
     """dnn_input = concat_f table_f[X[:, cols[f]].long()] ++ X[:, dense_col0:dense_col0+nd]."""
-    lib = L.load()
     _need_gpu(X, *tables)
     X = _f32_2d(X, "X")
-    F = len(tables)
-    E = tables[0].shape[1]
-    B = X.shape[0]
-    K0 = F * E + nd
     if out is None:
-        out = torch.empty((B, K0), dtype=torch.float32, device=X.device)
-    vocab = (L.i64 * F)(*[t.shape[0] for t in tables])
-    col = (L.i32 * F)(*cols)
-    rc = lib.mml_gather_fwd(_ptr_array(tables), vocab, col, F, E, X.data_ptr(), _ld(X), dense_col0, nd, B,
-                            out.data_ptr(), _ld(out), L.ptr(status), _stream())
-    L.check(rc, "mml_gather_fwd")
+        out = torch.empty((X.shape[0], len(tables) * tables[0].shape[1] + nd), dtype=torch.float32, device=X.device)
+    _issue(bind.gather_fwd(tables, X, cols, dense_col0, nd, out, status))
     return out
 
 
@@ -173,26 +160,17 @@ def gather_fwd_wgmax(tables, X, cols, dense_col0=0, nd=0, out=None, status=None)
         out = torch.empty((B, F * E + nd), dtype=torch.float32, device=X.device)
     n = int(lib.mml_gather_wgmax_len(F, E, nd, B))
     wg = torch.full((1, max(n, 1)), float("nan"), dtype=torch.float32, device=X.device)
-    vocab = (L.i64 * F)(*[t.shape[0] for t in tables])
-    col = (L.i32 * F)(*cols)
-    rc = lib.mml_gather_fwd_wgmax(_ptr_array(tables), vocab, col, F, E, X.data_ptr(), _ld(X), dense_col0, nd, B,
-                                  out.data_ptr(), _ld(out), wg.data_ptr(), n, L.ptr(status), _stream())
-    L.check(rc, "mml_gather_fwd_wgmax")
+    _issue(bind.gather_fwd_wgmax(tables, X, cols, dense_col0, nd, out, wg, n, status))
     return out, wg
 
 
 def gather_fwd_idx32(tables, idx, dense=None, out=None, status=None):
-    lib = L.load()
     _need_gpu(idx, *tables)
     F, E, B = len(tables), tables[0].shape[1], idx.shape[0]
     nd = 0 if dense is None else dense.shape[1]
     if out is None:
         out = torch.empty((B, F * E + nd), dtype=torch.float32, device=idx.device)
-    vocab = (L.i64 * F)(*[t.shape[0] for t in tables])
-    rc = lib.mml_gather_fwd_idx32(_ptr_array(tables), vocab, F, E, idx.data_ptr(), idx.stride(0), L.ptr(dense),
-                                  0 if dense is None else dense.stride(0), nd, B, out.data_ptr(), _ld(out),
-                                  L.ptr(status), _stream())
-    L.check(rc, "mml_gather_fwd_idx32")
+    _issue(bind.gather_fwd_idx32(tables, idx, dense, out, status))
     return out
 
 
@@ -256,10 +234,7 @@ def gather_pool_fwd(tables, X, singles, pooled, dense_col0=0, nd=0, out=None, ar
     if wgmax:
         n = int(lib.mml_gather_pool_wgmax_len(C.byref(d), nd, B))
         wg = torch.full((1, max(n, 1)), float("nan"), dtype=torch.float32, device=X.device)
-    rc = lib.mml_gather_pool_fwd(C.byref(d), X.data_ptr(), _ld(X), dense_col0, nd, B, out.data_ptr(), _ld(out),
-                                 L.ptr(argmax), 0 if argmax is None else _ld(argmax), L.ptr(wg), n, L.ptr(status),
-                                 _stream())
-    L.check(rc, "mml_gather_pool_fwd")
+    _issue(bind.gather_pool_fwd(d, X, dense_col0, nd, out, argmax, wg, n, status))
     return out, argmax, wg
 
 
@@ -267,17 +242,10 @@ def scatter_pool_bwd(grad_tables, X, singles, pooled, d_out, argmax=None, seen=N
                      touched_count=None, status=None, marks=None):
     """Table gradients of every field, single-valued and pooled, in ONE launch (mml_scatter_pool_bwd); seen / rowbase /
     marks are per TABLE (marks: marks_bytes of the tables' sizes)."""
-    lib = L.load()
     _need_gpu(X, d_out)
     d = make_pool_desc(grad_tables, singles, pooled)
-    T = len(grad_tables)
-    rc = lib.mml_scatter_pool_bwd(C.byref(d), X.data_ptr(), _ld(X), X.shape[0], d_out.data_ptr(), _ld(d_out),
-                                  L.ptr(argmax), 0 if argmax is None else _ld(argmax),
-                                  _ptr_array(seen) if seen is not None else None,
-                                  (L.i64 * (T + 1))(*rowbase) if rowbase is not None else None, L.ptr(touched),
-                                  L.ptr(touched_count), 0 if touched is None else touched.numel(), L.ptr(marks),
-                                  L.ptr(status), _stream())
-    L.check(rc, "mml_scatter_pool_bwd")
+    _issue(bind.scatter_pool_bwd(d, X, d_out, argmax, bind.rows_args(None, seen, rowbase, touched, touched_count, marks),
+                                 status))
 
 
 def scatter_pool_bwd_det(grad_tables, X, singles, pooled, d_out, acc64, marks, argmax=None, amax_slot=None,
@@ -286,7 +254,6 @@ def scatter_pool_bwd_det(grad_tables, X, singles, pooled, d_out, acc64, marks, a
     (all zero between calls), marks = the byte map of marks_bytes(table sizes).  Bitwise repeatable, independent of the
     order of the samples; tables shared by several fields are allowed.  amax_supplied / defer_totals as in
     scatter_bwd_det, with scatter_pool_det_shift(...) as the totals' shift.  `flags` (an int) replaces the three switches."""
-    lib = L.load()
     _need_gpu(X, d_out)
     d = make_pool_desc(grad_tables, singles, pooled)
     if amax_slot is None:
@@ -294,11 +261,7 @@ def scatter_pool_bwd_det(grad_tables, X, singles, pooled, d_out, acc64, marks, a
     if flags is None:
         flags = ((L.SCATTER_DET_CLEAR_MARKS if clear_marks else 0) | (L.SCATTER_DET_AMAX_SUPPLIED if amax_supplied else 0) |
                  (L.SCATTER_DET_DEFER_TOTALS if defer_totals else 0))
-    rc = lib.mml_scatter_pool_bwd_det(C.byref(d), X.data_ptr(), _ld(X), X.shape[0], d_out.data_ptr(), _ld(d_out),
-                                      L.ptr(argmax), 0 if argmax is None else _ld(argmax),
-                                      _ptr_array(acc64) if acc64 is not None else None, amax_slot.data_ptr(),
-                                      L.ptr(marks), int(flags), L.ptr(status), _stream())
-    L.check(rc, "mml_scatter_pool_bwd_det")
+    _issue(bind.scatter_pool_bwd_det(d, X, d_out, argmax, acc64, amax_slot, marks, flags, status))
 
 
 def scatter_pool_det_shift(desc, B):
@@ -315,11 +278,7 @@ def index_unique_pool(vocab, E, X, singles, pooled, seen, rowbase, touched, touc
     """The distinct VALID rows of a batch per table, without gradients (mml_index_unique_pool)."""
     _need_gpu(X, touched, touched_count)
     d = make_pool_desc(None, singles, pooled, vocab=(list(vocab), E))
-    T = len(vocab)
-    rc = L.load().mml_index_unique_pool(C.byref(d), X.data_ptr(), _ld(X), X.shape[0], _ptr_array(seen),
-                                        (L.i64 * (T + 1))(*rowbase), touched.data_ptr(), touched_count.data_ptr(),
-                                        touched.numel(), L.ptr(marks), L.ptr(status), _stream())
-    L.check(rc, "mml_index_unique_pool")
+    _issue(bind.index_unique_pool(d, X, bind.rows_args(None, seen, rowbase, touched, touched_count, marks), status))
 
 
 def marks_bytes(vocab):
@@ -331,17 +290,9 @@ def marks_bytes(vocab):
 def scatter_bwd(grad_tables, X, cols, d_out, seen=None, rowbase=None, touched=None, touched_count=None, status=None,
                 marks=None):
     """grad_tables[f][X[:, cols[f]].long()] += d_out[:, f*E:(f+1)*E] (float atomics)."""
-    lib = L.load()
     _need_gpu(X, d_out, *grad_tables)
-    F, E, B = len(grad_tables), grad_tables[0].shape[1], X.shape[0]
-    vocab = (L.i64 * F)(*[t.shape[0] for t in grad_tables])
-    col = (L.i32 * F)(*cols)
-    seen_arr = _ptr_array(seen) if seen is not None else None
-    rb = (L.i64 * (F + 1))(*rowbase) if rowbase is not None else None
-    rc = lib.mml_scatter_bwd(_ptr_array(grad_tables), vocab, col, F, E, X.data_ptr(), _ld(X), B, d_out.data_ptr(),
-                             _ld(d_out), seen_arr, rb, L.ptr(touched), L.ptr(touched_count),
-                             0 if touched is None else touched.numel(), L.ptr(marks), L.ptr(status), _stream())
-    L.check(rc, "mml_scatter_bwd")
+    _issue(bind.scatter_bwd(grad_tables, X, cols, d_out,
+                            bind.rows_args(None, seen, rowbase, touched, touched_count, marks), status))
 
 
 def scatter_bwd_det(grad_tables, X, cols, d_out, acc64, marks, amax_slot=None, clear_marks=True, status=None,
@@ -350,19 +301,12 @@ def scatter_bwd_det(grad_tables, X, cols, d_out, acc64, marks, amax_slot=None, c
     marks = the byte map of marks_bytes(vocab).  Bitwise repeatable, independent of the order of the samples.
     amax_supplied: amax_slot already holds the magnitude of d_out (no magnitude pass); defer_totals: the totals stay in
     acc64 and the marks set, for opt_step_dense entries that carry (acc64, slot, scatter_det_shift(B))."""
-    lib = L.load()
     _need_gpu(X, d_out, *grad_tables)
-    F, E, B = len(grad_tables), grad_tables[0].shape[1], X.shape[0]
-    vocab = (L.i64 * F)(*[t.shape[0] for t in grad_tables])
-    col = (L.i32 * F)(*cols)
     if amax_slot is None:
         amax_slot = amax_slots(1, X.device)[0]
-    rc = lib.mml_scatter_bwd_det(_ptr_array(grad_tables), vocab, col, F, E, X.data_ptr(), _ld(X), B, d_out.data_ptr(),
-                                 _ld(d_out), _ptr_array(acc64), amax_slot.data_ptr(), marks.data_ptr(),
-                                 (L.SCATTER_DET_CLEAR_MARKS if clear_marks else 0) |
-                                 (L.SCATTER_DET_AMAX_SUPPLIED if amax_supplied else 0) |
-                                 (L.SCATTER_DET_DEFER_TOTALS if defer_totals else 0), L.ptr(status), _stream())
-    L.check(rc, "mml_scatter_bwd_det")
+    flags = ((L.SCATTER_DET_CLEAR_MARKS if clear_marks else 0) | (L.SCATTER_DET_AMAX_SUPPLIED if amax_supplied else 0) |
+             (L.SCATTER_DET_DEFER_TOTALS if defer_totals else 0))
+    _issue(bind.scatter_bwd_det(grad_tables, X, cols, d_out, acc64, amax_slot, marks, flags, status))
 
 
 def scatter_det_shift(B):
@@ -373,16 +317,9 @@ def scatter_det_shift(B):
 def scatter_bwd_idx32(grad_tables, idx, d_out, seen=None, rowbase=None, touched=None, touched_count=None, status=None,
                       marks=None):
     """grad_tables[f][idx[:, f]] += d_out[:, f*E:(f+1)*E] with native int32 indices [B, F]."""
-    lib = L.load()
     _need_gpu(idx, d_out, *grad_tables)
-    F, E, B = len(grad_tables), grad_tables[0].shape[1], idx.shape[0]
-    vocab = (L.i64 * F)(*[t.shape[0] for t in grad_tables])
-    seen_arr = _ptr_array(seen) if seen is not None else None
-    rb = (L.i64 * (F + 1))(*rowbase) if rowbase is not None else None
-    rc = lib.mml_scatter_bwd_idx32(_ptr_array(grad_tables), vocab, F, E, idx.data_ptr(), idx.stride(0), B,
-                                   d_out.data_ptr(), _ld(d_out), seen_arr, rb, L.ptr(touched), L.ptr(touched_count),
-                                   0 if touched is None else touched.numel(), L.ptr(marks), L.ptr(status), _stream())
-    L.check(rc, "mml_scatter_bwd_idx32")
+    _issue(bind.scatter_bwd_idx32(grad_tables, idx, d_out,
+                                  bind.rows_args(None, seen, rowbase, touched, touched_count, marks), status))
 
 
 def route(X, cols, vocab, keybase, world, status=None):
@@ -1031,31 +968,17 @@ def opt_step_dense(entries, hyper):
 
 
 def opt_step_rows(tables, grad_tables, state1, state2, seen, rowbase, touched, touched_count, hyper, last=None):
-    F, E = len(tables), tables[0].shape[1]
-    rb = (L.i64 * (F + 1))(*rowbase)
-    L.check(L.load().mml_opt_step_rows(_ptr_array(tables), _ptr_array(grad_tables),
-                                       _ptr_array(state1) if state1 is not None else None,
-                                       _ptr_array(state2) if state2 is not None else None,
-                                       _ptr_array(seen), rb, F, E, touched.data_ptr(), touched_count.data_ptr(),
-                                       touched.numel(), _ptr_array(last) if last is not None else None,
-                                       C.byref(hyper), _stream()), "mml_opt_step_rows")
+    _issue(bind.opt_step_rows(tables, grad_tables, state1, state2,
+                              bind.rows_args(None, seen, rowbase, touched, touched_count), hyper, last))
 
 
 def index_unique(vocab, cols, E, X, seen, rowbase, touched, touched_count, status=None, marks=None):
-    F = len(vocab)
-    L.check(L.load().mml_index_unique((L.i64 * F)(*vocab), (L.i32 * F)(*cols), F, E, X.data_ptr(), _ld(X), X.shape[0],
-                                      _ptr_array(seen), (L.i64 * (F + 1))(*rowbase), touched.data_ptr(),
-                                      touched_count.data_ptr(), touched.numel(), L.ptr(marks), L.ptr(status), _stream()),
-            "mml_index_unique")
+    _issue(bind.index_unique(vocab, cols, E, X, bind.rows_args(None, seen, rowbase, touched, touched_count, marks), status))
 
 
 def opt_catchup_rows(tables, state1, state2, last, rowbase, touched, touched_count, hyper):
-    F, E = len(tables), tables[0].shape[1]
-    L.check(L.load().mml_opt_catchup_rows(_ptr_array(tables), _ptr_array(state1),
-                                          _ptr_array(state2) if state2 is not None else None, _ptr_array(last),
-                                          (L.i64 * (F + 1))(*rowbase), F, E, touched.data_ptr(),
-                                          touched_count.data_ptr(), touched.numel(), C.byref(hyper), _stream()),
-            "mml_opt_catchup_rows")
+    _issue(bind.opt_catchup_rows(tables, state1, state2, last, bind.rows_args(None, None, rowbase, touched, touched_count),
+                                 hyper))
 
 
 def opt_catchup_dense(table, state1, state2, last, hyper):
@@ -1206,16 +1129,11 @@ def cast16(src, transpose=False, out=None):
 
 def gather16_fwd(tables, X, cols, dense_col0=0, nd=0, out=None, status=None):
     """gather_fwd writing dnn_input as bf16 (mml_gather16_fwd)."""
-    lib = L.load()
     _need_gpu(X, *tables)
     X = _f32_2d(X, "X")
-    F, E, B = len(tables), tables[0].shape[1], X.shape[0]
     if out is None:
-        out = torch.empty((B, F * E + nd), dtype=torch.bfloat16, device=X.device)
-    vocab = (L.i64 * F)(*[t.shape[0] for t in tables])
-    col = (L.i32 * F)(*cols)
-    L.check(lib.mml_gather16_fwd(_ptr_array(tables), vocab, col, F, E, X.data_ptr(), _ld(X), dense_col0, nd, B,
-                                 out.data_ptr(), _ld(out), L.ptr(status), _stream()), "mml_gather16_fwd")
+        out = torch.empty((X.shape[0], len(tables) * tables[0].shape[1] + nd), dtype=torch.bfloat16, device=X.device)
+    _issue(bind.gather16_fwd(tables, X, cols, dense_col0, nd, out, status))
     return out
 
 

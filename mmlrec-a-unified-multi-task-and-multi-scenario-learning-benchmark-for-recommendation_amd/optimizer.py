@@ -16,6 +16,7 @@ import torch
 from . import _lib as L
 from . import engine as E
 from . import ops
+from . import bind
 
 
 @dataclasses.dataclass(frozen=True)
@@ -532,44 +533,32 @@ class Optimizer:
         """The row update over the touched list (sparse_rows, lazy_exact, the touched half of a split dense update) and,
         for the appending scatter only, the list's reset."""
         rows = self.store.rows
-        a = self._row_arrays(plan, names, grads=True, last=self.table_update == "lazy_exact")
+        tabs = [self.store.pvals[n] for n in names]
         self.all_rows_warm(names)  # (the row kernels write moments and know no warm map)
-        calls = [(L.load().mml_opt_step_rows, (a["param"], a["grad"], a["s1"], a["s2"], a["seen"], a["rowbase"], a["F"],
-                                               a["E"], rows.touched.data_ptr(), rows.count.data_ptr(),
-                                               rows.touched.numel(), a["last"], C.byref(hyper)),
-                  dict(kernel="opt_rows_kernel"))]
+        calls = [plan.bound(bind.opt_step_rows([t.data for t in tabs], [t.grad for t in tabs], *self._moments(names),
+                                               bind.rows_args(rows), hyper,
+                                               last=[self.last[n] for n in names] if self.table_update == "lazy_exact"
+                                               else None), kernel="opt_rows_kernel")]
         # the list is REBUILT every step by the compaction that follows the marking kernels (E in 4, 8, 16: it
         # resets the counter itself); only the appending atomic path needs the reset here
-        if a["E"] not in (4, 8, 16) or knobs.scatter_old:
+        if tabs[0].data.shape[1] not in (4, 8, 16) or knobs.scatter_old:
             calls.append((L.load().mml_counter_update, (rows.count.data_ptr(), 0, 1)))
         return calls
 
-    def _row_arrays(self, plan, names, grads=False, state=True, last=False):
-        """The per-table arrays the row kernels take (mml_index_unique, mml_opt_catchup_rows, mml_opt_step_rows), over the
-        tables `names` and the store's row bookkeeping, kept alive in plan.keep; what was not asked for is None."""
-        st, rows = self.store, self.store.rows
-        tabs = [st.pvals[n] for n in names]
-        F = len(tabs)
-        a = dict(F=F, E=tabs[0].data.shape[1], vocab=(L.i64 * F)(*[t.data.shape[0] for t in tabs]),
-                 param=ops._ptr_array([t.data for t in tabs]), seen=ops._ptr_array(rows.seen),
-                 rowbase=(L.i64 * (F + 1))(*rows.rowbase),
-                 grad=ops._ptr_array([t.grad for t in tabs]) if grads else None,
-                 s1=ops._ptr_array([self.state[n][0] for n in names]) if state and self.kind != "sgd" else None,
-                 s2=ops._ptr_array([self.state[n][1] for n in names]) if state and self.kind == "adam" else None,
-                 last=ops._ptr_array([self.last[n] for n in names]) if last else None)
-        plan.keep += [v for v in a.values() if isinstance(v, C.Array)]
-        return a
+    def _moments(self, names):
+        """(state1, state2) of the tables `names` as the row kernels take them: a list per moment the optimizer kind keeps,
+        None for the others."""
+        return ([self.state[n][0] for n in names] if self.kind != "sgd" else None,
+                [self.state[n][1] for n in names] if self.kind == "adam" else None)
 
-    def _index_unique_call(self, plan, gop, a):
-        """The batch's distinct rows -> `seen` bitmaps + touched list (a = _row_arrays over every table)."""
-        rows = self.store.rows
+    def _index_unique_entry(self, plan, gop):
+        """The batch's distinct rows -> `seen` bitmaps + touched list, over every table of the store."""
+        st = self.store
+        tabs = [st.pvals[n] for n in st.table_names]
         X, nrows = gop.index_view(plan)
-        col = (L.i32 * a["F"])(*gop.cols)
-        plan.keep.append(col)
-        return (L.load().mml_index_unique, (a["vocab"], col, a["F"], a["E"], X.data_ptr(), ops._ld(X), nrows, a["seen"],
-                                            a["rowbase"], rows.touched.data_ptr(), rows.count.data_ptr(),
-                                            rows.touched.numel(), rows.marks.data_ptr(), plan.status.data_ptr()),
-                dict(kernel="mark_rows_kernel+rows_compact_kernel", bytes=float(nrows) * a["F"] * 5))
+        return plan.bound(bind.index_unique([t.data.shape[0] for t in tabs], gop.cols, tabs[0].data.shape[1], X,
+                                            bind.rows_args(st.rows), plan.status, B=nrows),
+                          kernel="mark_rows_kernel+rows_compact_kernel", bytes=float(nrows) * len(tabs) * 5)
 
     def index_pre_calls(self, plan):
         """Index pre-pass of the split dense update (and of a PCGrad per-task step over sparse_rows): the batch's distinct
@@ -577,8 +566,7 @@ class Optimizer:
         st, gop = self.store, plan.ops[0]
         if st.rows is None or list(st.rows_names) != list(st.table_names):
             raise L.MMLError("split dense update needs ParamStore.ensure_rows over every table")
-        unique = self._index_unique_call(plan, gop, self._row_arrays(plan, st.table_names, state=False))
-        return gop.pre_index_calls(plan) + [unique]
+        return gop.pre_index_calls(plan) + [self._index_unique_entry(plan, gop)]
 
     # ---- regulariser (model/basemodel.py:524-540) ---------------------------------------------------------
     def _reg_map(self):
@@ -614,25 +602,23 @@ class Optimizer:
         rows = st.rows
         if self.last is None:
             self.last = {n: torch.zeros(st.pvals[n].data.shape[0], dtype=torch.int32, device=st.device) for n in names}
-        a = self._row_arrays(plan, names, last=True)
+        tabs = [st.pvals[n].data for n in names]
+        ra = bind.rows_args(rows)
         self.all_rows_warm(names)  # (the catch-up writes moments)
         hyper = ops.make_hyper(self.kind, self.lr, step=0, step_dev=self.step_dev)
-        plan.keep.append(hyper)
-        catchup = (lib.mml_opt_catchup_rows, (a["param"], a["s1"], a["s2"], a["last"], a["rowbase"], a["F"], a["E"],
-                                              rows.touched.data_ptr(), rows.count.data_ptr(), rows.touched.numel(),
-                                              C.byref(hyper)), dict(kernel="opt_catchup_kernel"))
+        catchup = plan.bound(bind.opt_catchup_rows(tabs, *self._moments(names), [self.last[n] for n in names], ra, hyper),
+                             kernel="opt_catchup_kernel")
         if getattr(gop, "owns_lazy", False):
             # row-sharded tables: the keys to bring up to date only exist on the owner after the index exchange, so
             # the gather op launches (unique -> catch-up) itself, on the flat shard (F == 1)
-            if a["F"] != 1:
+            if len(tabs) != 1:
                 raise L.MMLError("row-sharded lazy_exact expects the single flat shard")
+            vocab, Em = (L.i64 * 1)(tabs[0].shape[0]), tabs[0].shape[1]
 
             def launch(keys_ptr, n, stream):
                 if n:
-                    L.check(lib.mml_index_unique_idx32(a["vocab"], 1, a["E"], keys_ptr, 1, n, a["seen"], a["rowbase"],
-                                                       rows.touched.data_ptr(), rows.count.data_ptr(),
-                                                       rows.touched.numel(), rows.marks.data_ptr(),
-                                                       plan.status.data_ptr(), stream), "mml_index_unique_idx32")
+                    L.check(lib.mml_index_unique_idx32(vocab, 1, Em, keys_ptr, 1, n, *ra, plan.status.data_ptr(),
+                                                       stream), "mml_index_unique_idx32")
                     L.check(catchup[0](*catchup[1], stream), "mml_opt_catchup_rows")
             gop.lazy_launch = launch
             return []
@@ -640,8 +626,7 @@ class Optimizer:
             raise L.MMLError("lazy_exact table updates are not available on the table-wise sharded path")
         if isinstance(gop, E.PooledGatherOp):
             return gop.pre_index_calls(plan) + gop.unique_calls(plan, rows) + [catchup]
-        unique = self._index_unique_call(plan, gop, a)
-        return gop.pre_index_calls(plan) + [unique, catchup]
+        return gop.pre_index_calls(plan) + [self._index_unique_entry(plan, gop), catchup]
 
     def flush(self):
         """Bring EVERY table row to the current step (needed before anything outside the fused step reads a table)."""

@@ -31,6 +31,7 @@ from . import _lib as L
 from . import engine as E
 from . import optimizer as O
 from . import ops
+from . import bind
 
 
 class CollectiveError(RuntimeError):
@@ -309,14 +310,7 @@ class RowShardedGatherOp(E.Op):
         self.grad_send = torch.empty(self.B * self.F, self.sh.emb, dtype=torch.float32, device=plan.device)
         self.d_tab = ops._ptr_array([self.grad_send] * self.F)
         self.o_grad = ops._ptr_array([self.shard.grad])
-        sr = self.sparse_rows
-        if sr is not None:
-            self.o_seen = ops._ptr_array(sr.seen)
-            self.o_rb = (L.i64 * 2)(*sr.rowbase)
-            self.o_extra = (self.o_seen, self.o_rb, sr.touched.data_ptr(), sr.count.data_ptr(), sr.touched.numel(),
-                            sr.marks.data_ptr())
-        else:
-            self.o_extra = (None, None, None, None, 0, L.ptr(self.grad_marks))
+        self.o_extra = bind.rows_args(self.sparse_rows, marks=self.grad_marks)
         return [(E.PY, self._backward, (), dict(kernel="row_sharded_backward_exchange", tail=True))]
 
     # ---- run time ----------------------------------------------------------------------------------
@@ -584,7 +578,7 @@ class ShardedGatherOp(E.Op):
         self.comm.all_to_all_single(out, inp, out_splits, in_splits)
 
     def fwd_calls(self, plan):
-        sh, lib = self.sh, L.load()
+        sh = self.sh
         B, W, Em = plan.B, sh.world, sh.emb
         F = len(self.tables)
         nfm = sh.nf[sh.rank]
@@ -598,14 +592,10 @@ class ShardedGatherOp(E.Op):
         calls.append((E.PY, self._a2a, (self.recv_idx[:sum(irecv)], self.send_idx[:sum(isend)], irecv, isend),
                       dict(kernel="all_to_all(indices)")))
         if nfm:
-            mine = [self.tables[f] for f in sh.mine]
-            tabs = ops._ptr_array([t.data for t in mine])
-            vocab = (L.i64 * nfm)(*[t.data.shape[0] for t in mine])
-            col = (L.i32 * nfm)(*range(nfm))
-            plan.keep += [tabs, vocab, col]
-            calls.append((lib.mml_gather_fwd, (tabs, vocab, col, nfm, Em, self.recv_idx.data_ptr(), nfm, 0, 0, W * B,
-                                               self.rows_send.data_ptr(), nfm * Em, plan.status.data_ptr()),
-                          dict(kernel="gather_vec4_kernel", bytes=float(W * B) * nfm * (4 + 8 * Em))))
+            # the received indices are a [W * B, nfm] matrix of this rank's fields, the rows sent back [W * B, nfm * E]
+            calls.append(plan.bound(bind.gather_fwd([self.tables[f].data for f in sh.mine], self.recv_idx.view(W * B, nfm),
+                                                    range(nfm), 0, 0, self.rows_send.view(W * B, nfm * Em), plan.status),
+                                    kernel="gather_vec4_kernel", bytes=float(W * B) * nfm * (4 + 8 * Em)))
         calls.append((E.PY, self._a2a, (self.rows_recv[:sum(rrecv)], self.rows_send[:sum(rsend)], rrecv, rsend),
                       dict(kernel="all_to_all(rows)")))
         segs = sh.unpack_row_segments(self.rows_recv, self.out.buf, B)
@@ -615,7 +605,7 @@ class ShardedGatherOp(E.Op):
         return calls
 
     def bwd_calls(self, plan):
-        sh, lib = self.sh, L.load()
+        sh = self.sh
         if self.out.grad is None:
             return []
         B, W, Em = plan.B, sh.world, sh.emb
@@ -632,24 +622,12 @@ class ShardedGatherOp(E.Op):
             mine = [self.tables[f] for f in sh.mine]
             if not all(t.needs_grad for t in mine):
                 raise L.MMLError("sharded tables need gradient accumulators (ParamStore.ensure_table_grads)")
-            gt = ops._ptr_array([t.grad for t in mine])
-            vocab = (L.i64 * nfm)(*[t.data.shape[0] for t in mine])
-            col = (L.i32 * nfm)(*range(nfm))
-            plan.keep += [gt, vocab, col]
             for t in mine:
                 E._claim(t)
-            sr = self.sparse_rows
-            if sr is not None:
-                seen = ops._ptr_array(sr.seen)
-                rb = (L.i64 * (nfm + 1))(*sr.rowbase)
-                plan.keep += [seen, rb]
-                extra = (seen, rb, sr.touched.data_ptr(), sr.count.data_ptr(), sr.touched.numel(), sr.marks.data_ptr())
-            else:
-                extra = (None, None, None, None, 0, None)
-            calls.append((lib.mml_scatter_bwd, (gt, vocab, col, nfm, Em, self.recv_idx.data_ptr(), nfm, W * B,
-                                                self.grad_recv.data_ptr(), nfm * Em) + extra +
-                          (plan.status.data_ptr(),),
-                          dict(kernel=E.scatter_symbol(Em), bytes=float(W * B) * nfm * (4 + 12 * Em), tail=True)))
+            calls.append(plan.bound(bind.scatter_bwd([t.grad for t in mine], self.recv_idx.view(W * B, nfm), range(nfm),
+                                                     self.grad_recv.view(W * B, nfm * Em),
+                                                     bind.rows_args(self.sparse_rows), plan.status),
+                                    kernel=E.scatter_symbol(Em), bytes=float(W * B) * nfm * (4 + 12 * Em), tail=True))
         return calls
 
 

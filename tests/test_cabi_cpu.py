@@ -190,10 +190,6 @@ def ptr(a):
     return a.ctypes.data
 
 
-def ptr_array(arrs):
-    return (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
-
-
 def test_mmoe_training_step_through_the_cpu_cabi_matches_the_reference_golden(cpu):
     lib, L = cpu
     g = load_golden("mmoe_ae30")
@@ -212,8 +208,12 @@ def test_mmoe_training_step_through_the_cpu_cabi_matches_the_reference_golden(cp
     tabs = [P[f"embedding_dict.{n}.weight"] for n in names]
     x0 = f32(B, K0)
     status = np.zeros(1, dtype=np.int32)
-    rc = lib.mml_gather_fwd(ptr_array(tabs), (C.c_int64 * F)(*vocab), (C.c_int32 * F)(*range(F)), F, E, ptr(X), X.shape[1],
-                            0, 0, B, ptr(x0), K0, ptr(status), None)
+    # (the marshalling the package itself uses: mmlrec_amd/bind.py, on host views of the numpy arrays)
+    import torch
+    from mmlrec_amd import bind
+    T_ = torch.from_numpy
+    b = bind.gather_fwd([T_(t) for t in tabs], T_(X), range(F), 0, 0, T_(x0), T_(status))
+    rc = lib.mml_gather_fwd(*b.args, None)
     assert rc == 0 and status[0] == 0
     assert np.array_equal(x0, g["dnn_input"])  # index work: bit-exact
 
@@ -322,8 +322,8 @@ def test_mmoe_training_step_through_the_cpu_cabi_matches_the_reference_golden(cp
             [(dG[t], W_(f"gate_dnn.{t}.linears.0")) for t in range(T)])])
     # ---- K2 scatter
     gt = [np.zeros_like(t) for t in tabs]
-    rc = lib.mml_scatter_bwd(ptr_array(gt), (C.c_int64 * F)(*vocab), (C.c_int32 * F)(*range(F)), F, E, ptr(X), X.shape[1], B,
-                             ptr(dx0), K0, None, None, None, None, 0, None, ptr(status), None)
+    rc = lib.mml_scatter_bwd(*bind.scatter_bwd([T_(t) for t in gt], T_(X), range(F), T_(dx0), bind.rows_args(),
+                                               T_(status)).args, None)
     assert rc == 0
     for n, t in zip(names, gt):
         grads[f"embedding_dict.{n}.weight"] = t
@@ -365,11 +365,10 @@ def test_bf16_storage_family_on_the_cpu_library(cpu):
     idx = torch.stack([torch.randint(0, v, (B,), generator=g) for v in vocab], 1)
     X = idx.float().contiguous()
     x0 = torch.empty(B, F * E, dtype=torch.bfloat16)
-    vs = (L.i64 * F)(*vocab)
-    col = (L.i32 * F)(*range(F))
     status = torch.zeros(1, dtype=torch.int32)
-    assert lib.mml_gather16_fwd(ops._ptr_array(tabs), vs, col, F, E, X.data_ptr(), F, 0, 0, B, x0.data_ptr(), F * E,
-                                status.data_ptr(), None) == 0 and int(status) == 0
+    from mmlrec_amd import bind
+    assert lib.mml_gather16_fwd(*bind.gather16_fwd(tabs, X, range(F), 0, 0, x0, status).args, None) == 0
+    assert int(status) == 0
     ref0 = torch.cat([tabs[f][idx[:, f]] for f in range(F)], 1).to(torch.bfloat16)
     assert torch.equal(x0, ref0)
     W1, b1 = torch.randn(H1, F * E, generator=g) / (F * E) ** 0.5, torch.randn(H1, generator=g) * 0.1
