@@ -1,12 +1,17 @@
-"""The argument order of the row-family entry points (include/mmlrec.h: gather, scatter, index-unique, rows bookkeeping,
-row optimizer), written ONCE per entry point.  A builder takes tensors (or ctypes arrays already built) plus sizes and
-returns Bound(name, args): the C symbol and its positional arguments without the trailing stream.  Two consumers:
-the eager wrappers (ops._issue) and the recorded plans (engine.Plan.bound).  Marshalling only -- no checks, no allocation,
-no device work -- so the builders also run on host tensors (the CPU restatement of the C ABI, tests/test_bind_cpu.py).
+"""The argument order of the C entry points that take four or more positional arguments (include/mmlrec.h), written
+ONCE per entry point: the row family (gather, scatter, index-unique, rows bookkeeping, row optimizer) and the model layer
+(BatchNorm, dropout, APG, SNR, ESMM / ESCM, the element-wise and copy kernels, PCGrad, counters).  A builder takes
+tensors (or ctypes arrays and structures already built) plus sizes and flags and returns Bound(name, args): the C symbol
+and its positional arguments without the trailing stream.  Two consumers: the eager wrappers (ops._issue) and the
+recorded plans (engine.Plan.bound).  Marshalling only -- no checks, no allocation, no device work -- so the builders also
+run on host tensors (the CPU restatement of the C ABI, tests/test_bind_cpu.py, tests/test_bind_model_cpu.py).  Entry points
+whose whole list is (descriptor array, count) or (byref(group), workspace, bytes) are written where they are used.
+A Bound holds ADDRESSES: whoever records one keeps the tensors alive (Plan.bound keeps only the ctypes objects).
 
 Conventions: `tables` = the [V, E] tensors of the fields (their order is the field order), `X` = the [B, ldX] fp32-encoded
 index matrix, `rows` = the bookkeeping tuple of rows_args, `d` = an mml_pool_desc (ops.make_pool_desc), `B` = the rows of
-X to read when not all of them."""
+X to read when not all of them.  Model layer: rows, columns and pitches come from the 2-D views given (`ld`); `ws` = a
+uint8 workspace tensor, which supplies its address and its byte count; `acc` / `accumulate` = add to the output."""
 import collections
 import ctypes as C
 
@@ -17,6 +22,15 @@ Bound = collections.namedtuple("Bound", "name args")
 
 def ld(t):
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def _mat(t):
+    """(address, row pitch) of a 2-D view: how the header passes every matrix; (null, 0) for None."""
+    return (None, 0) if t is None else (t.data_ptr(), ld(t))
+
+
+def _ptrs(*tensors):
+    return tuple(L.ptr(t) for t in tensors)
 
 
 def ptr_array(tensors):
@@ -87,14 +101,10 @@ def gather_fwd_idx32(tables, idx, dense, out, status=None):
                   0 if dense is None else dense.shape[1], idx.shape[0], out.data_ptr(), ld(out), L.ptr(status)))
 
 
-def _ld_or_0(t):
-    return 0 if t is None else ld(t)
-
-
 def gather_pool_fwd(d, X, dense_col0, nd, out, argmax=None, wg=None, n_wg=0, status=None, B=None):
     return Bound("mml_gather_pool_fwd",
-                 (C.byref(d), X.data_ptr(), ld(X), dense_col0, nd, _nrows(X, B), out.data_ptr(), ld(out), L.ptr(argmax),
-                  _ld_or_0(argmax), L.ptr(wg), n_wg, L.ptr(status)))
+                 (C.byref(d), X.data_ptr(), ld(X), dense_col0, nd, _nrows(X, B), out.data_ptr(), ld(out)) + _mat(argmax) +
+                 (L.ptr(wg), n_wg, L.ptr(status)))
 
 
 # ---------------------------------------------------------------------------------------------- scatter
@@ -119,14 +129,14 @@ def scatter_bwd_idx32(grad_tables, idx, d_out, rows, status=None):
 
 def scatter_pool_bwd(d, X, d_out, argmax, rows, status=None, B=None):
     return Bound("mml_scatter_pool_bwd",
-                 (C.byref(d), X.data_ptr(), ld(X), _nrows(X, B), d_out.data_ptr(), ld(d_out), L.ptr(argmax),
-                  _ld_or_0(argmax)) + rows + (L.ptr(status),))
+                 (C.byref(d), X.data_ptr(), ld(X), _nrows(X, B), d_out.data_ptr(), ld(d_out)) + _mat(argmax) + rows +
+                 (L.ptr(status),))
 
 
 def scatter_pool_bwd_det(d, X, d_out, argmax, acc64, amax_slot, marks, flags, status=None, B=None):
     return Bound("mml_scatter_pool_bwd_det",
-                 (C.byref(d), X.data_ptr(), ld(X), _nrows(X, B), d_out.data_ptr(), ld(d_out), L.ptr(argmax),
-                  _ld_or_0(argmax), ptr_array(acc64), amax_slot.data_ptr(), L.ptr(marks), int(flags), L.ptr(status)))
+                 (C.byref(d), X.data_ptr(), ld(X), _nrows(X, B), d_out.data_ptr(), ld(d_out)) + _mat(argmax) +
+                 (ptr_array(acc64), amax_slot.data_ptr(), L.ptr(marks), int(flags), L.ptr(status)))
 
 
 # ---------------------------------------------------------------------------------------------- rows bookkeeping
@@ -156,3 +166,138 @@ def opt_catchup_rows(tables, state1, state2, last, rows, hyper):
     return Bound("mml_opt_catchup_rows",
                  (ptr_array(tables), ptr_array(state1), ptr_array(state2), ptr_array(last), rows[1], len(tables),
                   tables[0].shape[1], rows[2], rows[3], rows[4], C.byref(hyper)))
+
+
+# ---------------------------------------------------------------------------------------------- BatchNorm
+def bn_fwd(x, gamma, beta, running_mean, running_var, batches_tracked, mean, rstd, y, act, training, eps, momentum, ws):
+    return Bound("mml_bn_fwd", _mat(x) + _ptrs(gamma, beta, running_mean, running_var, batches_tracked, mean, rstd) + _mat(y) +
+                 tuple(x.shape) + (int(act), int(training), float(eps), float(momentum), ws.data_ptr(), ws.numel()))
+
+
+def bn_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, acc, ws):
+    return Bound("mml_bn_bwd", _mat(dy) + _mat(x) + _ptrs(gamma, mean, rstd) + _mat(dx) + _ptrs(dgamma, dbeta) +
+                 (int(acc),) + tuple(x.shape) + (ws.data_ptr(), ws.numel()))
+
+
+def domain_bn_update(x, mask, pop_mean, pop_var, decay):
+    """mask: [B, D] one-hot rows; pop_mean / pop_var: [D, n]."""
+    return Bound("mml_domain_bn_update", _mat(x) + _mat(mask) + tuple(x.shape) + (mask.shape[1],) +
+                 _ptrs(pop_mean, pop_var) + (float(decay),))
+
+
+def domain_bn_eval(x, mask, pop_mean, pop_var, y, eps):
+    return Bound("mml_domain_bn_eval", _mat(x) + _mat(mask) + _ptrs(pop_mean, pop_var) + _mat(y) + tuple(x.shape) +
+                 (mask.shape[1], float(eps)))
+
+
+# ---------------------------------------------------------------------------------------------- dropout
+def dropout(x, out, p, seed, site, step_dev, step, accumulate, row0, rows=None):
+    """seed / site: any Python int, cut to the 64 / 32 bits the mask stream takes -- here, once; step_dev: the device
+    step counter (then `step` is not read) or None."""
+    return Bound("mml_dropout", _mat(x) + _mat(out) + (_nrows(x, rows), x.shape[1], int(row0), float(p),
+                                                       int(seed) & ((1 << 64) - 1), int(site) & 0xffffffff,
+                                                       L.ptr(step_dev), int(step), int(accumulate)))
+
+
+# ---------------------------------------------------------------------------------------------- APG
+def apg_features_fwd(o1, s, z, k, E):
+    return Bound("mml_apg_features_fwd", _mat(o1) + _mat(s) + _mat(z) + (o1.shape[0], k, E, z.shape[1]))
+
+
+def apg_features_bwd(dz, s, do1, k, E, acc):
+    return Bound("mml_apg_features_bwd", _mat(dz) + _mat(s) + _mat(do1) + (dz.shape[0], k, E, int(acc)))
+
+
+def apg_weights(Wkk, bkk, Wb, Wcat, k, E, direction, acc=(0, 0, 0)):
+    """direction 0: pack Wcat from the three; 1: unpack (the four are then the gradients), acc = one flag per target.
+    Wcat's pitch is k."""
+    return Bound("mml_apg_weights", _ptrs(Wkk, bkk, Wb, Wcat) + (k, k, E, int(direction)) + tuple(acc))
+
+
+# ---------------------------------------------------------------------------------------------- SNR
+def snr_gate_weights_fwd(u, alpha, M, W, n_blocks, block, zw, beta, gamma, eps):
+    return Bound("mml_snr_gate_weights_fwd", _ptrs(u, alpha, M, W) + (n_blocks, block, zw, float(beta), float(gamma), float(eps)))
+
+
+def snr_gate_weights_bwd(dW, M, u, alpha, du, dalpha, acc_u, acc_alpha, n_blocks, block, zw, beta, gamma, eps, scratch):
+    """du: None for a frozen u; scratch: n_blocks floats."""
+    return Bound("mml_snr_gate_weights_bwd", _ptrs(dW, M, u, alpha, du, dalpha) + (int(acc_u), int(acc_alpha), n_blocks, block,
+                                                                                   zw, float(beta), float(gamma), float(eps),
+                                                                                   scratch.data_ptr()))
+
+
+# ---------------------------------------------------------------------------------------------- ESMM / ESCM
+def _combine(name, raw, y, dout, prob, draw, loss, B, tail=()):
+    return Bound(name, _mat(raw) + _mat(y) + _mat(dout) + _mat(prob) + _mat(draw) + (L.ptr(loss), B) + tail)
+
+
+def esmm_combine(raw, y, dout, prob, draw, loss, B):
+    """y / dout / draw / loss: None for what the pass does not read or write."""
+    return _combine("mml_esmm_combine", raw, y, dout, prob, draw, loss, B)
+
+
+def escm_combine(raw, y, dout, prob, draw, loss, B, cf_w, global_w):
+    return _combine("mml_escm_combine", raw, y, dout, prob, draw, loss, B, (float(cf_w), float(global_w)))
+
+
+# ---------------------------------------------------------------------------------------------- element-wise
+def ew_mul(a, b, out):
+    return Bound("mml_ew_mul", _ptrs(a, b, out) + (out.numel(),))
+
+
+def ew_mul_bwd(dout, a, b, da, db, acc_a, acc_b):
+    return Bound("mml_ew_mul_bwd", _ptrs(dout, a, b, da, db) + (int(acc_a), int(acc_b), dout.numel()))
+
+
+def ew_mul_bwd_act(dout, a, b, da, db, acc_a, acc_b, act_a, act_b):
+    return Bound("mml_ew_mul_bwd_act", ew_mul_bwd(dout, a, b, da, db, acc_a, acc_b).args + (int(act_a), int(act_b)))
+
+
+def ew_add_n(inputs, out, n=None):
+    """n: the flat extent when it is not out's own (rows of a padded pitch); likewise act_bwd."""
+    arr = ptr_array(inputs)
+    return Bound("mml_ew_add_n", (arr, len(arr), out.data_ptr(), out.numel() if n is None else n))
+
+
+def act_bwd(y, dy, dst, act, n=None):
+    return Bound("mml_act_bwd", _ptrs(y, dy, dst) + (y.numel() if n is None else n, int(act)))
+
+
+def copy2d(src, dst, accumulate):
+    """dst (+)= src over src's [rows, cols].  (passes.merge_copies reads this layout positionally.)"""
+    return Bound("mml_copy2d", _mat(src) + _mat(dst) + tuple(src.shape) + (int(accumulate),))
+
+
+def copy_flat(src, dst, accumulate, n=None):
+    """The same entry point over n contiguous elements of tensors of any rank: one row of n columns."""
+    n = src.numel() if n is None else n
+    return Bound("mml_copy2d", (src.data_ptr(), n, dst.data_ptr(), n, 1, n, int(accumulate)))
+
+
+# ---------------------------------------------------------------------------------------------- PCGrad
+def pcgrad_gram(arr, n, T, gram, ws):
+    """arr: an mml_pcgrad_seg array (ops.make_pcgrad_segs) of n segments."""
+    return Bound("mml_pcgrad_gram", (arr, n, T, gram.data_ptr(), ws.data_ptr(), ws.numel()))
+
+
+def pcgrad_weights(gram, order, T, w, fired):
+    return Bound("mml_pcgrad_weights", _ptrs(gram, order) + (T,) + _ptrs(w, fired))
+
+
+def pcgrad_combine(arr, n, T, w):
+    return Bound("mml_pcgrad_combine", (arr, n, T, w.data_ptr()))
+
+
+def pcgrad_stash(arr, n, tables):
+    """tables: the segments are table gradients -- the rows copied are zeroed behind the copy (the header's `clear`)."""
+    return Bound("mml_pcgrad_stash", (arr, n, int(tables)))
+
+
+# ---------------------------------------------------------------------------------------------- counters
+def counter_update(counter, delta, reset):
+    return Bound("mml_counter_update", (counter.data_ptr(), int(delta), int(reset)))
+
+
+def amax_reset(pool, n):
+    """Zero the first n magnitude slots of the pool."""
+    return Bound("mml_amax_reset", (pool.data_ptr(), int(n)))

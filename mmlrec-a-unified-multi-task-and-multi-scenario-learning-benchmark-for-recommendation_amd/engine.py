@@ -213,6 +213,12 @@ class Plan:
         self.keep.append(t)
         return t
 
+    def workspace(self, nbytes, least=4):
+        """A kept uint8 buffer of max(nbytes, least) bytes: the workspace of ONE recorded call (never the shared scratch)."""
+        ws = torch.empty(max(int(nbytes), least), dtype=torch.uint8, device=self.device)
+        self.keep.append(ws)
+        return ws
+
     def bound(self, b, **meta):
         """The call-list entry (fn, args, meta) of a bind.Bound; the ctypes arrays and descriptors among its arguments
         are kept alive with the plan."""
@@ -545,8 +551,7 @@ class Plan:
                 if isinstance(v, Val) and v.grad is not None and v.act != L.ACT_NONE and not v.deriv_applied:
                     if v.is16 or v.grad.dtype != torch.float32:
                         raise L.MMLError(f"bf16 value {v.name!r}: its activation derivative must fold into its one consumer")
-                    self.bwd.append((L.load().mml_act_bwd, (v.buf.data_ptr(), v.grad.data_ptr(), v.grad.data_ptr(),
-                                                            self._flat_numel(v), v.act)))
+                    self.bwd.append(self.bound(bind.act_bwd(v.buf, v.grad, v.grad, v.act, n=self._flat_numel(v))))
                     v.deriv_applied = True
             mine = []
             for c in op.bwd_calls(self):
@@ -1249,10 +1254,8 @@ class LinearGroupOp(Op):
                 dA=dst, Y=None, act=L.ACT_NONE, mask=None, accumulate=acc if dst is g0 else 0,
                 srcs=[(q["out"].grad, cut(q["Wp"] if padded else q["W"].data), q.get("w_kn", 0),
                        q["amax_dc"], q["amax_w"]) for q in part]))
-        arr = ops._ptr_array([x.grad] + [t_ for t_ in targets[1:]])
-        plan.keep.append(arr)
-        return (L.load().mml_ew_add_n, (arr, len(targets), x.grad.data_ptr(), plan.B * pitch),
-                dict(kernel="ew_add_n_kernel", bytes=4.0 * plan.B * pitch * (len(targets) + 1)))
+        return plan.bound(bind.ew_add_n([x.grad] + targets[1:], x.grad, n=plan.B * pitch),
+                          kernel="ew_add_n_kernel", bytes=4.0 * plan.B * pitch * (len(targets) + 1))
 
     def _dgrad_chunked(self, plan, x, qs, waves):
         """The plain problem: the layers that read x in chunks of MAX_SRC sources, chunk k in launch k."""
@@ -1453,7 +1456,6 @@ class HeadOp(Op):
             plan.prob = plan.empty(plan.B, T)
         prob_buf, dprob_buf = self._prob_buffers(plan, use_dprob)
         hl, post = [], []
-        lib = L.load()
         for t, h in enumerate(self.heads):
             Hin = h["Hin"]
             q = dict(Hin=Hin.buf, w=h["w"].data, bias=h["bias"].data,
@@ -1493,15 +1495,14 @@ class HeadOp(Op):
                     plan.grad_of(Hin)
                     acc = _claim(Hin) if claim else h["_acc"]
                     h["_acc"] = acc
-                    post.append((lib.mml_copy2d, (tmp.data_ptr(), ops._ld(tmp), Hin.grad.data_ptr(), ops._ld(Hin.grad),
-                                                  plan.B, Hin.n, acc)))
+                    post.append(plan.bound(bind.copy2d(tmp, Hin.grad, acc)))
                 if claim:
                     h["_acc_w"] = _claim(h["w"])
                     h["_acc_b"] = _claim(h["bias"])
                 if h["_acc_b"]:  # a bias shared by several heads (reference model/esmm.py:55-56: one PredictionLayer)
                     tmpb = h.setdefault("_db_tmp", plan.empty(1))
                     q["dbias"] = tmpb
-                    post.append((lib.mml_copy2d, (tmpb.data_ptr(), 1, h["bias"].grad.data_ptr(), 1, 1, 1, 1)))
+                    post.append(plan.bound(bind.copy_flat(tmpb, h["bias"].grad, 1)))
                 else:
                     q["dbias"] = h["bias"].grad
                 if h["_acc_w"]:
@@ -1509,15 +1510,14 @@ class HeadOp(Op):
                     # scratch row that is added to the parameter's gradient after the launch
                     tmpw = h.setdefault("_dw_tmp", plan.empty(h["w"].data.numel()))
                     q["dw"] = tmpw
-                    n = tmpw.numel()
-                    post.append((lib.mml_copy2d, (tmpw.data_ptr(), n, h["w"].grad.data_ptr(), n, 1, n, 1)))
+                    post.append(plan.bound(bind.copy_flat(tmpw, h["w"].grad, 1)))
                 else:
                     q["dw"] = h["w"].grad
                 b2 = h.get("bias2")
                 if b2 is not None and b2.needs_grad:
                     acc = _claim(b2) if claim else h["_acc_b2"]
                     h["_acc_b2"] = acc
-                    post.append((lib.mml_copy2d, (h["bias"].grad.data_ptr(), 1, b2.grad.data_ptr(), 1, 1, 1, acc)))
+                    post.append(plan.bound(bind.copy_flat(h["bias"].grad, b2.grad, acc, n=1)))
             hl.append(q)
         grp = ops.make_head_group(hl, prob_buf, y=plan.y if (train and not use_dprob) else None, mask=plan.mask,
                                   loss=plan.loss if (train and not use_dprob) else None,
@@ -1578,16 +1578,12 @@ class EsmmHeadOp(HeadOp):
             self._draw = plan.empty(plan.B, 2)
         return self._raw, self._draw
 
-    def _fn_extra(self):
-        return L.load().mml_esmm_combine, ()
+    def _bind(self, *a):
+        return bind.esmm_combine(*a)
 
     def _combine(self, plan, y, dout, draw, loss):
-        fn, extra = self._fn_extra()
-        return (fn,
-                (self._raw.data_ptr(), 2, L.ptr(y), 2 if y is not None else 0, L.ptr(dout),
-                 ops._ld(dout) if dout is not None else 0, plan.prob.data_ptr(), ops._ld(plan.prob), L.ptr(draw),
-                 2 if draw is not None else 0, L.ptr(loss), plan.B) + extra,
-                dict(kernel=self.KERNEL, bytes=4.0 * plan.B * 8))
+        return plan.bound(self._bind(self._raw, y, dout, plan.prob, draw, loss, plan.B),
+                          kernel=self.KERNEL, bytes=4.0 * plan.B * 8)
 
     def infer_calls(self, plan):
         calls = super().infer_calls(plan)
@@ -1624,8 +1620,8 @@ class EscmHeadOp(EsmmHeadOp):
         super().__init__(heads, mask_cols)
         self.cf_w, self.global_w = float(cf_w), float(global_w)
 
-    def _fn_extra(self):
-        return L.load().mml_escm_combine, (self.cf_w, self.global_w)
+    def _bind(self, *a):
+        return bind.escm_combine(*a, self.cf_w, self.global_w)
 
 
 class BNOp(Op):
@@ -1644,24 +1640,15 @@ class BNOp(Op):
     def outputs(self):
         return [self.y]
 
-    def _ws(self, plan):
-        nbytes = int(L.load().mml_bn_workspace_bytes(plan.B, self.z.n))
-        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=plan.device)
-        plan.keep.append(ws)
-        return ws
-
     def fwd_calls(self, plan):
         n = self.z.n
         self.mean, self.rstd = plan.empty(n), plan.empty(n)
-        ws = self._ws(plan)
         m = self.m
-        return [(L.load().mml_bn_fwd,
-                 (self.z.buf.data_ptr(), ops._ld(self.z.buf), self.gamma.data.data_ptr(), self.beta.data.data_ptr(),
-                  m.running_mean.data_ptr(), m.running_var.data_ptr(), m.num_batches_tracked.data_ptr(),
-                  self.mean.data_ptr(), self.rstd.data_ptr(), self.y.buf.data_ptr(), ops._ld(self.y.buf), plan.B, n,
-                  self.y.act, int(getattr(plan, "bn_training", plan.training)), self.EPS, self.MOMENTUM, ws.data_ptr(),
-                  ws.numel()),
-                 dict(kernel="bn_fwd", bytes=4.0 * plan.B * n * 3))]
+        return [plan.bound(bind.bn_fwd(self.z.buf, self.gamma.data, self.beta.data, m.running_mean, m.running_var,
+                                       m.num_batches_tracked, self.mean, self.rstd, self.y.buf, self.y.act,
+                                       getattr(plan, "bn_training", plan.training), self.EPS, self.MOMENTUM,
+                                       plan.workspace(L.load().mml_bn_workspace_bytes(plan.B, n))),
+                           kernel="bn_fwd", bytes=4.0 * plan.B * n * 3)]
 
     def bwd_calls(self, plan):
         if self.y.grad is None:
@@ -1673,14 +1660,11 @@ class BNOp(Op):
         acc = _claim(self.gamma)
         if _claim(self.beta) != acc:
             raise L.MMLError("BatchNorm weight and bias must be written in the same order")
-        ws = self._ws(plan)
         n = self.z.n
-        return [(L.load().mml_bn_bwd,
-                 (self.y.grad.data_ptr(), ops._ld(self.y.grad), self.z.buf.data_ptr(), ops._ld(self.z.buf),
-                  self.gamma.data.data_ptr(), self.mean.data_ptr(), self.rstd.data_ptr(), self.z.grad.data_ptr(),
-                  ops._ld(self.z.grad), self.gamma.grad.data_ptr(), self.beta.grad.data_ptr(), acc, plan.B, n,
-                  ws.data_ptr(), ws.numel()),
-                 dict(kernel="bn_bwd", bytes=4.0 * plan.B * n * 5))]
+        return [plan.bound(bind.bn_bwd(self.y.grad, self.z.buf, self.gamma.data, self.mean, self.rstd, self.z.grad,
+                                       self.gamma.grad, self.beta.grad, acc,
+                                       plan.workspace(L.load().mml_bn_workspace_bytes(plan.B, n))),
+                           kernel="bn_bwd", bytes=4.0 * plan.B * n * 5)]
 
 
 class DropoutOp(Op):
@@ -1690,7 +1674,7 @@ class DropoutOp(Op):
     step counter the forward read -- the optimizer's device counter, bumped at the start of a fused step."""
 
     def __init__(self, x, y, p, seed, site):
-        self.x, self.y, self.p, self.seed, self.site = x, y, float(p), int(seed) & ((1 << 64) - 1), int(site) & 0xffffffff
+        self.x, self.y, self.p, self.seed, self.site = x, y, float(p), seed, site  # (bind.dropout cuts seed / site to size)
 
     def inputs(self):
         return [self.x]
@@ -1699,10 +1683,8 @@ class DropoutOp(Op):
         return [self.y]
 
     def _call(self, plan, src, dst, acc):
-        return (L.load().mml_dropout,
-                (src.data_ptr(), ops._ld(src), dst.data_ptr(), ops._ld(dst), plan.B, self.x.n, plan.row0, self.p, self.seed,
-                 self.site, plan.step_dev.data_ptr(), 0, int(acc)),
-                dict(kernel="dropout_kernel", bytes=4.0 * plan.B * self.x.n * (3 if acc else 2)))
+        return plan.bound(bind.dropout(src, dst, self.p, self.seed, self.site, plan.step_dev, 0, acc, plan.row0, rows=plan.B),
+                          kernel="dropout_kernel", bytes=4.0 * plan.B * self.x.n * (3 if acc else 2))
 
     def fwd_calls(self, plan):
         return [self._call(plan, self.x.buf, self.y.buf, 0)]
@@ -1766,9 +1748,8 @@ class PReluBatchOp(Op):
         for ch in ops.prelu_chunks(rows):
             arr = ops.make_prelu_bwd_descs(ch, seen)
             seen.update(d.dalpha for d in arr)
-            nbytes = int(L.load().mml_prelu_workspace_bytes(len(ch)))
-            ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=plan.device)
-            plan.keep += [arr, ws]
+            ws = plan.workspace(L.load().mml_prelu_workspace_bytes(len(ch)))
+            plan.keep.append(arr)
             calls.append((L.load().mml_prelu_batch_bwd, (arr, len(ch), ws.data_ptr(), ws.numel()),
                           dict(kernel="prelu_bwd_kernel", bytes=sum((16.0 if r["acc_dz"] else 12.0) * r["z"].numel()
                                                                     for r in ch))))
@@ -1802,34 +1783,22 @@ class DomainBNOp(Op):
     def outputs(self):
         return [self.y]
 
-    def _ws(self, plan):
-        nbytes = int(L.load().mml_bn_workspace_bytes(plan.B, self.x.n))
-        ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=plan.device)
-        plan.keep.append(ws)
-        return ws
-
     def fwd_calls(self, plan):
-        lib, n, D = L.load(), self.x.n, self.mask.shape[1]
+        n, D = self.x.n, self.mask.shape[1]
         pm, pv = self.m.population(plan.device)
         if pm.shape != (D, n):
             raise L.MMLError(f"DomainBatchNorm holds {tuple(pm.shape)} statistics, the mask has {D} domains")
         x, y = self.x.buf, self.y.buf
         if not getattr(plan, "bn_training", plan.training):
-            return [(lib.mml_domain_bn_eval, (x.data_ptr(), ops._ld(x), self.mask.data_ptr(), ops._ld(self.mask),
-                                              pm.data_ptr(), pv.data_ptr(), y.data_ptr(), ops._ld(y), plan.B, n, D,
-                                              self.EPS), dict(kernel="domain_bn_eval_kernel"))]
+            return [plan.bound(bind.domain_bn_eval(x, self.mask, pm, pv, y, self.EPS), kernel="domain_bn_eval_kernel")]
         self.ones, self.zeros = torch.ones(n, device=plan.device), torch.zeros(n, device=plan.device)
         self.mean, self.rstd = plan.empty(n), plan.empty(n)
         self.scratch = [plan.zeros(n), plan.zeros(n), plan.zeros(1, dtype=torch.int64)]  # F.batch_norm's discarded running stats
-        ws = self._ws(plan)
         plan.keep += [self.ones, self.zeros]
-        return [(lib.mml_domain_bn_update, (x.data_ptr(), ops._ld(x), self.mask.data_ptr(), ops._ld(self.mask), plan.B, n,
-                                            D, pm.data_ptr(), pv.data_ptr(), self.DECAY),
-                 dict(kernel="domain_bn_update_kernel")),
-                (lib.mml_bn_fwd, (x.data_ptr(), ops._ld(x), self.ones.data_ptr(), self.zeros.data_ptr(),
-                                  self.scratch[0].data_ptr(), self.scratch[1].data_ptr(), self.scratch[2].data_ptr(),
-                                  self.mean.data_ptr(), self.rstd.data_ptr(), y.data_ptr(), ops._ld(y), plan.B, n,
-                                  L.ACT_NONE, 1, self.EPS, 0.1, ws.data_ptr(), ws.numel()), dict(kernel="bn_fwd"))]
+        return [plan.bound(bind.domain_bn_update(x, self.mask, pm, pv, self.DECAY), kernel="domain_bn_update_kernel"),
+                plan.bound(bind.bn_fwd(x, self.ones, self.zeros, *self.scratch, self.mean, self.rstd, y, L.ACT_NONE, 1,
+                                       self.EPS, 0.1, plan.workspace(L.load().mml_bn_workspace_bytes(plan.B, n))),
+                           kernel="bn_fwd")]
 
     def bwd_calls(self, plan):
         if self.y.grad is None:
@@ -1840,13 +1809,9 @@ class DomainBNOp(Op):
         if _claim(self.x):
             raise NotImplementedError("DomainBatchNorm input with another consumer")
         n = self.x.n
-        dscr = plan.empty(2 * n)
-        ws = self._ws(plan)
-        return [(L.load().mml_bn_bwd,
-                 (self.y.grad.data_ptr(), ops._ld(self.y.grad), self.x.buf.data_ptr(), ops._ld(self.x.buf),
-                  self.ones.data_ptr(), self.mean.data_ptr(), self.rstd.data_ptr(), self.x.grad.data_ptr(),
-                  ops._ld(self.x.grad), dscr.data_ptr(), dscr[n:].data_ptr(), 0, plan.B, n, ws.data_ptr(), ws.numel()),
-                 dict(kernel="bn_bwd"))]
+        dscr = plan.empty(2 * n)  # (dgamma, dbeta of the constant gamma / beta: discarded)
+        return [plan.bound(bind.bn_bwd(self.y.grad, self.x.buf, self.ones, self.mean, self.rstd, self.x.grad, dscr, dscr[n:],
+                                       0, plan.workspace(L.load().mml_bn_workspace_bytes(plan.B, n))), kernel="bn_bwd")]
 
 
 class ApgFeatOp(Op):
@@ -1864,10 +1829,8 @@ class ApgFeatOp(Op):
         return [self.z]
 
     def fwd_calls(self, plan):
-        o1, z = self.o1.buf, self.z.buf
-        return [(L.load().mml_apg_features_fwd, (o1.data_ptr(), ops._ld(o1), self.s.data_ptr(), ops._ld(self.s),
-                                                 z.data_ptr(), ops._ld(z), plan.B, self.k, self.E, self.z.n),
-                 dict(kernel="apg_features_fwd_kernel", bytes=4.0 * plan.B * (self.z.n + self.k + self.E)))]
+        return [plan.bound(bind.apg_features_fwd(self.o1.buf, self.s, self.z.buf, self.k, self.E),
+                           kernel="apg_features_fwd_kernel", bytes=4.0 * plan.B * (self.z.n + self.k + self.E))]
 
     def bwd_calls(self, plan):
         if self.z.grad is None or not self.o1.needs_grad:
@@ -1876,10 +1839,8 @@ class ApgFeatOp(Op):
             raise NotImplementedError("ApgFeatOp input must be a plain linear output")
         do1 = plan.grad_of(self.o1)
         acc = _claim(self.o1)
-        dz = self.z.grad
-        return [(L.load().mml_apg_features_bwd, (dz.data_ptr(), ops._ld(dz), self.s.data_ptr(), ops._ld(self.s),
-                                                 do1.data_ptr(), ops._ld(do1), plan.B, self.k, self.E, acc),
-                 dict(kernel="apg_features_bwd_kernel", bytes=4.0 * plan.B * (self.z.n + self.k + self.E)))]
+        return [plan.bound(bind.apg_features_bwd(self.z.grad, self.s, do1, self.k, self.E, acc),
+                           kernel="apg_features_bwd_kernel", bytes=4.0 * plan.B * (self.z.n + self.k + self.E))]
 
 
 class ApgWeightsOp(Op):
@@ -1891,17 +1852,15 @@ class ApgWeightsOp(Op):
         self.Wkk, self.bkk, self.Wb, self.Wcat, self.k, self.E = Wkk, bkk, Wb, Wcat, k, E
 
     def fwd_calls(self, plan):
-        return [(L.load().mml_apg_weights, (self.Wkk.data.data_ptr(), self.bkk.data.data_ptr(), self.Wb.data.data_ptr(),
-                                            self.Wcat.data.data_ptr(), self.k, self.k, self.E, 0, 0, 0, 0),
-                 dict(kernel="apg_weights_kernel"))]
+        return [plan.bound(bind.apg_weights(self.Wkk.data, self.bkk.data, self.Wb.data, self.Wcat.data, self.k, self.E, 0),
+                           kernel="apg_weights_kernel")]
 
     def bwd_calls(self, plan):
         if not self.Wcat.written:
             return []
-        a, b, c = _claim(self.Wkk), _claim(self.bkk), _claim(self.Wb)
-        return [(L.load().mml_apg_weights, (self.Wkk.grad.data_ptr(), self.bkk.grad.data_ptr(), self.Wb.grad.data_ptr(),
-                                            self.Wcat.grad.data_ptr(), self.k, self.k, self.E, 1, a, b, c),
-                 dict(kernel="apg_weights_kernel", side=True))]
+        acc = (_claim(self.Wkk), _claim(self.bkk), _claim(self.Wb))
+        return [plan.bound(bind.apg_weights(self.Wkk.grad, self.bkk.grad, self.Wb.grad, self.Wcat.grad, self.k, self.E, 1,
+                                            acc), kernel="apg_weights_kernel", side=True)]
 
 
 class Attn2Op(Op):
@@ -1916,36 +1875,26 @@ class Attn2Op(Op):
     def outputs(self):
         return [self.out]
 
-    def _desc(self, plan):
-        d = L.Attn2Desc()
-        for t, (V, K, Q) in enumerate(self.tokens):
-            d.V[t], d.K[t], d.Q[t] = V.buf.data_ptr(), K.buf.data_ptr(), Q.buf.data_ptr()
-            d.ldv[t], d.ldk[t], d.ldq[t] = ops._ld(V.buf), ops._ld(K.buf), ops._ld(Q.buf)
-        d.out, d.ldo = self.out.buf.data_ptr(), ops._ld(self.out.buf)
-        d.A = self.A.data_ptr()
-        d.B, d.H, d.sqrt_h = plan.B, self.out.n, self.sqrt_h
+    def _desc(self, plan, grads=None):
+        d = ops.make_attn2_desc([[v.buf for v in tok] for tok in self.tokens], self.out.buf, self.A, plan.B, self.out.n,
+                                self.sqrt_h, grads)
+        plan.keep.append(d)
         return d
 
     def fwd_calls(self, plan):
         self.A = plan.empty(plan.B, 2)
         d = self._desc(plan)
-        plan.keep.append(d)
         return [(L.load().mml_attn2_fwd, (C.byref(d),), dict(kernel="attn2_fwd_kernel", bytes=4.0 * plan.B * 7 * self.out.n))]
 
     def bwd_calls(self, plan):
         if self.out.grad is None:
             return []
-        d = self._desc(plan)
-        d.dout, d.lddo = self.out.grad.data_ptr(), ops._ld(self.out.grad)
-        for t, (V, K, Q) in enumerate(self.tokens):
-            for v in (V, K, Q):
-                if v.act != L.ACT_NONE or len(v.consumers) != 1:
-                    raise NotImplementedError("Attn2Op inputs must be plain linear outputs with this op as sole consumer")
-                plan.grad_of(v)
-                _claim(v)
-            d.dV[t], d.dK[t], d.dQ[t] = V.grad.data_ptr(), K.grad.data_ptr(), Q.grad.data_ptr()
-            d.lddv[t], d.lddk[t], d.lddq[t] = ops._ld(V.grad), ops._ld(K.grad), ops._ld(Q.grad)
-        plan.keep.append(d)
+        for v in self.inputs():
+            if v.act != L.ACT_NONE or len(v.consumers) != 1:
+                raise NotImplementedError("Attn2Op inputs must be plain linear outputs with this op as sole consumer")
+            plan.grad_of(v)
+            _claim(v)
+        d = self._desc(plan, (self.out.grad, [[v.grad for v in tok] for tok in self.tokens]))
         return [(L.load().mml_attn2_bwd, (C.byref(d),), dict(kernel="attn2_bwd_kernel", bytes=4.0 * plan.B * 14 * self.out.n))]
 
 
@@ -2058,16 +2007,7 @@ class MulBatchOp(Op):
 
     @staticmethod
     def _descs(plan, rows):
-        arr = (L.SumProdDesc * len(rows))()
-        for d, row in zip(arr, rows):
-            out, n, terms, acc, act, deriv_of = row[:6]
-            if len(terms) > 8:
-                raise NotImplementedError("more than 8 products share one operand")
-            d.out, d.n, d.n_terms, d.accumulate = out.data_ptr(), n, len(terms), int(acc)
-            d.amax_out = L.ptr(row[6]) if len(row) > 6 else None
-            d.act, d.deriv_of = int(act), (deriv_of.data_ptr() if act != L.ACT_NONE else None)
-            for k, (x, y) in enumerate(terms):
-                d.x[k], d.y[k] = x.data_ptr(), y.data_ptr()
+        arr = ops.make_sumprod_descs(rows, "more than 8 products share one operand")
         plan.keep.append(arr)
         return arr
 
@@ -2127,8 +2067,7 @@ class CopyColsOp(Op):
             # round 6: the copy raises the magnitude slot of the operand it assembles (mml_copy2d_desc.amax_out) -- PepNet's
             # two gate inputs cost a pass of mml_amax_batch each (17-20 us of a 1.67 ms step) right behind their copies
             return [_copy2d_batch_call(plan, [(self.src, self.dst)], amax=[self.amax_out])]
-        return [(L.load().mml_copy2d, (self.src.data_ptr(), ops._ld(self.src), self.dst.data_ptr(), ops._ld(self.dst),
-                                       plan.B, self.src.shape[1], 0))]
+        return [plan.bound(bind.copy2d(self.src, self.dst, 0))]
 
 
 class SumProdBatchOp(Op):
@@ -2142,15 +2081,12 @@ class SumProdBatchOp(Op):
 
     @staticmethod
     def _descs(plan, rows):
-        arr = (L.SumProdDesc * len(rows))()
-        for d, (out, terms, acc) in zip(arr, rows):
-            if len(terms) > 8:
-                raise NotImplementedError("more than 8 terms in one derived-parameter sum")
-            d.out, d.n, d.n_terms, d.accumulate = out.data_ptr(), out.numel(), len(terms), int(acc)
-            for k, (x, y) in enumerate(terms):
-                if x.numel() != out.numel() or (y is not None and y.numel() != out.numel()):
-                    raise L.MMLError("SumProdBatchOp: operand size mismatch")
-                d.x[k], d.y[k] = x.data_ptr(), (y.data_ptr() if y is not None else None)
+        """rows: (out, [(x, y or None), ...], accumulate) over whole tensors of one size."""
+        for out, terms, _ in rows:
+            if any(t.numel() != out.numel() for xy in terms for t in xy if t is not None):
+                raise L.MMLError("SumProdBatchOp: operand size mismatch")
+        arr = ops.make_sumprod_descs([(out, out.numel(), terms, acc, L.ACT_NONE, None) for out, terms, acc in rows],
+                                     "more than 8 terms in one derived-parameter sum")
         plan.keep.append(arr)
         return arr
 
@@ -2194,22 +2130,20 @@ class SnrWeightsOp(Op):
             raise L.MMLError("SnrWeightsOp: u must hold one coefficient per block or per block column")
 
     def fwd_calls(self, plan):
-        return [(L.load().mml_snr_gate_weights_fwd,
-                 (self.u_data.data_ptr(), self.alpha.data.data_ptr(), self.M.data_ptr(), self.W.data_ptr(),
-                  self.n_blocks, self.block, self.zw, self.BETA, self.GAMMA, self.EPS),
-                 dict(kernel="snr_weights_fwd_kernel", bytes=8.0 * self.W.numel()))]
+        return [plan.bound(bind.snr_gate_weights_fwd(self.u_data, self.alpha.data, self.M, self.W, self.n_blocks,
+                                                     self.block, self.zw, self.BETA, self.GAMMA, self.EPS),
+                           kernel="snr_weights_fwd_kernel", bytes=8.0 * self.W.numel())]
 
     def bwd_calls(self, plan):
         if not any(v.written for v in self.views):
             return []
         if not all(v.written for v in self.views):
             raise L.MMLError("SnrWeightsOp: every routing weight needs its gradient")
-        du, acc_u = (self.u.grad.data_ptr(), _claim(self.u)) if self.u_learned else (None, 0)
-        return [(L.load().mml_snr_gate_weights_bwd,
-                 (self.dW.data_ptr(), self.M.data_ptr(), self.u_data.data_ptr(), self.alpha.data.data_ptr(), du,
-                  self.alpha.grad.data_ptr(), acc_u, _claim(self.alpha), self.n_blocks, self.block, self.zw, self.BETA,
-                  self.GAMMA, self.EPS, plan.empty(self.n_blocks).data_ptr()),
-                 dict(kernel="snr_weights_bwd_kernel", bytes=8.0 * self.W.numel(), side=True))]
+        du, acc_u = (self.u.grad, _claim(self.u)) if self.u_learned else (None, 0)
+        return [plan.bound(bind.snr_gate_weights_bwd(self.dW, self.M, self.u_data, self.alpha.data, du, self.alpha.grad,
+                                                     acc_u, _claim(self.alpha), self.n_blocks, self.block, self.zw,
+                                                     self.BETA, self.GAMMA, self.EPS, plan.empty(self.n_blocks)),
+                           kernel="snr_weights_bwd_kernel", bytes=8.0 * self.W.numel(), side=True)]
 
 
 class PAddOp(Op):
@@ -2219,20 +2153,13 @@ class PAddOp(Op):
         self.ins, self.out = ins, out
 
     def fwd_calls(self, plan):
-        arr = ops._ptr_array([p.data for p in self.ins])
-        plan.keep.append(arr)
-        return [(L.load().mml_ew_add_n, (arr, len(self.ins), self.out.data.data_ptr(), self.out.data.numel()))]
+        return [plan.bound(bind.ew_add_n([p.data for p in self.ins], self.out.data))]
 
     def bwd_calls(self, plan):
         if not self.out.written:
             return []
-        calls = []
-        n = self.out.data.numel()
-        for p in self.ins:
-            if p.needs_grad:
-                calls.append((L.load().mml_copy2d, (self.out.grad.data_ptr(), n, p.grad.data_ptr(), n, 1, n, _claim(p)),
-                              dict(kernel="copy2d_kernel", side=True)))
-        return calls
+        return [plan.bound(bind.copy_flat(self.out.grad, p.grad, _claim(p), n=self.out.data.numel()),
+                           kernel="copy2d_kernel", side=True) for p in self.ins if p.needs_grad]
 
 
 # ---- PCGrad per-task step (reference model/optimizer.py:10-138; trainer.PCGradSchedule) --------------------------------

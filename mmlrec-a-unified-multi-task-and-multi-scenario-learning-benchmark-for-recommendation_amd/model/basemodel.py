@@ -19,6 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
+from .. import bind
 from .. import engine as E
 from .. import optimizer as O
 from .. import ops
@@ -413,11 +414,9 @@ class BaseModel(nn.Module):
             # move it -- every forward would draw the SAME dropout mask.  The forward bumps it first; the
             # backward of that forward regenerates the mask from the same value.
             own = plan.shared_step_dev
-            plan.prepend([(L.load().mml_counter_update, (own.data_ptr(), 1, 0),
-                           dict(kernel="mml_counter_update", bytes=4.0)),
+            plan.prepend([plan.bound(bind.counter_update(own, 1, False), kernel="mml_counter_update", bytes=4.0),
                           # (a 4-byte copy: the kernel moves the word's bits unchanged)
-                          (L.load().mml_copy2d, (own.data_ptr(), 1, plan.step_dev.data_ptr(), 1, 1, 1, 0),
-                           dict(kernel="copy2d_kernel", bytes=8.0))])
+                          plan.bound(bind.copy_flat(own, plan.step_dev, False), kernel="copy2d_kernel", bytes=8.0)])
         return plan
 
     def _maybe_deterministic(self, gop, store, tables, training, E_dim):

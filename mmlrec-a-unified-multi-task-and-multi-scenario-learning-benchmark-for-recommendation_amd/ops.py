@@ -753,32 +753,62 @@ def rows_phase1_then_batched_reduce(head_groups, gate_groups, device):
 
 # ---------------------------------------------------------------------------------------------- K6/K7
 def ew_mul(a, b, out):
-    L.check(L.load().mml_ew_mul(a.data_ptr(), b.data_ptr(), out.data_ptr(), out.numel(), _stream()), "mml_ew_mul")
+    _issue(bind.ew_mul(a, b, out))
 
 
 def ew_mul_bwd(dout, a, b, da=None, db=None, acc_a=False, acc_b=False):
-    L.check(L.load().mml_ew_mul_bwd(dout.data_ptr(), L.ptr(a), L.ptr(b), L.ptr(da), L.ptr(db), int(acc_a), int(acc_b),
-                                    dout.numel(), _stream()), "mml_ew_mul_bwd")
+    _issue(bind.ew_mul_bwd(dout, a, b, da, db, acc_a, acc_b))
 
 
 def ew_add_n(inputs, out):
-    L.check(L.load().mml_ew_add_n(_ptr_array(inputs), len(inputs), out.data_ptr(), out.numel(), _stream()),
-            "mml_ew_add_n")
+    _issue(bind.ew_add_n(inputs, out))
 
 
 def dropout(x, out, p, seed, site=0, step=0, step_dev=None, accumulate=False, row0=0):
     """out (+)= x * keep / (1 - p) on [rows, cols] views (row pitches may differ; out may be x); the backward is the same
     call on the gradient (include/mmlrec.h: mml_dropout; reference model/utils.py:159)."""
-    L.check(L.load().mml_dropout(x.data_ptr(), _ld(x), out.data_ptr(), _ld(out), x.shape[0], x.shape[1], int(row0), float(p),
-                                 int(seed) & ((1 << 64) - 1), int(site) & 0xffffffff, L.ptr(step_dev), int(step),
-                                 int(accumulate), _stream()), "mml_dropout")
+    _issue(bind.dropout(x, out, p, seed, site, step_dev, step, accumulate, row0))
 
 
 def copy2d(src, dst, accumulate=False):
     """dst[:, :] (+)= src[:, :] for 2-D row-strided views (column slices of wider buffers are fine)."""
-    rows, cols = src.shape
-    L.check(L.load().mml_copy2d(src.data_ptr(), _ld(src), dst.data_ptr(), _ld(dst), rows, cols, int(accumulate),
-                                _stream()), "mml_copy2d")
+    _issue(bind.copy2d(src, dst, accumulate))
+
+
+def make_sumprod_descs(rows, too_many="more than 8 terms in one sum"):
+    """The SumProdDesc block of mml_sumprod_batch: out (+)= sum_k x_k * (y_k or 1) over n flat elements per row.
+    rows: (out, n, [(x, y or None), ...], accumulate, act, deriv_of[, amax slot]) -- act != ACT_NONE multiplies the sum by
+    act'(deriv_of); the slot is raised with the magnitude of what is stored.  too_many: the caller's words for a row of
+    more than 8 terms."""
+    arr = (L.SumProdDesc * len(rows))()
+    for d, row in zip(arr, rows):
+        out, n, terms, acc, act, deriv_of = row[:6]
+        if len(terms) > 8:
+            raise NotImplementedError(too_many)
+        d.out, d.n, d.n_terms, d.accumulate = out.data_ptr(), n, len(terms), int(acc)
+        d.amax_out = L.ptr(row[6]) if len(row) > 6 else None
+        d.act, d.deriv_of = int(act), (deriv_of.data_ptr() if act != L.ACT_NONE else None)
+        for k, (x, y) in enumerate(terms):
+            d.x[k], d.y[k] = x.data_ptr(), L.ptr(y)
+    return arr
+
+
+def make_attn2_desc(tokens, out, A, B, H, sqrt_h, grads=None):
+    """mml_attn2_desc: tokens = [(V, K, Q)] x 2 of [B, H] views, out [B, H], A = the [B, 2] attention weights the forward
+    leaves for the backward; grads = (dout, [(dV, dK, dQ)] x 2) for mml_attn2_bwd."""
+    d = L.Attn2Desc()
+    for t, (V, K, Q) in enumerate(tokens):
+        d.V[t], d.K[t], d.Q[t] = V.data_ptr(), K.data_ptr(), Q.data_ptr()
+        d.ldv[t], d.ldk[t], d.ldq[t] = _ld(V), _ld(K), _ld(Q)
+    d.out, d.ldo, d.A = out.data_ptr(), _ld(out), A.data_ptr()
+    d.B, d.H, d.sqrt_h = B, H, sqrt_h
+    if grads is not None:
+        dout, dtokens = grads
+        d.dout, d.lddo = dout.data_ptr(), _ld(dout)
+        for t, (dV, dK, dQ) in enumerate(dtokens):
+            d.dV[t], d.dK[t], d.dQ[t] = dV.data_ptr(), dK.data_ptr(), dQ.data_ptr()
+            d.lddv[t], d.lddk[t], d.lddq[t] = _ld(dV), _ld(dK), _ld(dQ)
+    return d
 
 
 def prelu_max_batch():
@@ -887,9 +917,7 @@ def pcgrad_gram(segs, T, gram=None):
     if gram is None:
         gram = torch.empty((T, T), dtype=torch.float64, device=dev)
     nbytes = int(L.load().mml_pcgrad_workspace_bytes(arr, len(segs), T))
-    ws = workspace(nbytes, dev)
-    L.check(L.load().mml_pcgrad_gram(arr, len(segs), T, gram.data_ptr(), ws.data_ptr(), nbytes, _stream()),
-            "mml_pcgrad_gram")
+    _issue(bind.pcgrad_gram(arr, len(segs), T, gram, workspace(nbytes, dev)))  # (the byte count is only checked)
     return gram
 
 
@@ -905,8 +933,7 @@ def pcgrad_weights(gram, order, w=None, fired=None):
         w = torch.empty(2 * T, dtype=torch.float32, device=gram.device)
     if fired is None:
         fired = torch.empty((T, T), dtype=torch.int32, device=gram.device)
-    L.check(L.load().mml_pcgrad_weights(gram.data_ptr(), order.data_ptr(), T, w.data_ptr(), fired.data_ptr(), _stream()),
-            "mml_pcgrad_weights")
+    _issue(bind.pcgrad_weights(gram, order, T, w, fired))
     return w, fired
 
 
@@ -915,11 +942,11 @@ def pcgrad_combine(segs, T, w):
     (mml_pcgrad_combine)."""
     _need_gpu(w)
     arr = make_pcgrad_segs(segs, T, need_out=True)
-    L.check(L.load().mml_pcgrad_combine(arr, len(segs), T, w.data_ptr(), _stream()), "mml_pcgrad_combine")
+    _issue(bind.pcgrad_combine(arr, len(segs), T, w))
 
 
 def act_bwd(y, dy, dst, act):
-    L.check(L.load().mml_act_bwd(y.data_ptr(), dy.data_ptr(), dst.data_ptr(), y.numel(), act, _stream()), "mml_act_bwd")
+    _issue(bind.act_bwd(y, dy, dst, act))
 
 
 # ---------------------------------------------------------------------------------------------- K8
@@ -988,7 +1015,7 @@ def opt_catchup_dense(table, state1, state2, last, hyper):
 
 
 def counter_update(counter, delta=1, reset=False):
-    L.check(L.load().mml_counter_update(counter.data_ptr(), int(delta), int(reset), _stream()), "mml_counter_update")
+    _issue(bind.counter_update(counter, delta, reset))
 
 
 def step_counter(device):

@@ -542,7 +542,7 @@ class Optimizer:
         # the list is REBUILT every step by the compaction that follows the marking kernels (E in 4, 8, 16: it
         # resets the counter itself); only the appending atomic path needs the reset here
         if tabs[0].data.shape[1] not in (4, 8, 16) or knobs.scatter_old:
-            calls.append((L.load().mml_counter_update, (rows.count.data_ptr(), 0, 1)))
+            calls.append(plan.bound(bind.counter_update(rows.count, 0, True)))
         return calls
 
     def _moments(self, names):

@@ -347,7 +347,7 @@ class RowShardedGatherOp(E.Op):
                                          rs.pos.data_ptr(), st, s), "mml_lookup_slots")
             L.check(lib.mml_rows_clear(rq.touched.data_ptr(), rq.count.data_ptr(), rq.touched.numel(), rs.req_rb,
                                        rs.req_seen, F, s), "mml_rows_clear")
-            L.check(lib.mml_counter_update(rq.count.data_ptr(), 0, 1, s), "mml_counter_update")
+            ops.counter_update(rq.count, 0, reset=True)
         else:
             L.check(lib.mml_route_count(Xp, ldX, None, 0, self.col, self.vocab, F, B, W, cp, st, s), "mml_route_count")
             rs.cnt_pair[0].copy_(rs.counters[:W])  # (mml_route_place moves the cursors, not the counts)

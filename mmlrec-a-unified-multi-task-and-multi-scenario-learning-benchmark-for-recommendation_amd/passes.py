@@ -15,6 +15,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
+from . import bind
 from . import engine as E
 from . import ops
 from .engine import call_meta
@@ -62,8 +63,8 @@ def amax_prologue(plan, lib=None):
     if plan.amax_pool is None or not plan.amax_next or plan.amax_pre_done:
         return
     lib = lib or L.load()
-    pre = [(lib.mml_amax_reset, (plan.amax_pool.data_ptr(), plan.amax_next),
-            dict(kernel="amax_reset", bytes=32.0 * plan.amax_next))]
+    reset = bind.amax_reset(plan.amax_pool, plan.amax_next)
+    pre = [(getattr(lib, reset.name), reset.args, dict(kernel="amax_reset", bytes=32.0 * plan.amax_next))]
     cut = []
     if plan.planes_items:  # (after the magnitudes of the weights: the cut reads them)
         arr = ops.make_planes_descs(plan.planes_items)

@@ -257,8 +257,7 @@ class PCGradSchedule(OneList):
 
     def __init__(self, plan, store, opt, opt_split, use_graph):
         from . import _lib as L
-        from . import ops
-        lib = L.load()
+        from . import bind, ops
         T, B, dev = plan.pcgrad_T, plan.B, plan.device
         if T > L.PCGRAD_MAX_TASKS:
             raise NotImplementedError(f"PCGrad per_task: {T} tasks (at most {L.PCGRAD_MAX_TASKS})")
@@ -308,43 +307,38 @@ class PCGradSchedule(OneList):
                 prev = (t - 1) % T  # (pass 0: the column the previous step's last pass left set)
                 cols.append((zeros, plan.mask[:, prev:prev + 1]))
             calls = [copies(cols),
-                     (lib.mml_ew_mul, (plan.y.data_ptr(), plan.mask.data_ptr(), self.y_heads.data_ptr(), B * T),
-                      dict(kernel="ew_mul_kernel", bytes=12.0 * B * T))]
+                     plan.bound(bind.ew_mul(plan.y, plan.mask, self.y_heads), kernel="ew_mul_kernel", bytes=12.0 * B * T)]
             calls += plan.head_train + plan.bwd + plan.bwd_tail + list(getattr(plan, "head_side", [])) + plan.bwd_side
             calls.append(copies([(plan.prob, self.prob_sum), (loss2d, self.loss_sum)], accumulate=t > 0))
             a = ops.make_pcgrad_segs([dict(banks=[store.arena], out=self.dense_bank[t])], 1, need_out=True)
-            plan.keep.append(a)
-            calls.append((lib.mml_pcgrad_stash, (a, 1, 0),
-                          dict(kernel="pcgrad_stash_kernel", bytes=8.0 * store.arena.numel())))
+            calls.append(plan.bound(bind.pcgrad_stash(a, 1, False), kernel="pcgrad_stash_kernel",
+                                    bytes=8.0 * store.arena.numel()))
             if tabs:
                 b = ops.make_pcgrad_segs(table_segs[t], 1, need_out=True)
-                plan.keep.append(b)
-                calls.append((lib.mml_pcgrad_stash, (b, len(tabs), 1),
-                              dict(kernel="pcgrad_stash_kernel", bytes=12.0 * B * len(tabs) * tabs[0].data.shape[1])))
+                calls.append(plan.bound(bind.pcgrad_stash(b, len(tabs), True), kernel="pcgrad_stash_kernel",
+                                        bytes=12.0 * B * len(tabs) * tabs[0].data.shape[1]))
             self.passes.append(calls)
         arr = ops.make_pcgrad_segs(self.segs, T, need_out=True)
         n = len(self.segs)
-        nws = int(lib.mml_pcgrad_workspace_bytes(arr, n, T))
-        ws = torch.empty(max(nws, 256), dtype=torch.uint8, device=dev)
-        plan.keep += [arr, ws, self.dense_bank, self.table_banks, self.gram, self.w, self.fired, self.order]
+        ws = plan.workspace(L.load().mml_pcgrad_workspace_bytes(arr, n, T), least=256)
+        plan.keep += [self.dense_bank, self.table_banks, self.gram, self.w, self.fired, self.order]
         elems = float(sum(int(sg["out"].numel()) if sg.get("marks") is None else
                           min(int(sg["out"].numel()), B * int(sg["out"].shape[1])) for sg in self.segs))
         self.surgery = [
             copies([(self.prob_sum, plan.prob), (self.loss_sum, loss2d)]),
-            (lib.mml_pcgrad_gram, (arr, n, T, self.gram.data_ptr(), ws.data_ptr(), ws.numel()),
-             dict(kernel="pcgrad_gram_kernel", bytes=4.0 * T * elems)),
-            (lib.mml_pcgrad_weights, (self.gram.data_ptr(), self.order.data_ptr(), T, self.w.data_ptr(),
-                                      self.fired.data_ptr()), dict(kernel="pcgrad_weights_kernel", bytes=8.0 * T * T)),
-            (lib.mml_pcgrad_combine, (arr, n, T, self.w.data_ptr()),
-             dict(kernel="pcgrad_combine_kernel", bytes=4.0 * (T + 1) * elems)),
+            plan.bound(bind.pcgrad_gram(arr, n, T, self.gram, ws), kernel="pcgrad_gram_kernel", bytes=4.0 * T * elems),
+            plan.bound(bind.pcgrad_weights(self.gram, self.order, T, self.w, self.fired), kernel="pcgrad_weights_kernel",
+                       bytes=8.0 * T * T),
+            plan.bound(bind.pcgrad_combine(arr, n, T, self.w), kernel="pcgrad_combine_kernel",
+                       bytes=4.0 * (T + 1) * elems),
         ]
         # the marked dense update clears the scatter's marks itself; the row-wise updates do not read them
         self.unmark = []
         if gm is not None and opt.table_update != "dense_exact":
             z = torch.zeros((gm.numel() // 32, 8), dtype=torch.float32, device=dev)  # (the map is padded to 32 bytes per table)
             plan.keep.append(z)
-            self.unmark = [(lib.mml_copy2d, (z.data_ptr(), 8, gm.data_ptr(), 8, z.shape[0], 8, 0),
-                            dict(kernel="copy2d_kernel", bytes=2.0 * gm.numel()))]
+            self.unmark = [plan.bound(bind.copy2d(z, gm.view(torch.float32).view_as(z), False), kernel="copy2d_kernel",
+                                      bytes=2.0 * gm.numel())]
         self.gradients = plan.fwd + [c for p_ in self.passes for c in p_] + self.surgery
         self.calls = (opt_split["pre"] + self.gradients + self.unmark + opt_split["tables"] + opt_split["mlp"])
         OneList.__init__(self, Segments(self.calls, use_graph))

@@ -1,6 +1,7 @@
 """A recorded plan entry and the eager wrapper launch the same thing: GatherOp and PooledGatherOp record their forward and
 backward on a bare Plan (engine.Plan.bound over mmlrec_amd/bind.py), the entries are run, and every result is compared
-bit for bit with the ops.* call on the same inputs.
+bit for bit with the ops.* call on the same inputs.  The last test does the same for the model-layer ops that have an eager
+twin (DropoutOp, CopyColsOp, PAddOp), at B = 5.
 
 Schema: 2 single-valued fields and 2 pooled fields (maxlen 3; one "sum", one "max"), the "sum" field sharing its table
 with a single field; E = 8, B = 257 (more than one block, no multiple of a tile), one dense column, 37 .. 61 rows per table.
@@ -205,3 +206,55 @@ def test_pooled_scatter_backward_entries_are_the_eager_calls(env):
     assert all(torch.equal(t.grad, g) for t, g in zip(pv, gt_det))
     assert all(torch.equal(a, b) for a, b in zip(gt, gt_det))
     assert int(plan.status.item()) == 0
+
+
+def test_dropout_copy_and_add_entries_are_the_eager_calls(env):
+    """The model-layer ops whose eager twin exists, at B = 5 with a pitch of its own per buffer: DropoutOp (forward and
+    backward), CopyColsOp, PAddOp (forward: mml_ew_add_n, backward: the flat mml_copy2d)."""
+    E, ops, dev = env["E"], env["ops"], env["dev"]
+    Bs, n, p, seed, site = 5, 7, 0.3, (1 << 64) + 0xfeedfacecafebeef, (1 << 32) + 0x9e3779b9
+    g = torch.Generator().manual_seed(3)
+
+    def mat(cols, ld, c0=0):
+        return torch.randn(Bs, ld, generator=g).to(dev)[:, c0:c0 + cols]
+
+    plan = E.Plan(dev, Bs, True)
+    plan.step_dev, plan.row0 = torch.tensor([5], dtype=torch.int32, device=dev), 3
+    x, y = E.Val(mat(n, 9), name="x"), E.Val(mat(n, 11), name="y")
+    op = E.DropoutOp(x, y, p, seed, site)
+    x.consumers.append(op)
+    calls = op.fwd_calls(plan)
+    assert [c[0].__name__ for c in calls] == ["mml_dropout"] and calls[0][1][8] < (1 << 64) and calls[0][1][9] < (1 << 32)
+    E.Plan._run(calls)
+    ref = mat(n, 13)
+    ops.dropout(x.buf, ref, p, seed, site, step=99, step_dev=plan.step_dev, row0=3)
+    assert torch.equal(y.buf, ref) and bool((ref == 0).any()) and bool((ref != 0).any())
+    y.grad = mat(n, 10)
+    calls = op.bwd_calls(plan)
+    assert [c[0].__name__ for c in calls] == ["mml_dropout"] and calls[0][1][-1] == 0
+    E.Plan._run(calls)
+    ops.dropout(y.grad, ref, p, seed, site, step_dev=plan.step_dev, row0=3)
+    assert torch.equal(x.grad, ref)
+
+    src, dst, ref = mat(4, 9, 2), mat(4, 12, 3), mat(4, 6, 1)
+    calls = E.CopyColsOp(src, dst).fwd_calls(plan)
+    assert [c[0].__name__ for c in calls] == ["mml_copy2d"] and calls[0][2] == {}
+    E.Plan._run(calls)
+    ops.copy2d(src, ref)
+    assert torch.equal(dst, ref) and torch.equal(dst, src)
+
+    ins = [E.PVal(torch.randn(n, generator=g).to(dev), torch.full((n,), 7.0, device=dev), f"b{i}") for i in range(3)]
+    out = E.PVal(torch.zeros(n, device=dev), torch.randn(n, generator=g).to(dev), "b_eff")
+    add = E.PAddOp(ins, out)
+    E.Plan._run(add.fwd_calls(plan))
+    ref = torch.zeros(n, device=dev)
+    ops.ew_add_n([q.data for q in ins], ref)
+    assert torch.equal(out.data, ref) and bool(ref.any())
+    out.written = 1
+    calls = add.bwd_calls(plan)
+    assert [c[0].__name__ for c in calls] == ["mml_copy2d"] * 3
+    assert all(c[2] == dict(kernel="copy2d_kernel", side=True) for c in calls)
+    E.Plan._run(calls)
+    ref = torch.full((1, n), 7.0, device=dev)
+    ops.copy2d(out.grad.view(1, n), ref)
+    assert all(torch.equal(q.grad, ref[0]) for q in ins) and torch.equal(ref[0], out.grad)

@@ -3,7 +3,7 @@
 
     python tools/plan_dump.py --workload mmoe_ae30 --batch 65536 [--table-update dense_exact] [--scatter-mode atomic]
                               [--gemm-mode N] [--streams 2] [--vocab-scale 0.2] [--split-dense force|off]
-                              [--pcgrad total|per_task] [--infer] [--out FILE]
+                              [--pcgrad total|per_task] [--model-kw KEY=VALUE ...] [--infer] [--out FILE]
 
 Two trees record the same step iff their dumps are equal: the before / after check of a change to engine.py or
 trainer.py (diff the two files).  Per entry: the function's name, its meta without pointers, its scalar arguments, and
@@ -14,6 +14,7 @@ The first line names every option of THIS copy of the tool (pcgrad= and split_de
 in that line from one an older copy wrote: make both sides of a comparison with one copy (it runs in older trees)."""
 import argparse
 import ctypes as C
+import json
 import os
 import sys
 
@@ -109,6 +110,12 @@ def dump(args):
         kw["scatter_mode"] = args.scatter_mode
     if args.pcgrad:  # (the workload's model as model_name "pcg": PCGrad over its tasks)
         kw.update(seed=0, model_name="pcg")
+    for item in args.model_kw:  # (forwarded to workloads.build_model: the value as JSON, else as the string it is)
+        key, _, text = item.partition("=")
+        try:
+            kw[key] = json.loads(text)
+        except ValueError:
+            kw[key] = text
     model, cfg, _, _ = W.build_model(args.workload, dev, vocab_scale=args.vocab_scale, **kw)
     if args.pcgrad:
         model.optim_config["pcgrad_objectives"] = args.pcgrad
@@ -154,6 +161,8 @@ def main():
                     help="the split_dense request of train_step_runner: True, 'force' or False")
     ap.add_argument("--pcgrad", default=None, choices=["total", "per_task"],
                     help="build the workload as model_name='pcg' with these pcgrad_objectives")
+    ap.add_argument("--model-kw", action="append", default=[], metavar="KEY=VALUE",
+                    help="a keyword for workloads.build_model (repeatable), e.g. dnn_use_bn=true, dnn_activation=prelu")
     ap.add_argument("--infer", action="store_true", help="the forward-only plan instead of a training step")
     ap.add_argument("--out", default=None, help="write here instead of stdout")
     args = ap.parse_args()
