@@ -64,6 +64,23 @@ __device__ __forceinline__ void amax_flush(float amf, uint32_t* slot) {
   }
   __syncthreads();  // (the array may be reused by the next flush of the same kernel)
 }
+
+// ---- activations chosen at run time (MML_ACT_*): forward, and the derivative from the OUTPUT value y ----
+__device__ __forceinline__ float act_fwd(float v, int act) {
+  if (act == MML_ACT_RELU) return v > 0.f ? v : 0.f;
+  if (act == MML_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
+  if (act == MML_ACT_SIGMOID2) return 2.f / (1.f + __expf(-v));
+  return v;
+}
+__device__ __forceinline__ float act_bwd(float y, int act) {
+  if (act == MML_ACT_RELU) return y > 0.f ? 1.f : 0.f;
+  if (act == MML_ACT_SIGMOID) return y * (1.f - y);
+  if (act == MML_ACT_SIGMOID2) {
+    const float s = 0.5f * y;
+    return 2.f * s * (1.f - s);
+  }
+  return 1.f;
+}
 #endif
 
 }  // namespace mml

@@ -16,7 +16,9 @@ __global__ __launch_bounds__(256) void ew_mul_kernel(const float* a, const float
 }
 
 // act_a / act_b: the operand is the OUTPUT of that activation and this product is its only consumer, so the
-// activation's derivative (from the output value, like mml_act_bwd) is folded into the gradient written here
+// activation's derivative (from the output value, like mml_act_bwd) is folded into the gradient written here.
+// (The same function as common.hpp's act_bwd in another spelling: SIGMOID2 as y (1 - y / 2) = 2 s (1 - s), s = y / 2.  The
+// two round differently, so this one keeps its own text and the kernels here their bits.)
 __device__ __forceinline__ float act_deriv_from_output(float y, int act) {
   if (act == MML_ACT_RELU) return y > 0.f ? 1.f : 0.f;
   if (act == MML_ACT_SIGMOID) return y * (1.f - y);

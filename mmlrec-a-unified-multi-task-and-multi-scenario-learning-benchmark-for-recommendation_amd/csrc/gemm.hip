@@ -18,6 +18,7 @@
 #include "gemm_route.hpp"
 #include "lds_async.hpp"
 #include "reduce.hpp"
+#include "two_plane.hpp"
 
 #include <stdlib.h>
 
@@ -73,25 +74,10 @@ struct Problem {
   uint32_t* amax_out2;
 };
 
-// ---- operand magnitudes (mml_amax_*, the amax fields of the GEMM descriptors) ----
-// A magnitude slot is MML_AMAX_WORDS consecutive words; producers atomicMax the bit pattern of |x| into ANY of them
-// (which one is picked from the workgroup / wave number, so that thousands of same-address atomics do not serialise
-// at the memory side), consumers take the largest.
-__device__ __forceinline__ uint32_t amax_load(const uint32_t* p) {
-  if (!p) return 0x3f800000u;  // (no magnitude given: scale 2^14; the host only selects the fp16 form when all are there)
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < MML_AMAX_WORDS; ++i) m = p[i] > m ? p[i] : m;
-  return m;
+// ---- operand magnitudes (mml_amax_*, the amax fields of the GEMM descriptors; slot, exponent and 2^k: two_plane.hpp) ----
+__device__ __forceinline__ uint32_t amax_slot_or_one(const uint32_t* p) {
+  return p ? amax_slot(p) : 0x3f800000u;  // (no magnitude given: scale 2^14; the host only selects the fp16 form when all are there)
 }
-// power-of-two exponent k with |x| 2^k < 2^15 for every |x| <= the slot's value (fp16: largest finite 65504)
-__device__ __forceinline__ int amax_scale_exp(uint32_t bits) {
-  int e = (int)((bits >> 23) & 0xffu);  // |x| < 2^(e - 126)
-  if (e == 255) return 0;               // Inf / NaN in the operand: they propagate whatever the scale
-  int k = 141 - e;
-  return k > 110 ? 110 : (k < -110 ? -110 : k);
-}
-__device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
 // wave-wide maximum of a per-lane bit pattern, then ONE atomic per wave into the slot
 __device__ __forceinline__ void amax_publish(uint32_t am, uint32_t* slot, int salt) {
 #pragma unroll
@@ -127,19 +113,19 @@ __global__ __launch_bounds__(256) void planes_cut_kernel(const PlanesLaunch L) {
   } else if ((int)threadIdx.x < D.n_amax) {
     // K6: the matrix is a product of two factors: its magnitude bound is the product of theirs (a non-finite factor
     // bound stays non-finite: exponent 0 below)
-    const float a = __uint_as_float(amax_load(D.amax[threadIdx.x])), b = __uint_as_float(amax_load(D.amax[D.n_amax + threadIdx.x]));
+    const float a = __uint_as_float(amax_slot_or_one(D.amax[threadIdx.x])), b = __uint_as_float(amax_slot_or_one(D.amax[D.n_amax + threadIdx.x]));
     atomicMax(&mx, __float_as_uint(a * b));
   }
   __syncthreads();
-  // (amax_scale_exp is monotone: the exponent of the largest magnitude is the smallest exponent of the group; an
+  // (scale_exp_of is monotone: the exponent of the largest magnitude is the smallest exponent of the group; an
   // Inf / NaN pattern gives 0 like the in-kernel cut of the operand that holds it)
-  int k = amax_scale_exp(mx);
+  int k = scale_exp_of(mx);
   if (D.n_amax > 1 && (mx >> 23) >= 255u) {  // a non-finite slot must not hide the finite ones' exponents: redo per slot
     k = 110;
     for (int a = 0; a < D.n_amax; ++a) {
-      uint32_t bits = amax_load(D.amax[a]);
-      if (D.W2) bits = __float_as_uint(__uint_as_float(bits) * __uint_as_float(amax_load(D.amax[D.n_amax + a])));
-      const int ka = amax_scale_exp(bits);
+      uint32_t bits = amax_slot_or_one(D.amax[a]);
+      if (D.W2) bits = __float_as_uint(__uint_as_float(bits) * __uint_as_float(amax_slot_or_one(D.amax[D.n_amax + a])));
+      const int ka = scale_exp_of(bits);
       k = ka < k ? ka : k;
     }
   }
@@ -215,23 +201,6 @@ struct Launch {
   int32_t chunk;         // wgrad: batch rows per split (multiple of BK)
   float* slab;           // wgrad workspace
 };
-
-__device__ __forceinline__ float act_fwd(float v, int act) {
-  if (act == MML_ACT_RELU) return v > 0.f ? v : 0.f;
-  if (act == MML_ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
-  if (act == MML_ACT_SIGMOID2) return 2.f / (1.f + __expf(-v));
-  return v;
-}
-
-__device__ __forceinline__ float act_bwd(float y, int act) {
-  if (act == MML_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  if (act == MML_ACT_SIGMOID) return y * (1.f - y);
-  if (act == MML_ACT_SIGMOID2) {
-    const float s = 0.5f * y;
-    return 2.f * s * (1.f - s);
-  }
-  return 1.f;
-}
 
 // ---- global -> register tile fetch ---------------------------------------------------------------
 // RC: tile is [ROWS rows][BK k], memory k-contiguous. thread t, piece c: row = (t + 256c) / 8, k4 = (t + 256c) % 8.
@@ -779,24 +748,19 @@ __global__ __launch_bounds__(256, ((BN == 64 && EPI != EPI_DGRAD && !K7) ? 3 : 2
     int kA = 110, kB = 110;
     const int s0 = L.p[pi].src0, ns = L.p[pi].nsrc;
     for (int s2 = 0; s2 < ns; ++s2) {
-      const int ka = amax_scale_exp(amax_load(L.src[s0 + s2].amaxA));
+      const int ka = scale_exp_of(amax_slot_or_one(L.src[s0 + s2].amaxA));
       kA = ka < kA ? ka : kA;
       if constexpr (!BPL) {
-        const int kb = amax_scale_exp(amax_load(L.src[s0 + s2].amaxB));
+        const int kb = scale_exp_of(amax_slot_or_one(L.src[s0 + s2].amaxB));
         kB = kb < kB ? kb : kB;
       }
     }
     if constexpr (BPL) {  // the exponent the planes were cut with (one per problem: its sources were cut as a group)
       kB = *reinterpret_cast<const int32_t*>(L.src[s0].amaxB);
-      // (the planes are what they are: where the exponents add up beyond fp32's range the row operand alone gives way)
-      if (kA + kB > 126) kA = 126 - kB;
-      if (kA + kB < -126) kA = -126 - kB;
+      kA = row_gives_way(kA, kB);
     }
-    // 1 / (sA sB) must be ONE fp32 number (the epilogue multiplies once): where the exponents add up beyond its range
-    // -- two operands below 2^-48, whose products fp32 can barely hold -- both scales give way equally
-    const int over = kA + kB - 126, under = -126 - (kA + kB);
-    if (over > 0) { kA -= (over + 1) >> 1; kB -= over >> 1; }
-    if (under > 0) { kA += (under + 1) >> 1; kB += under >> 1; }
+    // 1 / (sA sB) must be ONE fp32 number (the epilogue multiplies once)
+    { const ScalePair g = both_give_way(kA, kB); kA = g.row; kB = g.col; }
     kA = __builtin_amdgcn_readfirstlane(kA);
     kB = __builtin_amdgcn_readfirstlane(kB);
     sA = pow2f(kA);

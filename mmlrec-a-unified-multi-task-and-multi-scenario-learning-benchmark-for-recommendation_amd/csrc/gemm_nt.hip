@@ -23,6 +23,7 @@
 #include "common.hpp"
 #include "gemm_route.hpp"
 #include "lds_async.hpp"
+#include "two_plane.hpp"
 
 namespace mml {
 
@@ -50,21 +51,6 @@ struct NtLaunch {
   NtProblem p[NT_MAX_GROUP];
   int32_t n_prob, steps, slabs, tiles;
 };
-
-__device__ __forceinline__ uint32_t nt_amax_load(const uint32_t* p) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < MML_AMAX_WORDS; ++i) m = p[i] > m ? p[i] : m;
-  return m;
-}
-// power-of-two exponent k with |x| 2^k < 2^15 for every |x| <= the slot's value (the rule of gemm.hip)
-__device__ __forceinline__ int nt_scale_exp(uint32_t bits) {
-  const int e = (int)((bits >> 23) & 0xffu);
-  if (e == 255) return 0;
-  const int k = 141 - e;
-  return k > 110 ? 110 : (k < -110 ? -110 : k);
-}
-__device__ __forceinline__ float nt_pow2(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
 
 // image (b) of the CDNA programming guide, T10: 256-byte rows, chunk c of row r at position c ^ (((r & 3) << 2) | ((r >> 2) & 3))
 __device__ __forceinline__ int nt_swz32(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
@@ -126,17 +112,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const NtLaunch L) {
   const int s_begin = slab * per, s_end = min(L.steps, s_begin + per);
   const bool want_bias = P.ws_bias != nullptr && kt == 0;  // (uniform)
 
-  // scales (one pair per problem); 1 / (sC sA) must be one fp32 number: where the exponents add up beyond its range both
-  // give way equally (gemm.hip: problem_scales)
-  int kC = nt_scale_exp(nt_amax_load(P.amax_dc)), kA = nt_scale_exp(nt_amax_load(P.amax_a));
-  {
-    const int over = kC + kA - 126, under = -126 - (kC + kA);
-    if (over > 0) { kC -= (over + 1) >> 1; kA -= over >> 1; }
-    if (under > 0) { kC += (under + 1) >> 1; kA += under >> 1; }
-  }
+  // scales (one pair per problem); 1 / (sC sA) must be one fp32 number (two_plane.hpp)
+  int kC = scale_exp_of(amax_slot(P.amax_dc)), kA = scale_exp_of(amax_slot(P.amax_a));
+  { const ScalePair g = both_give_way(kC, kA); kC = g.row; kA = g.col; }
   kC = __builtin_amdgcn_readfirstlane(kC);
   kA = __builtin_amdgcn_readfirstlane(kA);
-  const float sC = nt_pow2(kC), sA = nt_pow2(kA), inv = nt_pow2(-(kC + kA));
+  const float sC = pow2f(kC), sA = pow2f(kA), inv = pow2f(-(kC + kA));
 
   f32x16 acc[2][2];
 #pragma unroll
@@ -319,15 +300,11 @@ __global__ __launch_bounds__(256, 2) void gemm_ntd_kernel(const NtLaunch L) {
   const int s_begin = slab * per, s_end = min(L.steps, s_begin + per);
   const bool want_bias = P.ws_bias != nullptr && kt == 0;  // (uniform)
 
-  int kC = nt_scale_exp(nt_amax_load(P.amax_dc)), kA = nt_scale_exp(nt_amax_load(P.amax_a));
-  {
-    const int over = kC + kA - 126, under = -126 - (kC + kA);
-    if (over > 0) { kC -= (over + 1) >> 1; kA -= over >> 1; }
-    if (under > 0) { kC += (under + 1) >> 1; kA += under >> 1; }
-  }
+  int kC = scale_exp_of(amax_slot(P.amax_dc)), kA = scale_exp_of(amax_slot(P.amax_a));
+  { const ScalePair g = both_give_way(kC, kA); kC = g.row; kA = g.col; }
   kC = __builtin_amdgcn_readfirstlane(kC);
   kA = __builtin_amdgcn_readfirstlane(kA);
-  const float sC = nt_pow2(kC), sA = nt_pow2(kA), inv = nt_pow2(-(kC + kA));
+  const float sC = pow2f(kC), sA = pow2f(kA), inv = pow2f(-(kC + kA));
 
   f32x16 acc[2][2];
 #pragma unroll

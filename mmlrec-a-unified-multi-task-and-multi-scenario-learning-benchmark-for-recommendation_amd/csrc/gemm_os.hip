@@ -20,6 +20,7 @@
 #include "common.hpp"
 #include "gemm_route.hpp"
 #include "lds_async.hpp"
+#include "two_plane.hpp"
 
 #include <stdlib.h>
 
@@ -56,21 +57,6 @@ struct OsLaunch {
 };
 static_assert(sizeof(OsLaunch) <= 4096, "OsLaunch must fit the kernel-argument block");
 
-__device__ __forceinline__ uint32_t os_amax_load(const uint32_t* p) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < MML_AMAX_WORDS; ++i) m = p[i] > m ? p[i] : m;
-  return m;
-}
-// (the rule of gemm.hip: |x| 2^k < 2^15 for every |x| <= the slot's value; Inf / NaN: scale 1)
-__device__ __forceinline__ int os_scale_exp(uint32_t bits) {
-  const int e = (int)((bits >> 23) & 0xffu);
-  if (e == 255) return 0;
-  const int k = 141 - e;
-  return k > 110 ? 110 : (k < -110 ? -110 : k);
-}
-__device__ __forceinline__ float os_pow2(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
-
 __device__ __forceinline__ void os_wait_vm(const int n) {  // n in {0, 2, 4, 6}
   if (n >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -95,19 +81,16 @@ __global__ __launch_bounds__(512, 1) void gemm_os_kernel(const OsLaunch Larg) {
   const int npanels = (M + OS_BM - 1) / OS_BM;
 
   // ONE scale pair for the problem (gemm.hip, problem_scales with pre-cut weights): the smallest exponent over the
-  // sources' gradients, the exponent the planes were cut with; where the two add up beyond fp32's range the row operand
-  // gives way
+  // sources' gradients, the exponent the planes were cut with
   int kA = 110;
   for (int s = 0; s < nsrc; ++s) {
-    const int ka = os_scale_exp(os_amax_load(L.s[s].amax_dc));
+    const int ka = scale_exp_of(amax_slot(L.s[s].amax_dc));
     kA = ka < kA ? ka : kA;
   }
   const int kB = *L.kexp;
-  if (kA + kB > 126) kA = 126 - kB;
-  if (kA + kB < -126) kA = -126 - kB;
-  kA = __builtin_amdgcn_readfirstlane(kA);
-  const float sA = os_pow2(kA);
-  const float inv = os_pow2(-(kA + __builtin_amdgcn_readfirstlane(kB)));
+  kA = __builtin_amdgcn_readfirstlane(row_gives_way(kA, kB));
+  const float sA = pow2f(kA);
+  const float inv = pow2f(-(kA + __builtin_amdgcn_readfirstlane(kB)));
 
   // ---- DMA lane geometry ----
   // dC: wave-instruction i (of 16 per stage) covers rows 16 i .. 16 i + 15 of the panel: lane -> (row, physical chunk);

@@ -24,6 +24,7 @@
 #include "common.hpp"
 #include "gemm_route.hpp"
 #include "lds_async.hpp"
+#include "two_plane.hpp"
 
 #include <stdlib.h>
 
@@ -73,21 +74,6 @@ struct PanelLaunch {
   int32_t half[PN_MAXH];  // problem << 16 | first column of the half tile (32-bit words: scalar loads, not VMEM)
 };
 static_assert(sizeof(PanelLaunch) <= 4096, "PanelLaunch must fit the kernel-argument block");
-
-__device__ __forceinline__ uint32_t pn_amax_load(const uint32_t* p) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < MML_AMAX_WORDS; ++i) m = p[i] > m ? p[i] : m;
-  return m;
-}
-// (the rule of gemm.hip: |x| 2^k < 2^15 for every |x| <= the slot's value; Inf / NaN: scale 1)
-__device__ __forceinline__ int pn_scale_exp(uint32_t bits) {
-  const int e = (int)((bits >> 23) & 0xffu);
-  if (e == 255) return 0;
-  const int k = 141 - e;
-  return k > 110 ? 110 : (k < -110 ? -110 : k);
-}
-__device__ __forceinline__ float pn_pow2(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
 
 // s_waitcnt vmcnt(n) for a run-time n (the immediate is six bits wide)
 __device__ __forceinline__ void pn_wait_vm(const int n) {
@@ -187,7 +173,7 @@ __global__ __launch_bounds__(256, 1) void gemm_panel_kernel(const PanelLaunch La
   }
   if (tid < MML_MAX_GROUP) {
     // the weights' exponents, once: a global load inside the tile loop would make hipcc drain the LDS-DMA ring there
-    const float ib = tid < L.n_prob ? pn_pow2(-*L.p[tid].kexp) : 1.f;
+    const float ib = tid < L.n_prob ? pow2f(-*L.p[tid].kexp) : 1.f;
     const uint32_t b = lds0 + PN_INVB_OFF + tid * 4;
     asm volatile("ds_write_b32 %0, %1" ::"v"(b), "v"(ib) : "memory");
   }
@@ -199,8 +185,8 @@ __global__ __launch_bounds__(256, 1) void gemm_panel_kernel(const PanelLaunch La
   __builtin_amdgcn_s_barrier();
 
   // power-of-two scale of the activations (one per launch: every problem reads the same panel)
-  const int kA = __builtin_amdgcn_readfirstlane(pn_scale_exp(pn_amax_load(L.amaxA)));
-  const float sA = pn_pow2(kA), invA = pn_pow2(-kA);
+  const int kA = __builtin_amdgcn_readfirstlane(scale_exp_of(amax_slot(L.amaxA)));
+  const float sA = pow2f(kA), invA = pow2f(-kA);
 
   // ---- weight fragment reads (the image of gemm.hip: 64-byte rows, 16-byte chunk c of row r at c ^ ((r >> 2) & 3)) ----
   const int swz = (l31 >> 2) & 3;

@@ -29,6 +29,7 @@
 #include "common.hpp"
 #include "gemm_route.hpp"
 #include "lds_async.hpp"
+#include "two_plane.hpp"
 
 #include <stdlib.h>
 
@@ -41,15 +42,6 @@ constexpr int WS_AMAX_OFF = WS_BIAS_OFF + 1024;     // the workgroup's magnitude
 constexpr int WS_TURN_OFF = WS_AMAX_OFF + 64;       // eight waves x 2 KiB: 32 rows x 64 bytes turned row-major for the stores
 constexpr int WS_LDS_BYTES = WS_TURN_OFF + 8 * 2048;
 static_assert(WS_LDS_BYTES <= 160 * 1024, "weight-stationary kernel LDS budget");
-__device__ __forceinline__ float ws_act_bwd(const float y, const int act) {  // (gemm.hip: act_bwd)
-  if (act == MML_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  if (act == MML_ACT_SIGMOID) return y * (1.f - y);
-  if (act == MML_ACT_SIGMOID2) {
-    const float s_ = 0.5f * y;
-    return 2.f * s_ * (1.f - s_);
-  }
-  return 1.f;
-}
 struct WsProblem {
   const float* A;          // [M, Kred] activations (forward) / output gradients (input gradient)
   const uint32_t* amaxA;   // magnitude slot of A
@@ -78,21 +70,6 @@ struct WsLaunch {
   WsProblem p[MML_MAX_GROUP];
 };
 static_assert(sizeof(WsLaunch) <= 4096, "WsLaunch must fit the kernel-argument block");
-
-__device__ __forceinline__ uint32_t ws_amax_load(const uint32_t* p) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < MML_AMAX_WORDS; ++i) m = p[i] > m ? p[i] : m;
-  return m;
-}
-// (the rule of gemm.hip: |x| 2^k < 2^15 for every |x| <= the slot's value; Inf / NaN: scale 1)
-__device__ __forceinline__ int ws_scale_exp(uint32_t bits) {
-  const int e = (int)((bits >> 23) & 0xffu);
-  if (e == 255) return 0;
-  const int k = 141 - e;
-  return k > 110 ? 110 : (k < -110 ? -110 : k);
-}
-__device__ __forceinline__ float ws_pow2(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
 
 // MODE 0: forward (bias, ReLU, sign mask out when MASKS); MODE 1: input gradient (sign mask in when MASKS, accumulation)
 // K7: forward with the product epilogue / input gradient in gate mode (see the head of this file)
@@ -133,10 +110,10 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(const WsLaunch L) {
   }
   __syncthreads();
 
-  const int kA = __builtin_amdgcn_readfirstlane(ws_scale_exp(ws_amax_load(P.amaxA)));
+  const int kA = __builtin_amdgcn_readfirstlane(scale_exp_of(amax_slot(P.amaxA)));
   const int kB = __builtin_amdgcn_readfirstlane(*P.kexp);
-  const float sA = ws_pow2(kA);
-  const float inv = ws_pow2(-kA) * ws_pow2(-kB);
+  const float sA = pow2f(kA);
+  const float inv = pow2f(-kA) * pow2f(-kB);
 
   const int nrb = (M + 31) >> 5;
   const int stride = L.wg_per_prob * 8;
@@ -251,13 +228,13 @@ __global__ __launch_bounds__(512, 2) void gemm_ws_kernel(const WsLaunch L) {
               float4 e0 = make_float4(q0.x * m0.x, q0.y * m0.y, q0.z * m0.z, q0.w * m0.w);
               float4 e1 = make_float4(q1.x * m1.x, q1.y * m1.y, q1.z * m1.z, q1.w * m1.w);
               if (a2 != MML_ACT_NONE) {
-                e0.x *= ws_act_bwd(g0.x, a2); e0.y *= ws_act_bwd(g0.y, a2); e0.z *= ws_act_bwd(g0.z, a2); e0.w *= ws_act_bwd(g0.w, a2);
-                e1.x *= ws_act_bwd(g1.x, a2); e1.y *= ws_act_bwd(g1.y, a2); e1.z *= ws_act_bwd(g1.z, a2); e1.w *= ws_act_bwd(g1.w, a2);
+                e0.x *= act_bwd(g0.x, a2); e0.y *= act_bwd(g0.y, a2); e0.z *= act_bwd(g0.z, a2); e0.w *= act_bwd(g0.w, a2);
+                e1.x *= act_bwd(g1.x, a2); e1.y *= act_bwd(g1.y, a2); e1.z *= act_bwd(g1.z, a2); e1.w *= act_bwd(g1.w, a2);
               }
-              q0.x *= g0.x * ws_act_bwd(m0.x, a1); q0.y *= g0.y * ws_act_bwd(m0.y, a1);
-              q0.z *= g0.z * ws_act_bwd(m0.z, a1); q0.w *= g0.w * ws_act_bwd(m0.w, a1);
-              q1.x *= g1.x * ws_act_bwd(m1.x, a1); q1.y *= g1.y * ws_act_bwd(m1.y, a1);
-              q1.z *= g1.z * ws_act_bwd(m1.z, a1); q1.w *= g1.w * ws_act_bwd(m1.w, a1);
+              q0.x *= g0.x * act_bwd(m0.x, a1); q0.y *= g0.y * act_bwd(m0.y, a1);
+              q0.z *= g0.z * act_bwd(m0.z, a1); q0.w *= g0.w * act_bwd(m0.w, a1);
+              q1.x *= g1.x * act_bwd(m1.x, a1); q1.y *= g1.y * act_bwd(m1.y, a1);
+              q1.z *= g1.z * act_bwd(m1.z, a1); q1.w *= g1.w * act_bwd(m1.w, a1);
               if (P.acc2) {
                 if (ok0) {
                   const float4 o = *reinterpret_cast<const float4*>(P.c2 + oc2);

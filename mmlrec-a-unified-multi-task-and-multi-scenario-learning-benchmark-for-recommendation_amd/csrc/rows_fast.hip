@@ -107,15 +107,6 @@ __device__ __forceinline__ float dot4(const float4& a, const float4& b) {
 __device__ __forceinline__ float4 mul4(const float4& a, const float4& b) {
   return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w);
 }
-__device__ __forceinline__ float act_bwd_rows(const float y, const int act) {  // (gemm.hip: act_bwd)
-  if (act == MML_ACT_RELU) return y > 0.f ? 1.f : 0.f;
-  if (act == MML_ACT_SIGMOID) return y * (1.f - y);
-  if (act == MML_ACT_SIGMOID2) {
-    const float s_ = 0.5f * y;
-    return 2.f * s_ * (1.f - s_);
-  }
-  return 1.f;
-}
 __device__ __forceinline__ void fma4(float4& acc, float s, const float4& v) {
   acc.x += s * v.x; acc.y += s * v.y; acc.z += s * v.z; acc.w += s * v.w;
 }
@@ -945,8 +936,8 @@ __global__ __launch_bounds__(FB) void head_fast_kernel(const mml_head_group g, c
               fma4(dwacc[t], dlogit, mul4(hv, gv));
               float4 dg = mul4(dh, hv);
               if (d.gate_act != MML_ACT_NONE) {
-                dg.x *= act_bwd_rows(gv.x, d.gate_act); dg.y *= act_bwd_rows(gv.y, d.gate_act);
-                dg.z *= act_bwd_rows(gv.z, d.gate_act); dg.w *= act_bwd_rows(gv.w, d.gate_act);
+                dg.x *= act_bwd(gv.x, d.gate_act); dg.y *= act_bwd(gv.y, d.gate_act);
+                dg.z *= act_bwd(gv.z, d.gate_act); dg.w *= act_bwd(gv.w, d.gate_act);
               }
               dh = mul4(dh, gv);
               if (valid) {

@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "lds_async.hpp"
 #include "reduce.hpp"
+#include "two_plane.hpp"
 
 #include <stdlib.h>
 
@@ -64,20 +65,6 @@ struct ThLaunch {
   ThProblem p[TH_MAX];
 };
 static_assert(sizeof(ThLaunch) <= 4096, "ThLaunch must fit the kernel-argument block");
-
-__device__ __forceinline__ uint32_t th_amax_load(const uint32_t* p) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int i = 0; i < MML_AMAX_WORDS; ++i) m = p[i] > m ? p[i] : m;
-  return m;
-}
-__device__ __forceinline__ int th_scale_exp(uint32_t bits) {  // (gemm.hip's rule: |x| 2^k < 2^15)
-  const int e = (int)((bits >> 23) & 0xffu);
-  if (e == 255) return 0;
-  const int k = 141 - e;
-  return k > 110 ? 110 : (k < -110 ? -110 : k);
-}
-__device__ __forceinline__ float th_pow2(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }
 
 // NS: tower width / 32 (the head's H), NS2: tower input width / 32
 // KINDS: some task has a non-zero kind (include/mmlrec.h K5; chosen on the host).  A workgroup serves ONE task, so its kind
@@ -129,11 +116,11 @@ __global__ __launch_bounds__(512, 2) void tower_head_kernel(const ThLaunch L) {
   }
   __syncthreads();
 
-  const int kA = __builtin_amdgcn_readfirstlane(th_scale_exp(th_amax_load(P.amaxA)));
+  const int kA = __builtin_amdgcn_readfirstlane(scale_exp_of(amax_slot(P.amaxA)));
   const int kF = __builtin_amdgcn_readfirstlane(*P.kexpF);
   const int kB = __builtin_amdgcn_readfirstlane(*P.kexpB);
-  const float sA = th_pow2(kA);
-  const float invF = th_pow2(-kA) * th_pow2(-kF);
+  const float sA = pow2f(kA);
+  const float invF = pow2f(-kA) * pow2f(-kF);
   float hb = P.hbias[0];
   for (int i = 0; i < P.n_hbias2; ++i) hb += P.hbias2[i];
 
@@ -271,9 +258,9 @@ __global__ __launch_bounds__(512, 2) void tower_head_kernel(const ThLaunch L) {
       am_dh = fmaxf(am_dh, amb);
 #pragma unroll
       for (int o = 32; o > 0; o >>= 1) amb = fmaxf(amb, __shfl_xor(amb, o, 64));
-      const int kD = __builtin_amdgcn_readfirstlane(th_scale_exp(__float_as_uint(amb)));
-      const float sD = th_pow2(kD);
-      const float invB = th_pow2(-kD) * th_pow2(-kB);
+      const int kD = __builtin_amdgcn_readfirstlane(scale_exp_of(__float_as_uint(amb)));
+      const float sD = pow2f(kD);
+      const float invB = pow2f(-kD) * pow2f(-kB);
       // ---- dH to memory (the tower's weight gradient reads it): row-major through the wave's turn area
       const int tR = lane >> 2, tc = lane & 3;
       const int64_t orow = rb * 32 + tR;

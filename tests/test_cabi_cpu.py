@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, load_golden
+from two_plane_refs import kexp, planes as image, slot
 
 RTOL = 1e-4
 
@@ -72,33 +73,6 @@ def test_cpu_library_planes_cut_layout(cpu):
     kernel to the same numpy image.)"""
     lib, L = cpu
     rng = np.random.default_rng(4)
-
-    def slot(v):
-        s = np.zeros(8, dtype=np.uint32)
-        s[3] = np.float32(v).view(np.uint32)
-        return s
-
-    def kexp(v):
-        e = (np.float32(v).view(np.uint32) >> 23) & 0xff
-        return int(np.clip(141 - int(e), -110, 110))
-
-    def image(W, k, layout):
-        y = W.astype(np.float32) * np.float32(2.0 ** k)
-        h = y.astype(np.float16)
-        lo = (y - h.astype(np.float32)).astype(np.float16)
-        hb, lb = h.view(np.uint16).astype(np.uint32), lo.view(np.uint16).astype(np.uint32)
-        if layout == 1:
-            hb, lb = hb.T, lb.T
-        out = np.zeros(hb.shape, dtype=np.uint32)
-        S = [[4 * hh + (e & 3) + 8 * (e >> 2) for e in range(8)] for hh in range(2)]
-        for b in range(hb.shape[1] // 16):
-            bh, bl = hb[:, 16 * b:16 * b + 16], lb[:, 16 * b:16 * b + 16]
-            for hh in range(2):
-                for i in range(4):
-                    k0, k1 = S[hh][2 * i], S[hh][2 * i + 1]
-                    out[:, 16 * b + 4 * hh + i] = bh[:, k0] | (bh[:, k1] << 16)
-                    out[:, 16 * b + 8 + 4 * hh + i] = bl[:, k0] | (bl[:, k1] << 16)
-        return out.T.copy() if layout == 1 else out
 
     N, K, KP = 48, 72, 80
     W = (rng.standard_normal((N, K)) * 3e-4).astype(np.float32)

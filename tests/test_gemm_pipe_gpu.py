@@ -11,6 +11,8 @@ import os
 import numpy as np
 import pytest
 
+from two_plane_refs import kexp, planes as planes_ref
+
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
 
@@ -326,39 +328,6 @@ def test_amax_of_fallback_kernel_and_nonfinite(env):
     assert not torch.isfinite(C2[3]).all() and torch.isfinite(C2[4]).all()
 
 
-def _cut_ref(W, k):
-    """numpy restatement of the two-plane cut (csrc/lds_async.hpp, csrc/gemm.hip: planes_cut_kernel): h = rne16(w 2^k),
-    l = rne16(w 2^k - h), as uint16 bit patterns."""
-    y = W.astype(np.float32) * np.float32(2.0 ** k)
-    h = y.astype(np.float16)
-    l = (y - h.astype(np.float32)).astype(np.float16)
-    return h.view(np.uint16).astype(np.uint32), l.view(np.uint16).astype(np.uint32)
-
-
-def _planes_ref(W, k, layout):
-    """Expected plane image (include/mmlrec.h: mml_gemm_planes_cut): per block of 16 along the reduction, word 4h + i =
-    h-plane halves (S_h[2i], S_h[2i+1]), word 8 + 4h + i = the same of the l plane, S_h = (4h..4h+3, 8+4h..8+4h+3)."""
-    hb, lb = _cut_ref(W, k)
-    if layout == 1:
-        hb, lb = hb.T, lb.T  # reduction down the rows: work on the transpose, transpose back
-    R, Cn = hb.shape
-    out = np.zeros((R, Cn), dtype=np.uint32)
-    S = [[4 * h + (e & 3) + 8 * (e >> 2) for e in range(8)] for h in range(2)]
-    for b in range(Cn // 16):
-        blk_h, blk_l = hb[:, 16 * b:16 * b + 16], lb[:, 16 * b:16 * b + 16]
-        for h in range(2):
-            for i in range(4):
-                k0, k1 = S[h][2 * i], S[h][2 * i + 1]
-                out[:, 16 * b + 4 * h + i] = blk_h[:, k0] | (blk_h[:, k1] << 16)
-                out[:, 16 * b + 8 + 4 * h + i] = blk_l[:, k0] | (blk_l[:, k1] << 16)
-    return out.T.copy() if layout == 1 else out
-
-
-def _kexp(amax):
-    e = (np.float32(amax).view(np.uint32) >> 23) & 0xff
-    return int(np.clip(141 - int(e), -110, 110))
-
-
 @pytest.mark.parametrize("scale_w", [1e-4, 1.0, 3e5])
 def test_planes_cut_image_and_exponent(env, scale_w):
     """mml_gemm_planes_cut against the numpy restatement: both layouts, a pitched weight, a group of two magnitudes."""
@@ -380,13 +349,13 @@ def test_planes_cut_image_and_exponent(env, scale_w):
                     (W, pc, ops.PLANES_COLS, [slots[0], slots[1]], kx[1:2]),   # group of two: the larger magnitude rules
                     (W2, p2, ops.PLANES_COLS, [slots[1], slots[0]], kx[2:3])])
     torch.cuda.synchronize()
-    k_own = _kexp(float(W.abs().max()))
-    k_grp = min(k_own, _kexp(float(W2.abs().max())))
+    k_own = kexp(float(W.abs().max()))
+    k_grp = min(k_own, kexp(float(W2.abs().max())))
     assert kx.tolist() == [k_own, k_grp, k_grp]
     Wn = W.cpu().numpy()
-    assert np.array_equal(pr.cpu().numpy().view(np.uint32), _planes_ref(Wn, k_own, 0))
-    assert np.array_equal(pc.cpu().numpy().view(np.uint32), _planes_ref(Wn, k_grp, 1))
-    assert np.array_equal(p2.cpu().numpy().view(np.uint32), _planes_ref(W2.cpu().numpy(), k_grp, 1))
+    assert np.array_equal(pr.cpu().numpy().view(np.uint32), planes_ref(Wn, k_own, 0))
+    assert np.array_equal(pc.cpu().numpy().view(np.uint32), planes_ref(Wn, k_grp, 1))
+    assert np.array_equal(p2.cpu().numpy().view(np.uint32), planes_ref(W2.cpu().numpy(), k_grp, 1))
     with pytest.raises(L.MMLError):  # reduction extent not a multiple of 16 and no room for the rounded-up block
         ops.planes_cut([(W[:, :72], torch.zeros(N, 72, dtype=torch.int32, device=dev), ops.PLANES_ROWS, [slots[0]], kx[0:1])])
     with pytest.raises(L.MMLError):  # reduction down the rows: the row count must be a multiple of 16
@@ -399,8 +368,8 @@ def test_planes_cut_image_and_exponent(env, scale_w):
     torch.cuda.synchronize()
     Wpad = np.zeros((N, 80), dtype=np.float32)
     Wpad[:, :72] = Wr.cpu().numpy()
-    assert np.array_equal(pp.cpu().numpy().view(np.uint32), _planes_ref(Wpad, k_own, 0))
-    assert np.array_equal(pq.cpu().numpy().view(np.uint32), _planes_ref(Wpad, k_own, 1))
+    assert np.array_equal(pp.cpu().numpy().view(np.uint32), planes_ref(Wpad, k_own, 0))
+    assert np.array_equal(pq.cpu().numpy().view(np.uint32), planes_ref(Wpad, k_own, 1))
 
 
 @pytest.mark.parametrize("M,K,Ns", [(1000, 240, [256, 256, 64]), (70000, 128, [128, 128]), (300, 32, [128, 4]),

@@ -4,7 +4,7 @@ mml_star_linear_bwd -- against the cut of the materialised product (bit for bit)
 import numpy as np
 import pytest
 
-from test_gemm_pipe_gpu import _kexp, _planes_ref
+from two_plane_refs import kexp, planes as planes_ref
 
 pytestmark = pytest.mark.gpu
 RTOL = 2e-6
@@ -54,14 +54,14 @@ def test_product_planes_are_the_planes_of_the_fp32_product(env, scale):
     f32 = np.float32
     bw = f32(float(Wa.abs().max())) * f32(float(Wb.abs().max()))
     bv = f32(float(Va.abs().max())) * f32(float(Vb.abs().max()))
-    k_own = _kexp(bw)
-    k_grp = min(k_own, _kexp(bv))
+    k_own = kexp(bw)
+    k_grp = min(k_own, kexp(bv))
     assert kx.tolist() == [k_own, k_grp, k_grp]
     P = (Wa * Wb).cpu().numpy()       # the fp32 product
     Q = (Va * Vb).cpu().numpy()
-    assert np.array_equal(pr.cpu().numpy().view(np.uint32), _planes_ref(P, k_own, 0))
-    assert np.array_equal(pc.cpu().numpy().view(np.uint32), _planes_ref(P, k_grp, 1))
-    assert np.array_equal(pv.cpu().numpy().view(np.uint32), _planes_ref(Q, k_grp, 1))
+    assert np.array_equal(pr.cpu().numpy().view(np.uint32), planes_ref(P, k_own, 0))
+    assert np.array_equal(pc.cpu().numpy().view(np.uint32), planes_ref(P, k_grp, 1))
+    assert np.array_equal(pv.cpu().numpy().view(np.uint32), planes_ref(Q, k_grp, 1))
     # the same planes as the cut of the stored product under the same exponent: force it by giving the product's cut a
     # slot that holds the bound
     bound = ops.amax_slots(1, dev)
